@@ -5,6 +5,7 @@ probabilistic ODE solve, FitzHugh-Nagumo n_vars=2 q(n_deriv)=3, 4000 steps, `sol
 1024 trajectories per GPU (BASELINE.json configs[1]; SURVEY.md section 8d "C2").
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns its own N rank processes)
+    python bench.py ... --dump-outputs DIR                        (also writes the last timed solve's results, dump_outputs())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W                  (the driver's launch: RANK / WORLD_SIZE from the env)
 
@@ -146,6 +147,31 @@ def cpu_baseline(W, x0, theta, prior, budget_s=14.0):
     return out
 
 
+DUMP_SAMPLE, DUMP_SEED = 32, 20241
+
+
+def dump_outputs(plan, out_dir):
+    """
+    The arrays a caller of the timed path receives from its last solve (SolvePlan.state_host(): smoothed mean
+    (B, N+1, n_block, n_bstate) and variance (B, N+1, n_block, n_bstate, n_bstate), float64), written as DIR/<name>.npy.
+    The whole result is 0.8 GB, so what is written is: every trajectory at t_max, and all time points of a fixed seeded
+    sample of DUMP_SAMPLE trajectories (their indices in `sample_traj_index`) -- about 25 MB in all.
+    """
+    mean, var = plan.state_host()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(mean.shape[0], min(DUMP_SAMPLE, mean.shape[0]), replace=False))
+    arrays = {
+        "mean_state_final": mean[:, -1], "var_state_final": var[:, -1],
+        "mean_state_sample": mean[idx], "var_state_sample": var[idx],
+        "sample_traj_index": idx.astype(np.float64),
+    }
+    total = sum(a.size * 8 for a in arrays.values())
+    assert total <= 64 << 20, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays), total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,7 +182,11 @@ def main():
     ap.add_argument("--comm", choices=["rccl", "host"], default="rccl", help="N > 1: what carries the barriers")
     ap.add_argument("--allow-host-fallback", action="store_true",
                     help="N > 1 on a box with N GPUs: keep going on the host channel when RCCL does not come up (default: exit 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed solve computed (rank 0's trajectories) to DIR/<name>.npy, see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # own launcher: N rank processes of this script, started before anything here has touched a GPU
         from rodeo_amd import hostgroup
@@ -244,6 +274,10 @@ def main():
     # sanity on the result of the timed computation (cheap): finite, end conditions
     last = plan.var_state.slice0_host(-1)                      # state at t_max (tile layout: [Sigma | mu] rows)
     ok = bool(np.all(np.isfinite(last)))
+
+    if rank == 0 and args.dump_outputs:
+        names, nbytes = dump_outputs(plan, args.dump_outputs)
+        print(f"dumped {', '.join(names)} ({nbytes / 2**20:.1f} MB) to {args.dump_outputs}", file=sys.stderr)
 
     if rank == 0:
         units = N_TRAJ * N_STEPS                                  # trajectory-steps per launch per rank
