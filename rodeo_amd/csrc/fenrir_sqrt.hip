@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "kalman_small.hpp"
 #include "solve_args.hpp"
+#include "solve_paths.hpp"
 #include "sqrt_small.hpp"
 
 namespace rk {
@@ -245,29 +246,21 @@ int fenrir_sqrt_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, c
     const dim3 grid(div_up(a.B * a.D, 64)), block(64);
     {
         LaunchTimer t(h, "fenrir_bwd_sqrt_kernel");
-#define RK_FS(P_, M_)                                                                                                      \
-    if (c->n_bstate == P_ && n_bobs == M_) {                                                                             \
-        if (states) hipLaunchKernelGGL((fenrir_bwd_sqrt_kernel<P_, true, M_>), grid, block, 0, h->stream, a, obs, obs_w, obs_v, obs_ind, n_obs, logdens, states); \
-        else hipLaunchKernelGGL((fenrir_bwd_sqrt_kernel<P_, false, M_>), grid, block, 0, h->stream, a, obs, obs_w, obs_v, obs_ind, n_obs, logdens, states); \
-    }
-        RK_FS(2, 1) RK_FS(2, 2) RK_FS(2, 3) RK_FS(3, 1) RK_FS(3, 2) RK_FS(3, 3) RK_FS(4, 1) RK_FS(4, 2) RK_FS(4, 3)
-        RK_FS(5, 1) RK_FS(5, 2) RK_FS(5, 3) RK_FS(6, 1) RK_FS(6, 2) RK_FS(6, 3)
-        RK_FS(7, 1) RK_FS(7, 2) RK_FS(7, 3) RK_FS(8, 1) RK_FS(8, 2) RK_FS(8, 3)        // (functional: the stacks spill from n_bstate = 7 on)
-#undef RK_FS
+        // (functional: the stacks spill from n_bstate = 7 on)
+        dispatch_int<2, 8>(c->n_bstate, [&](auto P) {
+            dispatch_int<1, 3>(n_bobs, [&](auto M) {
+                if (states) hipLaunchKernelGGL((fenrir_bwd_sqrt_kernel<P, true, M>), grid, block, 0, h->stream, a, obs, obs_w, obs_v, obs_ind, n_obs, logdens, states);
+                else hipLaunchKernelGGL((fenrir_bwd_sqrt_kernel<P, false, M>), grid, block, 0, h->stream, a, obs, obs_w, obs_v, obs_ind, n_obs, logdens, states);
+            });
+        });
         t.stop();
     }
     RK_HIP(hipGetLastError());
     if (!states) return RK_OK;
     LaunchTimer t(h, "fenrir_smooth_sqrt_kernel");
-    switch (c->n_bstate) {
-        case 2: hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<2>, grid, block, 0, h->stream, a, states); break;
-        case 3: hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<3>, grid, block, 0, h->stream, a, states); break;
-        case 4: hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<4>, grid, block, 0, h->stream, a, states); break;
-        case 5: hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<5>, grid, block, 0, h->stream, a, states); break;
-        case 6: hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<6>, grid, block, 0, h->stream, a, states); break;
-        case 7: hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<7>, grid, block, 0, h->stream, a, states); break;
-        default: hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<8>, grid, block, 0, h->stream, a, states); break;
-    }
+    dispatch_int<2, 8>(c->n_bstate, [&](auto P) {
+        hipLaunchKernelGGL(fenrir_smooth_sqrt_kernel<P>, grid, block, 0, h->stream, a, states);
+    });
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;

@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "solve_args.hpp"
 #include "solve_dense_itg_kernels.hpp"
+#include "solve_paths.hpp"
 #include "build/embedded_sources.inc"
 
 namespace rk {
@@ -70,24 +71,24 @@ static bool hiprtc_takes_backend_options() {
     return v != 0;
 }
 
-static std::string kernel_expr(const UserRhs& u, int P, int itg, int kind) {
+static std::string kernel_expr(const UserRhs& u, int P, int itg, JitKind kind) {
     char buf[512];
     (void)u;   // the user's type is aliased to rk::UserRhsT inside the translation unit (it may be a template-id)
-    if (kind == 2) snprintf(buf, sizeof buf, "rk::interrogate_kernel<rk::UserRhsT, %d, %d>", P, itg);
-    else if (kind == 10) snprintf(buf, sizeof buf, "rk::interrogate_kernel_m<rk::UserRhsT, %d, %d>", P, itg);      // n_bmeas > 1, standalone
-    else if (kind == 3) snprintf(buf, sizeof buf, "rk::fwd_tile3_kernel<rk::UserRhsT, %d>", itg);      // MFMA-tile forward, p = 3
-    else if (kind == 4) snprintf(buf, sizeof buf, "rk::fwd_tile4_kernel<rk::UserRhsT, %d>", itg);      // MFMA-tile forward, p = 4
-    else if (kind == 7 || kind == 8)                                                                        // n_bmeas > 1
-        snprintf(buf, sizeof buf, "rk::fwd_kernel_m<rk::UserRhsT, %d, %d, %s>", P, itg, kind == 8 ? "true" : "false");
-    else if (kind == 6) snprintf(buf, sizeof buf, "rk::fwd_sqrt_kernel<rk::UserRhsT, %d, %d>", P, itg);   // square-root filter
-    else if (kind == 9) snprintf(buf, sizeof buf, "rk::dense_interrogate_kernel<rk::UserRhsT::Inner, %d, %d>", P, itg);   // dense path
-    else if (kind == 5) snprintf(buf, sizeof buf, "rk::fwd_tilen_kernel<rk::UserRhsT, %d, %d>", itg, P); // blocked tiles, P here = NB
-    else snprintf(buf, sizeof buf, "rk::fwd_kernel<rk::UserRhsT, %d, %d, %s>", P, itg, kind == 1 ? "true" : "false");
+    if (kind == JIT_ITG) snprintf(buf, sizeof buf, "rk::interrogate_kernel<rk::UserRhsT, %d, %d>", P, itg);
+    else if (kind == JIT_ITG_M) snprintf(buf, sizeof buf, "rk::interrogate_kernel_m<rk::UserRhsT, %d, %d>", P, itg);   // standalone
+    else if (kind == JIT_TILE3) snprintf(buf, sizeof buf, "rk::fwd_tile3_kernel<rk::UserRhsT, %d>", itg);
+    else if (kind == JIT_TILE4) snprintf(buf, sizeof buf, "rk::fwd_tile4_kernel<rk::UserRhsT, %d>", itg);
+    else if (kind == JIT_FWD_M || kind == JIT_FWD_M_STORE_PRED)
+        snprintf(buf, sizeof buf, "rk::fwd_kernel_m<rk::UserRhsT, %d, %d, %s>", P, itg, kind == JIT_FWD_M_STORE_PRED ? "true" : "false");
+    else if (kind == JIT_SQRT) snprintf(buf, sizeof buf, "rk::fwd_sqrt_kernel<rk::UserRhsT, %d, %d>", P, itg);
+    else if (kind == JIT_DENSE_ITG) snprintf(buf, sizeof buf, "rk::dense_interrogate_kernel<rk::UserRhsT::Inner, %d, %d>", P, itg);
+    else if (kind == JIT_TILEN) snprintf(buf, sizeof buf, "rk::fwd_tilen_kernel<rk::UserRhsT, %d, %d>", itg, P);  // P here = NB
+    else snprintf(buf, sizeof buf, "rk::fwd_kernel<rk::UserRhsT, %d, %d, %s>", P, itg, kind == JIT_FWD_STORE_PRED ? "true" : "false");
     return buf;
 }
 
 // compile one instantiation; returns code object in `code` and the mangled name in `lowered`
-static int jit_compile(const UserRhs& u, int P, int itg, int kind, std::vector<char>& code, std::string& lowered) {
+static int jit_compile(const UserRhs& u, int P, int itg, JitKind kind, std::vector<char>& code, std::string& lowered) {
     const std::string src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n"
                                         "#include \"solve_tile3_kernels.hpp\"\n#include \"solve_tile4_kernels.hpp\"\n"
                                         "#include \"solve_tilen_kernels.hpp\"\n#include \"solve_sqrt_kernels.hpp\"\n"
@@ -139,7 +140,7 @@ static int jit_compile(const UserRhs& u, int P, int itg, int kind, std::vector<c
 struct JitCode { int rc; std::vector<char> code; std::string lowered; std::string error; };
 static std::map<std::tuple<int, int, int, int>, JitCode> g_code;
 
-static const JitCode& jit_code_locked(int rhs_id, int P, int itg, int kind) {
+static const JitCode& jit_code_locked(int rhs_id, int P, int itg, JitKind kind) {
     const auto key = std::make_tuple(rhs_id, P, itg, kind);
     auto it = g_code.find(key);
     if (it == g_code.end()) {
@@ -151,7 +152,7 @@ static const JitCode& jit_code_locked(int rhs_id, int P, int itg, int kind) {
     return it->second;
 }
 
-static int jit_get(rk_handle h, int rhs_id, int P, int itg, int kind, hipFunction_t* fn) {
+static int jit_get(rk_handle h, int rhs_id, int P, int itg, JitKind kind, hipFunction_t* fn) {
     std::lock_guard<std::mutex> lk(g_mu);
     const int idx = rhs_id - RK_RHS_USER_BASE;
     RK_REQUIRE(idx >= 0 && idx < (int)g_rhs.size(), RK_ERR_INVALID, "unknown user rhs_id %d", rhs_id);
@@ -176,27 +177,28 @@ static int jit_get(rk_handle h, int rhs_id, int P, int itg, int kind, hipFunctio
     return RK_OK;
 }
 
+// The P key of a tile kernel's hiprtc build: the tile kind itself, or for the blocked tile kernel (solve_tilen_kernels.hpp)
+// its instance NB = 1 (p = 4) / 2 (p = 5 .. 8).
+static int tile_pkey(const rk_solve_cfg* c, JitKind tile) { return tile == JIT_TILEN ? (c->n_bstate <= 4 ? 1 : 2) : tile; }
+
 // Does the MFMA-tile forward kernel exist for this user right-hand side and configuration?  (It needs NDEP == 1 and a
 // block count the tile kernels support; decided by compiling it once -- cached -- so that rk_solve_layout and the
-// solve agree.)  which = 3 / 4 for n_bstate = 3 / 4.
-bool user_tile_available(const rk_solve_cfg* c, int which) {
+// solve agree.)  tile = JIT_TILE3 / JIT_TILE4 for n_bstate = 3 / 4, JIT_TILEN for the blocked tiles.
+bool user_tile_available(const rk_solve_cfg* c, JitKind tile) {
     std::lock_guard<std::mutex> lk(g_mu);
     const int idx = c->rhs_id - RK_RHS_USER_BASE;
     if (idx < 0 || idx >= (int)g_rhs.size()) return false;
     const int nb = g_rhs[idx].n_block;
     if (c->n_block != nb || c->n_bmeas != 1 || g_rhs[idx].n_bmeas != 1 || c->kalman_type != RK_KALMAN_STANDARD) return false;
-    if (nb < 1 || nb > (which == 4 ? 4 : 64)) return false;      // p = 3 and blocked tiles: up to 64 blocks (4 per wave, LDS exchange); p = 4: one wave
-    // which = 5: the blocked tile kernel (solve_tilen_kernels.hpp), instantiated per NB = 1 (p = 4) / 2 (p = 5 .. 8)
-    const int pkey = which == 5 ? (c->n_bstate <= 4 ? 1 : 2) : which;
-    const JitCode& jc = jit_code_locked(c->rhs_id, pkey, c->interrogate, which);
-    if (jc.rc && getenv("RK_JIT_VERBOSE")) fprintf(stderr, "[rk] tile kernel not available for user rhs %d (p = %d): %s\n", c->rhs_id, which, jc.error.c_str());
+    if (nb < 1 || nb > (tile == JIT_TILE4 ? 4 : 64)) return false;      // p = 3 and blocked tiles: up to 64 blocks (4 per wave, LDS exchange); p = 4: one wave
+    const JitCode& jc = jit_code_locked(c->rhs_id, tile_pkey(c, tile), c->interrogate, tile);
+    if (jc.rc && getenv("RK_JIT_VERBOSE")) fprintf(stderr, "[rk] tile kernel not available for user rhs %d (p = %d): %s\n", c->rhs_id, (int)tile, jc.error.c_str());
     return jc.rc == RK_OK;
 }
 
-int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int which) {
+int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, JitKind tile) {
     hipFunction_t fn;
-    const int pkey = which == 5 ? (c->n_bstate <= 4 ? 1 : 2) : which;
-    int rc = jit_get(h, c->rhs_id, pkey, c->interrogate, which, &fn);
+    int rc = jit_get(h, c->rhs_id, tile_pkey(c, tile), c->interrogate, tile, &fn);
     if (rc) return rc;
     SolveArgs args = a;
     int P = c->n_bstate;
@@ -205,7 +207,7 @@ int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, do
     const int nw = c->n_block <= 4 ? 1 : (c->n_block + 3) / 4;     // waves per workgroup (TileWaves<D>)
     const int grid = nw == 1 ? div_up(a.B * c->n_block, tpw) : a.B;
     launch_placement_primer(h, dim3(grid), dim3(64 * nw));
-    LaunchTimer t(h, which == 3 ? "fwd_tile3_kernel<user>" : (which == 4 ? "fwd_tile4_kernel<user>" : "fwd_tilen_kernel<user>"));
+    LaunchTimer t(h, tile == JIT_TILE3 ? "fwd_tile3_kernel<user>" : (tile == JIT_TILE4 ? "fwd_tile4_kernel<user>" : "fwd_tilen_kernel<user>"));
     RK_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, 64 * nw, 1, 1, 0, h->stream, params, nullptr));
     t.stop();
     return RK_OK;
@@ -223,7 +225,7 @@ int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
                    c->n_block, c->n_bmeas);
     }
     hipFunction_t fn;
-    int rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, 6, &fn);
+    int rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, JIT_SQRT, &fn);
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args};
@@ -265,7 +267,7 @@ bool user_dense_wanted(const rk_solve_cfg* c) {
 
 int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a) {
     hipFunction_t fn;
-    int rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, 9, &fn);
+    int rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, JIT_DENSE_ITG, &fn);
     if (rc) return rc;
     DenseItgArgs args = a;
     void* params[] = {&args};
@@ -278,7 +280,7 @@ int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     if (rc) return rc;
     hipFunction_t fn;
     const bool sp = (c->flags & RK_FLAG_STORE_PRED) != 0;
-    rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, user_n_bmeas(c->rhs_id) > 1 ? (sp ? 8 : 7) : (sp ? 1 : 0), &fn);
+    rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, user_n_bmeas(c->rhs_id) > 1 ? (sp ? JIT_FWD_M_STORE_PRED : JIT_FWD_M) : (sp ? JIT_FWD_STORE_PRED : JIT_FWD), &fn);
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args};
@@ -296,7 +298,7 @@ int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, dou
     RK_REQUIRE(!multi || c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED,
                "rk_interrogate_batched: n_bmeas > 1 with kalman_type = square-root is fused into the solvers only");
     hipFunction_t fn;
-    rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, multi ? 10 : 2, &fn);
+    rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, multi ? JIT_ITG_M : JIT_ITG, &fn);
     if (rc) return rc;
     SolveArgs args = a;
     int sqrt_mode = c->kalman_type == RK_KALMAN_SQRT ? 1 : 0;
@@ -338,8 +340,8 @@ int rk_rhs_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) 
     std::vector<char> code;
     std::string lowered;
     const bool dense = u.n_block == 1 && u.n_bmeas > 1 && (n_bstate > 9 || u.n_bmeas > 4);      // (user_dense_wanted)
-    int rc = jit_compile(u, n_bstate, interrogate, dense ? 9 : (u.n_bmeas > 1 ? 7 : 0), code, lowered);
-    if (rc == RK_OK && !dense && u.n_bmeas > 1) rc = jit_compile(u, n_bstate, interrogate, 10, code, lowered);     // + the standalone interrogation
+    int rc = jit_compile(u, n_bstate, interrogate, dense ? JIT_DENSE_ITG : (u.n_bmeas > 1 ? JIT_FWD_M : JIT_FWD), code, lowered);
+    if (rc == RK_OK && !dense && u.n_bmeas > 1) rc = jit_compile(u, n_bstate, interrogate, JIT_ITG_M, code, lowered);     // + the standalone interrogation
     return rc;
 }
 

@@ -41,6 +41,7 @@
 #include "linalg_small.hpp"
 #include "solve_args.hpp"
 #include "solve_dense_itg_kernels.hpp"
+#include "solve_paths.hpp"
 #include "philox.hpp"
 
 namespace rk {
@@ -1665,10 +1666,6 @@ __global__ void __launch_bounds__(DT) dense_bwd_sim_kernel(DenseArgs a) {
 #include "solve_dense_ops.hpp"
 
 namespace rk {
-
-bool is_user_rhs(int rhs_id);
-bool user_dense_wanted(const rk_solve_cfg* c);
-int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a);
 
 // The built-in linear ODE of config 5, and any hiprtc right-hand side in the non-block form (one block, several
 // measurements) beyond what the lane-per-trajectory kernels take (rhs_jit.hip: n_bstate > 9 or n_bmeas > 4).

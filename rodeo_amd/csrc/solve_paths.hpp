@@ -1,0 +1,124 @@
+// Host-side solver API shared by the translation units of librodeo_kalman.so (host code only, not part of the hiprtc set):
+// the functions one .hip file calls in another, the one rule that picks a configuration's device path, and the helpers
+// that turn run-time sizes / ids into template instances at the launch sites.
+#pragma once
+#include <stdint.h>
+#include <stddef.h>
+#include <type_traits>
+#include <utility>
+#include "common.hpp"
+#include "rhs.hpp"
+#include "solve_args.hpp"
+
+namespace rk {
+
+struct DenseItgArgs;
+struct SimLogpost;
+
+// ---- dense large-block path (solve_dense.hip) ----------------------------------------------------------------------
+bool dense_supported(const rk_solve_cfg* c, int mode);
+int dense_check(const rk_solve_cfg* c, const rk_solve_in* in, int mode);
+int dense_solve(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, int mode);
+size_t dense_ws_bytes(const rk_solve_cfg* c, int mode);
+
+// ---- user-supplied right-hand sides (rhs_jit.hip) ------------------------------------------------------------------
+// Kernel kinds of the hiprtc builds.  The values are keys of the JIT caches: do not renumber.
+enum JitKind : int {
+    JIT_FWD = 0,              // fwd_kernel<.., false>
+    JIT_FWD_STORE_PRED = 1,   // fwd_kernel<.., true>
+    JIT_ITG = 2,              // interrogate_kernel
+    JIT_TILE3 = 3,            // fwd_tile3_kernel
+    JIT_TILE4 = 4,            // fwd_tile4_kernel
+    JIT_TILEN = 5,            // fwd_tilen_kernel (P = NB)
+    JIT_SQRT = 6,             // fwd_sqrt_kernel
+    JIT_FWD_M = 7,            // fwd_kernel_m<.., false>   (n_bmeas > 1)
+    JIT_FWD_M_STORE_PRED = 8, // fwd_kernel_m<.., true>
+    JIT_DENSE_ITG = 9,        // dense_interrogate_kernel
+    JIT_ITG_M = 10,           // interrogate_kernel_m     (n_bmeas > 1)
+};
+bool is_user_rhs(int rhs_id);
+bool user_tile_available(const rk_solve_cfg* c, JitKind tile);
+int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, JitKind tile);
+int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
+int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
+int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
+                     const double* vp, double* wm, double* mm_, double* vm);
+bool user_dense_wanted(const rk_solve_cfg* c);
+int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a);
+
+// ---- fused square-root solver (solve_sqrt.hip) and fenrir in the square-root form (fenrir_sqrt.hip) ------------------
+int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, double* ws, size_t ws_bytes);
+size_t sqrt_ws_doubles(const rk_solve_cfg* c, int mode);
+size_t fenrir_sqrt_item_doubles(int p);
+int fenrir_sqrt_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* obs, const double* obs_w,
+                       const double* obs_v, const int32_t* obs_ind, int n_obs, int n_bobs, double* logdens, double* states);
+
+// ---- MFMA-tile paths: n_bstate = 3 (solve_tile3.hip), 4 (solve_tile4.hip), blocked 4 .. 8 (solve_tilen.hip) ----------
+bool tile3_supported(const rk_solve_cfg* c, int mode);
+int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp = nullptr);
+bool tile3_sim_logpost_supported(const rk_solve_cfg* c, int n_obs);
+int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, const double* obs,
+                            const int32_t* obs_ind, int n_obs, double noise_sd, const double* upars, int n_prior, double prior_sd,
+                            double* logpost);
+int tile3_fenrir_backward(rk_handle h, const SolveArgs& a, const double* tiles, const double* obs, const double* obs_w,
+                          const double* obs_v, const int32_t* obs_ind, int n_obs, double* logdens);
+bool tile4_supported(const rk_solve_cfg* c, int mode);
+int tile4_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode);
+size_t tile4_doubles(const rk_solve_cfg* c);
+bool tilen_supported(const rk_solve_cfg* c, int mode);
+int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, double* ws, size_t ws_bytes, int mode);
+size_t tilen_tile_doubles(const rk_solve_cfg* c);
+size_t tilen_ws_doubles(const rk_solve_cfg* c, int mode);
+
+// ---- the device path of a configuration -----------------------------------------------------------------------------
+enum class SolvePath { Dense, Sqrt, Tile3, Tile4, TileN, Small };
+
+// The one routing rule of rk_solve_filter / _mv / _sim (and of every query about their outputs).  The tile predicates
+// are disjoint and false for kalman_type = square-root; for a user right-hand side they consult (and fill) the hiprtc
+// cache, so they are asked in this order only.
+inline SolvePath solve_path(const rk_solve_cfg* c, int mode) {
+    if (dense_supported(c, mode)) return SolvePath::Dense;
+    if (tile4_supported(c, mode)) return SolvePath::Tile4;
+    if (tile3_supported(c, mode)) return SolvePath::Tile3;
+    if (tilen_supported(c, mode)) return SolvePath::TileN;
+    return c->kalman_type == RK_KALMAN_SQRT ? SolvePath::Sqrt : SolvePath::Small;
+}
+
+// RK_LAYOUT_* of a path's outputs.  The blocked tiles at n_bstate = 4 write the RK_LAYOUT_TILE4 records.
+inline int path_layout(SolvePath p, const rk_solve_cfg* c) {
+    switch (p) {
+        case SolvePath::Dense: return RK_LAYOUT_TRAJ_MAJOR;
+        case SolvePath::Tile3: return RK_LAYOUT_TILE3;
+        case SolvePath::Tile4: return RK_LAYOUT_TILE4;
+        case SolvePath::TileN: return c->n_bstate == 4 ? RK_LAYOUT_TILE4 : RK_LAYOUT_TILEP;
+        default: return RK_LAYOUT_BATCH_MINOR;
+    }
+}
+
+// ---- compile-time dispatch ------------------------------------------------------------------------------------------
+// f(std::integral_constant<int, v>{}) for v in [Lo, Hi]; false (f not called) outside.  Instantiates f for every value.
+template <int Lo, int Hi, class F>
+bool dispatch_int(int v, F&& f) {
+    if constexpr (Lo > Hi) {
+        return false;
+    } else {
+        if (v == Lo) {
+            f(std::integral_constant<int, Lo>{});
+            return true;
+        }
+        return dispatch_int<Lo + 1, Hi>(v, std::forward<F>(f));
+    }
+}
+
+// f(RHS{}) for the built-in right-hand side rhs_id; false (f not called) for any other id.
+template <class F>
+bool with_builtin_rhs(int rhs_id, F&& f) {
+    switch (rhs_id) {
+        case RK_RHS_FITZHUGH_NAGUMO: f(FitzHughNagumo{}); return true;
+        case RK_RHS_LORENZ63: f(Lorenz63{}); return true;
+        case RK_RHS_HIGHER_ORDER: f(HigherOrder{}); return true;
+    }
+    return false;
+}
+
+}  // namespace rk

@@ -11,6 +11,7 @@
 #include "philox.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
+#include "solve_paths.hpp"
 #include "solve_small_kernels.hpp"
 
 namespace rk {
@@ -452,29 +453,6 @@ static int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in) {
     return RK_OK;
 }
 
-template <class RHS, int P, int ITG>
-static int launch_fwd_t(rk_handle h, const SolveArgs& a, bool store_pred) {
-    const dim3 grid(div_up(a.B, 64)), block(64);
-    LaunchTimer t(h, "fwd_kernel");
-    if (store_pred) hipLaunchKernelGGL((fwd_kernel<RHS, P, ITG, true>), grid, block, 0, h->stream, a);
-    else hipLaunchKernelGGL((fwd_kernel<RHS, P, ITG, false>), grid, block, 0, h->stream, a);
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
-template <class RHS, int P>
-static int launch_fwd_p(rk_handle h, const SolveArgs& a, int itg, bool sp) {
-    switch (itg) {
-        case RK_INTERROGATE_RODEO: return launch_fwd_t<RHS, P, RK_INTERROGATE_RODEO>(h, a, sp);
-        case RK_INTERROGATE_SCHOBER: return launch_fwd_t<RHS, P, RK_INTERROGATE_SCHOBER>(h, a, sp);
-        case RK_INTERROGATE_KRAMER: return launch_fwd_t<RHS, P, RK_INTERROGATE_KRAMER>(h, a, sp);
-        case RK_INTERROGATE_CHKREBTII: return launch_fwd_t<RHS, P, RK_INTERROGATE_CHKREBTII>(h, a, sp);
-    }
-    set_error("unknown interrogate id %d", itg);
-    return RK_ERR_UNSUPPORTED;
-}
-
 template <class RHS>
 static int launch_fwd_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     RK_REQUIRE(c->n_block == RHS::D && c->n_bmeas == 1, RK_ERR_UNSUPPORTED,
@@ -482,48 +460,40 @@ static int launch_fwd_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a
     RK_REQUIRE(c->n_theta == 0 || c->n_theta >= RHS::NTHETA || !a.theta, RK_ERR_INVALID,
                "rhs %d needs %d parameters, got n_theta=%d", c->rhs_id, RHS::NTHETA, c->n_theta);
     const bool sp = (c->flags & RK_FLAG_STORE_PRED) != 0;
-    switch (c->n_bstate) {
-        case 2: return launch_fwd_p<RHS, 2>(h, a, c->interrogate, sp);
-        case 3: return launch_fwd_p<RHS, 3>(h, a, c->interrogate, sp);
-        case 4: return launch_fwd_p<RHS, 4>(h, a, c->interrogate, sp);
-        case 5: return launch_fwd_p<RHS, 5>(h, a, c->interrogate, sp);
-        case 6: return launch_fwd_p<RHS, 6>(h, a, c->interrogate, sp);
-    }
-    set_error("lane-per-trajectory path supports n_bstate in [2, 6] (the blocked tile path 4 .. 8 without RK_FLAG_STORE_PRED / "
-              "RK_FLAG_BATCH_MINOR), got %d", c->n_bstate);
-    return RK_ERR_UNSUPPORTED;
+    const dim3 grid(div_up(a.B, 64)), block(64);
+    bool itg_ok = false;
+    const bool p_ok = dispatch_int<2, 6>(c->n_bstate, [&](auto P) {
+        itg_ok = dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
+            LaunchTimer t(h, "fwd_kernel");
+            if (sp) hipLaunchKernelGGL((fwd_kernel<RHS, P, I, true>), grid, block, 0, h->stream, a);
+            else hipLaunchKernelGGL((fwd_kernel<RHS, P, I, false>), grid, block, 0, h->stream, a);
+            t.stop();
+        });
+    });
+    RK_REQUIRE(p_ok, RK_ERR_UNSUPPORTED, "lane-per-trajectory path supports n_bstate in [2, 6] (the blocked tile path 4 .. 8 without "
+               "RK_FLAG_STORE_PRED / RK_FLAG_BATCH_MINOR), got %d", c->n_bstate);
+    RK_REQUIRE(itg_ok, RK_ERR_UNSUPPORTED, "unknown interrogate id %d", c->interrogate);
+    RK_HIP(hipGetLastError());
+    return RK_OK;
 }
 
-int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
-bool is_user_rhs(int rhs_id);
-
-int small_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
+static int small_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     if (is_user_rhs(c->rhs_id)) return user_forward(h, c, a);
-    switch (c->rhs_id) {
-        case RK_RHS_FITZHUGH_NAGUMO: return launch_fwd_rhs<FitzHughNagumo>(h, c, a);
-        case RK_RHS_LORENZ63: return launch_fwd_rhs<Lorenz63>(h, c, a);
-        case RK_RHS_HIGHER_ORDER: return launch_fwd_rhs<HigherOrder>(h, c, a);
-    }
-    set_error("unknown rhs_id %d for the small-block path", c->rhs_id);
-    return RK_ERR_UNSUPPORTED;
+    int rc = RK_ERR_UNSUPPORTED;
+    if (!with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_rhs<decltype(rhs)>(h, c, a); }))
+        set_error("unknown rhs_id %d for the small-block path", c->rhs_id);
+    return rc;
 }
 
 template <bool SIM>
 static int small_backward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     const dim3 grid(div_up(a.B * a.D, 64)), block(64);
     LaunchTimer t(h, SIM ? "bwd_sim_kernel" : "bwd_mv_kernel");
-#define RK_BWD(P_)                                                                              \
-    case P_:                                                                                    \
-        if (SIM) hipLaunchKernelGGL((bwd_sim_kernel<P_>), grid, block, 0, h->stream, a);        \
-        else hipLaunchKernelGGL((bwd_mv_kernel<P_>), grid, block, 0, h->stream, a);             \
-        break;
-    switch (c->n_bstate) {
-        RK_BWD(2) RK_BWD(3) RK_BWD(4) RK_BWD(5) RK_BWD(6) RK_BWD(7) RK_BWD(8) RK_BWD(9)
-        default:
-            set_error("small-block path supports n_bstate in [2, 9] for the backward pass, got %d", c->n_bstate);
-            return RK_ERR_UNSUPPORTED;
-    }
-#undef RK_BWD
+    const bool ok = dispatch_int<2, 9>(c->n_bstate, [&](auto P) {
+        if (SIM) hipLaunchKernelGGL((bwd_sim_kernel<P>), grid, block, 0, h->stream, a);
+        else hipLaunchKernelGGL((bwd_mv_kernel<P>), grid, block, 0, h->stream, a);
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "small-block path supports n_bstate in [2, 9] for the backward pass, got %d", c->n_bstate);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;
@@ -536,71 +506,45 @@ static int launch_itg_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a
                "rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, RHS::D, c->n_block, c->n_bmeas);
     const dim3 grid(div_up(a.B, 64)), block(64);
     const int sqrt_mode = c->kalman_type == RK_KALMAN_SQRT ? 1 : 0;      // only interrogate_chkrebtii reads it
-#define RK_ITG2(P_, I_)                                                                                          \
-    hipLaunchKernelGGL((interrogate_kernel<RHS, P_, I_>), grid, block, 0, h->stream, a, t, step, mp, vp, wm, mm_, vm, sqrt_mode)
-#define RK_ITG(P_)                                                                      \
-    case P_:                                                                            \
-        switch (c->interrogate) {                                                       \
-            case RK_INTERROGATE_RODEO: RK_ITG2(P_, RK_INTERROGATE_RODEO); break;        \
-            case RK_INTERROGATE_SCHOBER: RK_ITG2(P_, RK_INTERROGATE_SCHOBER); break;    \
-            case RK_INTERROGATE_KRAMER: RK_ITG2(P_, RK_INTERROGATE_KRAMER); break;      \
-            case RK_INTERROGATE_CHKREBTII: RK_ITG2(P_, RK_INTERROGATE_CHKREBTII); break; \
-        }                                                                               \
-        break;
-    switch (c->n_bstate) {
-        RK_ITG(2) RK_ITG(3) RK_ITG(4) RK_ITG(5) RK_ITG(6)
-        default:
-            set_error("rk_interrogate_batched supports n_bstate in [2, 6], got %d", c->n_bstate);
-            return RK_ERR_UNSUPPORTED;
-    }
-#undef RK_ITG
-#undef RK_ITG2
+    const bool ok = dispatch_int<2, 6>(c->n_bstate, [&](auto P) {
+        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
+            hipLaunchKernelGGL((interrogate_kernel<RHS, P, I>), grid, block, 0, h->stream, a, t, step, mp, vp, wm, mm_, vm, sqrt_mode);
+        });
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "rk_interrogate_batched supports n_bstate in [2, 6], got %d", c->n_bstate);
     RK_HIP(hipGetLastError());
     return RK_OK;
 }
 
-// dense large-block path (solve_dense.hip)
-bool dense_supported(const rk_solve_cfg* c, int mode);
-int dense_check(const rk_solve_cfg* c, const rk_solve_in* in, int mode);
-int dense_solve(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, int mode);
-size_t dense_ws_bytes(const rk_solve_cfg* c, int mode);
+// fenrir's backward filter, one lane per (block, trajectory): fenrir_bwd_kernel<P, STORE, n_bobs, TILES> for P in [PLO, PHI]
+// (tiles: the records of the blocked-tile forward pass, TILES only)
+template <int PLO, int PHI, bool STORE, bool TILES>
+static void launch_fenrir_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int n_bobs, const double* obs,
+                              const double* obs_w, const double* obs_v, const int32_t* obs_ind, int n_obs, double* logdens,
+                              double* states, const double* tiles) {
+    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
+    dispatch_int<PLO, PHI>(c->n_bstate, [&](auto P) {
+        dispatch_int<1, 3>(n_bobs, [&](auto M) {
+            hipLaunchKernelGGL((fenrir_bwd_kernel<P, STORE, M, TILES>), grid, block, 0, h->stream, a, obs, obs_w, obs_v, obs_ind, n_obs,
+                               logdens, states, tiles);
+        });
+    });
+}
 
-// user-supplied right-hand sides (rhs_jit.hip)
-bool is_user_rhs(int rhs_id);
-int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
-int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
-                     const double* vp, double* wm, double* mm_, double* vm);
+// fenrir's smoothing sweep over the stored backward filter (fenrir_smooth_kernel<P>), P in [PLO, PHI]
+template <int PLO, int PHI>
+static void launch_fenrir_smooth(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* states) {
+    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
+    dispatch_int<PLO, PHI>(c->n_bstate, [&](auto P) {
+        hipLaunchKernelGGL(fenrir_smooth_kernel<P>, grid, block, 0, h->stream, a, states);
+    });
+}
 
-// fused square-root solver (solve_sqrt.hip)
-int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, double* ws, size_t ws_bytes);
-size_t sqrt_ws_doubles(const rk_solve_cfg* c, int mode);
-
-// fenrir with kalman_type = square-root (fenrir_sqrt.hip)
-size_t fenrir_sqrt_item_doubles(int p);
-int fenrir_sqrt_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* obs, const double* obs_w,
-                       const double* obs_v, const int32_t* obs_ind, int n_obs, int n_bobs, double* logdens, double* states);
-
-// MFMA-tile path for n_bstate = 4 (solve_tile4.hip)
-bool tile4_supported(const rk_solve_cfg* c, int mode);
-int tile4_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode);
-size_t tile4_doubles(const rk_solve_cfg* c);
-
-// blocked MFMA-tile path for n_bstate = 4 .. 8 (solve_tilen.hip)
-bool tilen_supported(const rk_solve_cfg* c, int mode);
-int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, double* ws, size_t ws_bytes, int mode);
-size_t tilen_tile_doubles(const rk_solve_cfg* c);
-size_t tilen_ws_doubles(const rk_solve_cfg* c, int mode);
-
-// MFMA-tile path (solve_tile3.hip)
-bool tile3_supported(const rk_solve_cfg* c, int mode);
-struct SimLogpost;
-int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp = nullptr);
-bool tile3_sim_logpost_supported(const rk_solve_cfg* c, int n_obs);
-int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, const double* obs,
-                            const int32_t* obs_ind, int n_obs, double noise_sd, const double* upars, int n_prior, double prior_sd,
-                            double* logpost);
-int tile3_fenrir_backward(rk_handle h, const SolveArgs& a, const double* tiles, const double* obs, const double* obs_w,
-                          const double* obs_v, const int32_t* obs_ind, int n_obs, double* logdens);
+static int begin_solve(rk_handle h) {
+    RK_HIP(hipSetDevice(h->device));
+    if (!h->profile_keep) { h->prof.clear(); h->event_used = 0; }
+    return RK_OK;
+}
 
 }  // namespace rk
 
@@ -611,20 +555,18 @@ extern "C" {
 int rk_solve_layout(const rk_solve_cfg* c, int32_t mode, int32_t* layout) {
     RK_REQUIRE(c && layout, RK_ERR_INVALID, "rk_solve_layout: null argument");
     RK_REQUIRE(mode >= RK_MODE_FILTER && mode <= RK_MODE_SIM, RK_ERR_INVALID, "rk_solve_layout: bad mode %d", mode);
-    *layout = dense_supported(c, mode) ? RK_LAYOUT_TRAJ_MAJOR
-              : (tile3_supported(c, mode) ? RK_LAYOUT_TILE3
-                 : (tile4_supported(c, mode) ? RK_LAYOUT_TILE4
-                    : (tilen_supported(c, mode) ? (c->n_bstate == 4 ? RK_LAYOUT_TILE4 : RK_LAYOUT_TILEP) : RK_LAYOUT_BATCH_MINOR)));
+    *layout = path_layout(solve_path(c, mode), c);
     return RK_OK;
 }
 
 int rk_solve_workspace_bytes(const rk_solve_cfg* c, int32_t mode, size_t* bytes) {
     RK_REQUIRE(c && bytes, RK_ERR_INVALID, "rk_solve_workspace_bytes: null argument");
-    if (dense_supported(c, mode)) *bytes = dense_ws_bytes(c, mode);
-    else if (c->kalman_type == RK_KALMAN_SQRT) *bytes = sqrt_ws_doubles(c, mode) * sizeof(double);     // optional (solve_sqrt.hip)
-    else if (!tile3_supported(c, mode) && !tile4_supported(c, mode) && tilen_supported(c, mode))
-        *bytes = tilen_ws_doubles(c, mode) * sizeof(double);
-    else *bytes = 0;
+    switch (solve_path(c, mode)) {
+        case SolvePath::Dense: *bytes = dense_ws_bytes(c, mode); break;
+        case SolvePath::Sqrt: *bytes = sqrt_ws_doubles(c, mode) * sizeof(double); break;     // optional (solve_sqrt.hip)
+        case SolvePath::TileN: *bytes = tilen_ws_doubles(c, mode) * sizeof(double); break;
+        default: *bytes = 0;
+    }
     return RK_OK;
 }
 
@@ -663,31 +605,31 @@ static int solve_common(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* i
     RK_REQUIRE(h, RK_ERR_INVALID, "null handle");
     int rc = check_cfg(c, in);
     if (rc) return rc;
-    const bool dense = dense_supported(c, mode);
-    const bool tile4 = !dense && tile4_supported(c, mode);
-    const bool tile3 = !dense && !tile4 && tile3_supported(c, mode);
-    const bool tilen = !dense && !tile4 && !tile3 && tilen_supported(c, mode);
-    const bool tile = tile4 || tile3 || tilen;
+    const SolvePath path = solve_path(c, mode);
+    const bool tile = path == SolvePath::Tile3 || path == SolvePath::Tile4 || path == SolvePath::TileN;
     RK_REQUIRE(out && out->var_state && (tile || out->mean_state), RK_ERR_INVALID,
                "out->mean_state / var_state must not be NULL");
-    if (dense) {
+    if (path == SolvePath::Dense) {
         rc = dense_check(c, in, mode);
         if (rc) return rc;
-        RK_HIP(hipSetDevice(h->device));
-        if (!h->profile_keep) { h->prof.clear(); h->event_used = 0; }
+        rc = begin_solve(h);
+        if (rc) return rc;
         return dense_solve(h, c, in, out, mode);
     }
     RK_REQUIRE(!(c->flags & RK_FLAG_STORE_PRED) || (out->mean_pred && out->var_pred), RK_ERR_INVALID,
                "RK_FLAG_STORE_PRED needs out->mean_pred / var_pred");
     RK_REQUIRE(mode != 2 || out->x_state, RK_ERR_INVALID, "rk_solve_sim needs out->x_state");
-    RK_HIP(hipSetDevice(h->device));
-    if (!h->profile_keep) { h->prof.clear(); h->event_used = 0; }
+    rc = begin_solve(h);
+    if (rc) return rc;
     SolveArgs a;
     make_args(c, in, out, a);
-    if (c->kalman_type == RK_KALMAN_SQRT) return sqrt_solve(h, c, a, mode, (double*)out->workspace, out->workspace_bytes);
-    if (tile4) return tile4_solve(h, c, a, out->var_state, mode);
-    if (tile3) return tile3_solve(h, c, a, out->var_state, mode);
-    if (tilen) return tilen_solve(h, c, a, out->var_state, (double*)out->workspace, out->workspace_bytes, mode);
+    switch (path) {
+        case SolvePath::Sqrt: return sqrt_solve(h, c, a, mode, (double*)out->workspace, out->workspace_bytes);
+        case SolvePath::Tile4: return tile4_solve(h, c, a, out->var_state, mode);
+        case SolvePath::Tile3: return tile3_solve(h, c, a, out->var_state, mode);
+        case SolvePath::TileN: return tilen_solve(h, c, a, out->var_state, (double*)out->workspace, out->workspace_bytes, mode);
+        default: break;
+    }
     rc = small_forward(h, c, a);
     if (rc) return rc;
     if (mode == 1) rc = small_backward<false>(h, c, a);
@@ -718,12 +660,12 @@ int rk_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* 
     RK_REQUIRE(!upars || n_prior >= 0, RK_ERR_INVALID, "rk_solve_sim_logpost: n_prior < 0");
     int rc = check_cfg(c, in);
     if (rc) return rc;
-    const bool dense = dense_supported(c, 2);
-    if (!dense && !tile4_supported(c, 2) && tile3_sim_logpost_supported(c, n_obs) && c->kalman_type == RK_KALMAN_STANDARD) {
+    // (tile3_sim_logpost_supported first: it implies the tile3 route, so solve_path stops there)
+    if (tile3_sim_logpost_supported(c, n_obs) && solve_path(c, RK_MODE_SIM) == SolvePath::Tile3) {
         // the sampler's consumer wave reduces the log-posterior itself; out->x_state may be NULL (no path is stored)
         RK_REQUIRE(out && out->var_state, RK_ERR_INVALID, "out->var_state must not be NULL");
-        RK_HIP(hipSetDevice(h->device));
-        if (!h->profile_keep) { h->prof.clear(); h->event_used = 0; }
+        rc = begin_solve(h);
+        if (rc) return rc;
         SolveArgs a;
         make_args(c, in, out, a);
         return tile3_solve_sim_logpost(h, c, a, out->var_state, obs, obs_ind, n_obs, noise_sd, upars, n_prior, prior_sd, logpost);
@@ -753,16 +695,12 @@ int rk_interrogate_batched(rk_handle h, const rk_solve_cfg* c, const rk_solve_in
     make_args(c, in, nullptr, a);
     if (is_user_rhs(c->rhs_id))
         return user_interrogate(h, c, a, t, step, mean_state_pred, var_state_pred, wgt_meas, mean_meas, var_meas);
-    switch (c->rhs_id) {
-        case RK_RHS_FITZHUGH_NAGUMO:
-            return launch_itg_rhs<FitzHughNagumo>(h, c, a, t, step, mean_state_pred, var_state_pred, wgt_meas, mean_meas, var_meas);
-        case RK_RHS_LORENZ63:
-            return launch_itg_rhs<Lorenz63>(h, c, a, t, step, mean_state_pred, var_state_pred, wgt_meas, mean_meas, var_meas);
-        case RK_RHS_HIGHER_ORDER:
-            return launch_itg_rhs<HigherOrder>(h, c, a, t, step, mean_state_pred, var_state_pred, wgt_meas, mean_meas, var_meas);
-    }
-    set_error("unknown rhs_id %d", c->rhs_id);
-    return RK_ERR_UNSUPPORTED;
+    int rc = RK_ERR_UNSUPPORTED;
+    if (!with_builtin_rhs(c->rhs_id, [&](auto rhs) {
+            rc = launch_itg_rhs<decltype(rhs)>(h, c, a, t, step, mean_state_pred, var_state_pred, wgt_meas, mean_meas, var_meas);
+        }))
+        set_error("unknown rhs_id %d", c->rhs_id);
+    return rc;
 }
 
 int rk_gauss_obs_logpost(rk_handle h, int32_t n_traj, int32_t n_steps, int32_t n_block, int32_t n_bstate,
@@ -804,7 +742,9 @@ int rk_fenrir_backward(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
         return fenrir_sqrt_launch(h, c, as, obs, obs_weight, obs_var, obs_ind, n_obs, n_bobs, logdens, nullptr);
     }
     RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "rk_fenrir_backward: unknown kalman_type %d", c->kalman_type);
-    if (n_bobs == 1 && !(c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) && tile3_supported(c, RK_MODE_FILTER)) {
+    const bool own_layout = !(c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR));
+    const SolvePath fpath = own_layout ? solve_path(c, RK_MODE_FILTER) : SolvePath::Small;      // the route rk_solve_filter took
+    if (n_bobs == 1 && fpath == SolvePath::Tile3) {
         // the filter ran on the MFMA-tile path: out->var_state holds the RK_LAYOUT_TILE3 tiles, predicted moments are
         // re-evaluated from the filtered ones (solve_tile3.hip, fenrir_bwd_tile3_kernel)
         RK_REQUIRE(out->var_state && n_obs >= 0, RK_ERR_INVALID, "rk_fenrir_backward: out->var_state (tiles) is null");
@@ -815,8 +755,7 @@ int rk_fenrir_backward(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
         RK_HIP(hipMemsetAsync(logdens, 0, sizeof(double) * (size_t)c->n_traj, h->stream));
         return tile3_fenrir_backward(h, at, out->var_state, obs, obs_weight, obs_var, obs_ind, n_obs, logdens);
     }
-    if (!(c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) && c->n_bstate >= 4 && c->n_bstate <= 8 &&
-        (tile4_supported(c, RK_MODE_FILTER) || tilen_supported(c, RK_MODE_FILTER))) {
+    if (fpath == SolvePath::Tile4 || fpath == SolvePath::TileN) {
         // the filter ran on the blocked MFMA tiles (n_bstate 4 .. 8): out->var_state holds its records [Sigma | mu]; the
         // backward filter runs one lane per (block, trajectory) on them and re-evaluates the predicted moments
         RK_REQUIRE(out->var_state && n_obs >= 0, RK_ERR_INVALID, "rk_fenrir_backward: out->var_state (tiles) is null");
@@ -825,12 +764,8 @@ int rk_fenrir_backward(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
         if (rct) return rct;
         RK_HIP(hipSetDevice(h->device));
         RK_HIP(hipMemsetAsync(logdens, 0, sizeof(double) * (size_t)c->n_traj, h->stream));
-        const dim3 tgrid(div_up(at.B * at.D, 64)), tblock(64);
         LaunchTimer t(h, "fenrir_bwd_kernel<tiles>");
-#define RK_FT(P_, M_) if (c->n_bstate == P_ && n_bobs == M_) hipLaunchKernelGGL((fenrir_bwd_kernel<P_, false, M_, true>), tgrid, tblock, 0, h->stream, at, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr, (const double*)out->var_state);
-        RK_FT(4, 1) RK_FT(4, 2) RK_FT(4, 3) RK_FT(5, 1) RK_FT(5, 2) RK_FT(5, 3) RK_FT(6, 1) RK_FT(6, 2) RK_FT(6, 3)
-        RK_FT(7, 1) RK_FT(7, 2) RK_FT(7, 3) RK_FT(8, 1) RK_FT(8, 2) RK_FT(8, 3)
-#undef RK_FT
+        launch_fenrir_bwd<4, 8, false, true>(h, c, at, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, nullptr, out->var_state);
         t.stop();
         RK_HIP(hipGetLastError());
         return RK_OK;
@@ -845,25 +780,8 @@ int rk_fenrir_backward(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
     if (rc) return rc;
     RK_HIP(hipSetDevice(h->device));
     RK_HIP(hipMemsetAsync(logdens, 0, sizeof(double) * (size_t)c->n_traj, h->stream));
-    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
     LaunchTimer t(h, "fenrir_bwd_kernel");
-    {
-            if (c->n_bstate == 2 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<2, false, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 2 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<2, false, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 2 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<2, false, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 3 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<3, false, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 3 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<3, false, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 3 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<3, false, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 4 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<4, false, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 4 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<4, false, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 4 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<4, false, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 5 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<5, false, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 5 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<5, false, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 5 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<5, false, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 6 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<6, false, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 6 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<6, false, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-            if (c->n_bstate == 6 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<6, false, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, (double*)nullptr);
-    }
+    launch_fenrir_bwd<2, 6, false, false>(h, c, a, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, nullptr, nullptr);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;
@@ -886,8 +804,8 @@ int rk_fenrir_solve_mv_tiles(rk_handle h, const rk_solve_cfg* c, const rk_solve_
                              int32_t n_obs, int32_t n_bobs, void* workspace, double* mean_out, double* var_out) {
     RK_REQUIRE(h && c && in && out && obs && obs_weight && obs_var && obs_ind && workspace && mean_out && var_out, RK_ERR_INVALID,
                "rk_fenrir_solve_mv_tiles: null argument");
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD && !(c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) && c->n_bstate >= 4 &&
-               c->n_bstate <= 8 && (tile4_supported(c, RK_MODE_FILTER) || tilen_supported(c, RK_MODE_FILTER)), RK_ERR_UNSUPPORTED,
+    const SolvePath fpath = !(c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) ? solve_path(c, RK_MODE_FILTER) : SolvePath::Small;
+    RK_REQUIRE(fpath == SolvePath::Tile4 || fpath == SolvePath::TileN, RK_ERR_UNSUPPORTED,
                "rk_fenrir_solve_mv_tiles: a configuration of the blocked-tile forward pass (kalman_type standard, n_bstate 4..8, no "
                "RK_FLAG_STORE_PRED / RK_FLAG_BATCH_MINOR)");
     RK_REQUIRE(out->var_state && n_obs >= 0 && n_bobs >= 1 && n_bobs <= 3, RK_ERR_INVALID,
@@ -897,25 +815,15 @@ int rk_fenrir_solve_mv_tiles(rk_handle h, const rk_solve_cfg* c, const rk_solve_
     if (rc) return rc;
     a.mean = mean_out; a.var = var_out;                             // (the smoothing pass's output; the backward filter reads the records)
     RK_HIP(hipSetDevice(h->device));
-    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
     double* st = (double*)workspace;
     {
         LaunchTimer t(h, "fenrir_bwd_kernel<tiles>");
-#define RK_FT(P_, M_) if (c->n_bstate == P_ && n_bobs == M_) hipLaunchKernelGGL((fenrir_bwd_kernel<P_, true, M_, true>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st, (const double*)out->var_state);
-        RK_FT(4, 1) RK_FT(4, 2) RK_FT(4, 3) RK_FT(5, 1) RK_FT(5, 2) RK_FT(5, 3) RK_FT(6, 1) RK_FT(6, 2) RK_FT(6, 3)
-        RK_FT(7, 1) RK_FT(7, 2) RK_FT(7, 3) RK_FT(8, 1) RK_FT(8, 2) RK_FT(8, 3)
-#undef RK_FT
+        launch_fenrir_bwd<4, 8, true, true>(h, c, a, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, nullptr, st, out->var_state);
         t.stop();
     }
     RK_HIP(hipGetLastError());
     LaunchTimer t(h, "fenrir_smooth_kernel");
-    switch (c->n_bstate) {
-        case 4: hipLaunchKernelGGL(fenrir_smooth_kernel<4>, grid, block, 0, h->stream, a, st); break;
-        case 5: hipLaunchKernelGGL(fenrir_smooth_kernel<5>, grid, block, 0, h->stream, a, st); break;
-        case 6: hipLaunchKernelGGL(fenrir_smooth_kernel<6>, grid, block, 0, h->stream, a, st); break;
-        case 7: hipLaunchKernelGGL(fenrir_smooth_kernel<7>, grid, block, 0, h->stream, a, st); break;
-        default: hipLaunchKernelGGL(fenrir_smooth_kernel<8>, grid, block, 0, h->stream, a, st); break;
-    }
+    launch_fenrir_smooth<4, 8>(h, c, a, st);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;
@@ -946,38 +854,15 @@ int rk_fenrir_solve_mv(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
     int rc = make_args(c, in, out, a);
     if (rc) return rc;
     RK_HIP(hipSetDevice(h->device));
-    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
     double* st = (double*)workspace;
     {
         LaunchTimer t(h, "fenrir_bwd_kernel");
-        {
-            if (c->n_bstate == 2 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<2, true, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 2 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<2, true, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 2 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<2, true, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 3 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<3, true, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 3 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<3, true, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 3 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<3, true, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 4 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<4, true, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 4 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<4, true, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 4 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<4, true, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 5 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<5, true, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 5 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<5, true, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 5 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<5, true, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 6 && n_bobs == 1) hipLaunchKernelGGL((fenrir_bwd_kernel<6, true, 1>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 6 && n_bobs == 2) hipLaunchKernelGGL((fenrir_bwd_kernel<6, true, 2>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-            if (c->n_bstate == 6 && n_bobs == 3) hipLaunchKernelGGL((fenrir_bwd_kernel<6, true, 3>), grid, block, 0, h->stream, a, obs, obs_weight, obs_var, obs_ind, n_obs, (double*)nullptr, st);
-        }
+        launch_fenrir_bwd<2, 6, true, false>(h, c, a, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, nullptr, st, nullptr);
         t.stop();
     }
     RK_HIP(hipGetLastError());
     LaunchTimer t(h, "fenrir_smooth_kernel");
-    switch (c->n_bstate) {
-        case 2: hipLaunchKernelGGL(fenrir_smooth_kernel<2>, grid, block, 0, h->stream, a, st); break;
-        case 3: hipLaunchKernelGGL(fenrir_smooth_kernel<3>, grid, block, 0, h->stream, a, st); break;
-        case 4: hipLaunchKernelGGL(fenrir_smooth_kernel<4>, grid, block, 0, h->stream, a, st); break;
-        case 5: hipLaunchKernelGGL(fenrir_smooth_kernel<5>, grid, block, 0, h->stream, a, st); break;
-        default: hipLaunchKernelGGL(fenrir_smooth_kernel<6>, grid, block, 0, h->stream, a, st); break;
-    }
+    launch_fenrir_smooth<2, 6>(h, c, a, st);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;

@@ -19,6 +19,7 @@
 #include "philox.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
+#include "solve_paths.hpp"
 #include "sqrt_small.hpp"
 #include "solve_sqrt_kernels.hpp"
 
@@ -364,41 +365,24 @@ __global__ void __launch_bounds__(64) sqrt_pred_kernel(SolveArgs a) {
     }
 }
 
-template <class RHS, int P>
-static int launch_fwd_sqrt_p(rk_handle h, const SolveArgs& a, int itg) {
-    const dim3 grid(div_up(a.B, 64 / RHS::D)), block(64);      // 64 / D trajectories per wave (solve_sqrt_kernels.hpp)
-    LaunchTimer t(h, "fwd_sqrt_kernel");
-    switch (itg) {
-        case RK_INTERROGATE_RODEO: hipLaunchKernelGGL((fwd_sqrt_kernel<RHS, P, RK_INTERROGATE_RODEO>), grid, block, 0, h->stream, a); break;
-        case RK_INTERROGATE_SCHOBER: hipLaunchKernelGGL((fwd_sqrt_kernel<RHS, P, RK_INTERROGATE_SCHOBER>), grid, block, 0, h->stream, a); break;
-        case RK_INTERROGATE_KRAMER: hipLaunchKernelGGL((fwd_sqrt_kernel<RHS, P, RK_INTERROGATE_KRAMER>), grid, block, 0, h->stream, a); break;
-        case RK_INTERROGATE_CHKREBTII: hipLaunchKernelGGL((fwd_sqrt_kernel<RHS, P, RK_INTERROGATE_CHKREBTII>), grid, block, 0, h->stream, a); break;
-        default: set_error("unknown interrogate id %d", itg); return RK_ERR_UNSUPPORTED;
-    }
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
 template <class RHS>
 static int launch_fwd_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     RK_REQUIRE(c->n_block == RHS::D && c->n_bmeas == 1, RK_ERR_UNSUPPORTED,
                "rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, RHS::D, c->n_block, c->n_bmeas);
-    switch (c->n_bstate) {
-        case 2: return launch_fwd_sqrt_p<RHS, 2>(h, a, c->interrogate);
-        case 3: return launch_fwd_sqrt_p<RHS, 3>(h, a, c->interrogate);
-        case 4: return launch_fwd_sqrt_p<RHS, 4>(h, a, c->interrogate);
-        case 5: return launch_fwd_sqrt_p<RHS, 5>(h, a, c->interrogate);
-        case 6: return launch_fwd_sqrt_p<RHS, 6>(h, a, c->interrogate);
-        case 7: return launch_fwd_sqrt_p<RHS, 7>(h, a, c->interrogate);
-        case 8: return launch_fwd_sqrt_p<RHS, 8>(h, a, c->interrogate);
-    }
-    set_error("square-root solver supports n_bstate in [2, 8], got %d", c->n_bstate);
-    return RK_ERR_UNSUPPORTED;
+    const dim3 grid(div_up(a.B, 64 / RHS::D)), block(64);      // 64 / D trajectories per wave (solve_sqrt_kernels.hpp)
+    bool itg_ok = false;
+    const bool p_ok = dispatch_int<2, 8>(c->n_bstate, [&](auto P) {
+        LaunchTimer t(h, "fwd_sqrt_kernel");
+        itg_ok = dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
+            hipLaunchKernelGGL((fwd_sqrt_kernel<RHS, P, I>), grid, block, 0, h->stream, a);
+        });
+        if (itg_ok) t.stop();
+    });
+    RK_REQUIRE(p_ok, RK_ERR_UNSUPPORTED, "square-root solver supports n_bstate in [2, 8], got %d", c->n_bstate);
+    RK_REQUIRE(itg_ok, RK_ERR_UNSUPPORTED, "unknown interrogate id %d", c->interrogate);
+    RK_HIP(hipGetLastError());
+    return RK_OK;
 }
-
-bool is_user_rhs(int rhs_id);
-int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
 
 int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a_, int mode, double* ws, size_t ws_bytes) {
     RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 8, RK_ERR_UNSUPPORTED, "square-root solver supports n_bstate in [2, 8], got %d",
@@ -406,11 +390,9 @@ int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a_, int mode
     const SolveArgs& a = a_;
     int rc;
     if (is_user_rhs(c->rhs_id)) rc = user_forward_sqrt(h, c, a);      // hiprtc build of fwd_sqrt_kernel (rhs_jit.hip)
-    else switch (c->rhs_id) {
-        case RK_RHS_FITZHUGH_NAGUMO: rc = launch_fwd_sqrt<FitzHughNagumo>(h, c, a); break;
-        case RK_RHS_LORENZ63: rc = launch_fwd_sqrt<Lorenz63>(h, c, a); break;
-        case RK_RHS_HIGHER_ORDER: rc = launch_fwd_sqrt<HigherOrder>(h, c, a); break;
-        default: set_error("unknown rhs_id %d for the square-root solver", c->rhs_id); return RK_ERR_UNSUPPORTED;
+    else if (!with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_sqrt<decltype(rhs)>(h, c, a); })) {
+        set_error("unknown rhs_id %d for the square-root solver", c->rhs_id);
+        return RK_ERR_UNSUPPORTED;
     }
     if (rc) return rc;
     if (c->flags & RK_FLAG_STORE_PRED) {
@@ -418,9 +400,7 @@ int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a_, int mode
         RK_REQUIRE(lanes < 0x7fffffffull * 64, RK_ERR_UNSUPPORTED, "square-root solver: too many (time, block, trajectory) items for one launch");
         const dim3 pgrid((unsigned)((lanes + 63) / 64)), pblock(64);
         LaunchTimer t(h, "sqrt_pred_kernel");
-#define RK_SQP(P_) case P_: hipLaunchKernelGGL((sqrt_pred_kernel<P_>), pgrid, pblock, 0, h->stream, a); break;
-        switch (c->n_bstate) { RK_SQP(2) RK_SQP(3) RK_SQP(4) RK_SQP(5) RK_SQP(6) RK_SQP(7) RK_SQP(8) }
-#undef RK_SQP
+        dispatch_int<2, 8>(c->n_bstate, [&](auto P) { hipLaunchKernelGGL((sqrt_pred_kernel<P>), pgrid, pblock, 0, h->stream, a); });
         t.stop();
         RK_HIP(hipGetLastError());
     }
@@ -434,16 +414,12 @@ int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a_, int mode
         const dim3 ggrid((unsigned)((lanes + 63) / 64));
         {
             LaunchTimer t(h, "sqrt_gain_kernel");
-#define RK_SQG(P_) case P_: hipLaunchKernelGGL((sqrt_gain_kernel<P_>), ggrid, block, 0, h->stream, a, ws); break;
-            switch (c->n_bstate) { RK_SQG(2) RK_SQG(3) RK_SQG(4) RK_SQG(5) RK_SQG(6) RK_SQG(7) RK_SQG(8) }
-#undef RK_SQG
+            dispatch_int<2, 8>(c->n_bstate, [&](auto P) { hipLaunchKernelGGL((sqrt_gain_kernel<P>), ggrid, block, 0, h->stream, a, ws); });
             t.stop();
             RK_HIP(hipGetLastError());
         }
         LaunchTimer t(h, "bwd_sqrt_chain_kernel");
-#define RK_SQC(P_) case P_: hipLaunchKernelGGL((bwd_sqrt_chain_kernel<P_>), grid, block, 0, h->stream, a, ws); break;
-        switch (c->n_bstate) { RK_SQC(2) RK_SQC(3) RK_SQC(4) RK_SQC(5) RK_SQC(6) RK_SQC(7) RK_SQC(8) }
-#undef RK_SQC
+        dispatch_int<2, 8>(c->n_bstate, [&](auto P) { hipLaunchKernelGGL((bwd_sqrt_chain_kernel<P>), grid, block, 0, h->stream, a, ws); });
         t.stop();
         RK_HIP(hipGetLastError());
         return RK_OK;
@@ -454,28 +430,21 @@ int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a_, int mode
         const dim3 ggrid((unsigned)((lanes + 63) / 64));
         {
             LaunchTimer t(h, "sqrt_sim_gain_kernel");
-#define RK_SQG(P_) case P_: hipLaunchKernelGGL((sqrt_sim_gain_kernel<P_>), ggrid, block, 0, h->stream, a, ws); break;
-            switch (c->n_bstate) { RK_SQG(2) RK_SQG(3) RK_SQG(4) RK_SQG(5) RK_SQG(6) RK_SQG(7) RK_SQG(8) }
-#undef RK_SQG
+            dispatch_int<2, 8>(c->n_bstate, [&](auto P) { hipLaunchKernelGGL((sqrt_sim_gain_kernel<P>), ggrid, block, 0, h->stream, a, ws); });
             t.stop();
             RK_HIP(hipGetLastError());
         }
         LaunchTimer t(h, "bwd_sqrt_sim_chain_kernel");
-#define RK_SQC(P_) case P_: hipLaunchKernelGGL((bwd_sqrt_sim_chain_kernel<P_>), grid, block, 0, h->stream, a, ws); break;
-        switch (c->n_bstate) { RK_SQC(2) RK_SQC(3) RK_SQC(4) RK_SQC(5) RK_SQC(6) RK_SQC(7) RK_SQC(8) }
-#undef RK_SQC
+        dispatch_int<2, 8>(c->n_bstate, [&](auto P) { hipLaunchKernelGGL((bwd_sqrt_sim_chain_kernel<P>), grid, block, 0, h->stream, a, ws); });
         t.stop();
         RK_HIP(hipGetLastError());
         return RK_OK;
     }
     LaunchTimer t(h, mode == RK_MODE_SIM ? "bwd_sqrt_sim_kernel" : "bwd_sqrt_mv_kernel");
-#define RK_SQ(P_)                                                                                        \
-    case P_:                                                                                             \
-        if (mode == RK_MODE_SIM) hipLaunchKernelGGL((bwd_sqrt_kernel<P_, true>), grid, block, 0, h->stream, a);  \
-        else hipLaunchKernelGGL((bwd_sqrt_kernel<P_, false>), grid, block, 0, h->stream, a);             \
-        break;
-    switch (c->n_bstate) { RK_SQ(2) RK_SQ(3) RK_SQ(4) RK_SQ(5) RK_SQ(6) RK_SQ(7) RK_SQ(8) }
-#undef RK_SQ
+    dispatch_int<2, 8>(c->n_bstate, [&](auto P) {
+        if (mode == RK_MODE_SIM) hipLaunchKernelGGL((bwd_sqrt_kernel<P, true>), grid, block, 0, h->stream, a);
+        else hipLaunchKernelGGL((bwd_sqrt_kernel<P, false>), grid, block, 0, h->stream, a);
+    });
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;

@@ -29,6 +29,7 @@
 #include "philox.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
+#include "solve_paths.hpp"
 #include "solve_tile3_kernels.hpp"
 
 namespace rk {
@@ -744,10 +745,6 @@ static int launch_fwd_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& 
     return RK_OK;
 }
 
-bool is_user_rhs(int rhs_id);
-bool user_tile_available(const rk_solve_cfg* c, int which);
-int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int which);
-
 bool tile3_supported(const rk_solve_cfg* c, int mode) {
     if (c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) return false;
     if (c->kalman_type != RK_KALMAN_STANDARD || c->n_bstate != 3 || c->n_bmeas != 1) return false;
@@ -755,7 +752,7 @@ bool tile3_supported(const rk_solve_cfg* c, int mode) {
     if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) return c->n_block == 2;
     if (c->rhs_id == RK_RHS_LORENZ63) return c->n_block == 3;
     if (c->rhs_id == RK_RHS_HIGHER_ORDER) return c->n_block == 1;
-    if (is_user_rhs(c->rhs_id)) return user_tile_available(c, 3);       // hiprtc build of fwd_tile3_kernel (rhs_jit.hip)
+    if (is_user_rhs(c->rhs_id)) return user_tile_available(c, JIT_TILE3);       // hiprtc build of fwd_tile3_kernel (rhs_jit.hip)
     return false;
 }
 
@@ -763,8 +760,6 @@ bool tile3_sim_logpost_supported(const rk_solve_cfg* c, int n_obs) {
     return tile3_supported(c, RK_MODE_SIM) && (c->n_block == 1 || c->n_block == 2 || c->n_block == 4) && n_obs <= LP_MAX_OBS &&
            n_obs * c->n_block <= LP_MAX_VALS;
 }
-
-int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp = nullptr);
 
 int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, const double* obs,
                             const int32_t* obs_ind, int n_obs, double noise_sd, const double* upars, int n_prior, double prior_sd,
@@ -776,11 +771,9 @@ int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs&
 }
 
 int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp) {
-    int rc;
-    if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) rc = launch_fwd_tile<FitzHughNagumo>(h, c, a, tiles);
-    else if (c->rhs_id == RK_RHS_LORENZ63) rc = launch_fwd_tile<Lorenz63>(h, c, a, tiles);
-    else if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, 3);
-    else rc = launch_fwd_tile<HigherOrder>(h, c, a, tiles);
+    int rc = RK_ERR_UNSUPPORTED;
+    if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, JIT_TILE3);
+    else with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_tile<decltype(rhs)>(h, c, a, tiles); });     // (tile3_supported: a built-in id)
     if (rc || mode == RK_MODE_FILTER) return rc;
     if (mode == RK_MODE_SIM) {
         LaunchTimer t(h, "bwd_sim_tile3_kernel");

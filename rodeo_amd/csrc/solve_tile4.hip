@@ -17,6 +17,7 @@
 #include "mfma_tile.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
+#include "solve_paths.hpp"
 #include "solve_tile4_kernels.hpp"
 
 namespace rk {
@@ -485,10 +486,6 @@ static int launch_fwd_tile4(rk_handle h, const rk_solve_cfg* c, const SolveArgs&
     return RK_OK;
 }
 
-bool is_user_rhs(int rhs_id);
-bool user_tile_available(const rk_solve_cfg* c, int which);
-int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int which);
-
 bool tile4_supported(const rk_solve_cfg* c, int mode) {
     if (c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) return false;
     if (mode == RK_MODE_SIM) return false;
@@ -499,7 +496,7 @@ bool tile4_supported(const rk_solve_cfg* c, int mode) {
     if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) return c->n_block == 2;
     if (c->rhs_id == RK_RHS_LORENZ63) return c->n_block == 3;
     if (c->rhs_id == RK_RHS_HIGHER_ORDER) return c->n_block == 1;
-    if (is_user_rhs(c->rhs_id)) return user_tile_available(c, 4);       // hiprtc build of fwd_tile4_kernel (rhs_jit.hip)
+    if (is_user_rhs(c->rhs_id)) return user_tile_available(c, JIT_TILE4);       // hiprtc build of fwd_tile4_kernel (rhs_jit.hip)
     return false;
 }
 
@@ -511,11 +508,9 @@ size_t tile4_doubles(const rk_solve_cfg* c) {
 }
 
 int tile4_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode) {
-    int rc;
-    if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) rc = launch_fwd_tile4<FitzHughNagumo>(h, c, a, tiles);
-    else if (c->rhs_id == RK_RHS_LORENZ63) rc = launch_fwd_tile4<Lorenz63>(h, c, a, tiles);
-    else if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, 4);
-    else rc = launch_fwd_tile4<HigherOrder>(h, c, a, tiles);
+    int rc = RK_ERR_UNSUPPORTED;
+    if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, JIT_TILE4);
+    else with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_tile4<decltype(rhs)>(h, c, a, tiles); });     // (tile4_supported: a built-in id)
     if (rc || mode == RK_MODE_FILTER || a.N < 2) return rc;
     const int tpw = a.D == 3 ? 3 : 4;
     // Two shapes of workgroup (RK_T4_BWD=quad|ds forces one).  quad: 4 waves, two workgroups per CU.  ds: 8 waves carrying two sets, each
@@ -539,16 +534,10 @@ int tile4_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
 #else
 #define T4_DBG
 #endif
-#define RK_T4_BWD(D_)                                                                                                   \
-    do {                                                                                                                \
-        if (quad) hipLaunchKernelGGL((bwd_mv_tile4_kernel<D_, 3, 1>), grid, block, 0, h->stream, a, tiles T4_DBG);      \
-        else hipLaunchKernelGGL((bwd_mv_tile4_kernel<D_, 2, 2>), grid, block, 0, h->stream, a, tiles T4_DBG);           \
-    } while (0)
-    if (a.D == 1) RK_T4_BWD(1);
-    else if (a.D == 2) RK_T4_BWD(2);
-    else if (a.D == 3) RK_T4_BWD(3);
-    else RK_T4_BWD(4);
-#undef RK_T4_BWD
+    dispatch_int<1, 4>(std::min(a.D, 4), [&](auto D) {
+        if (quad) hipLaunchKernelGGL((bwd_mv_tile4_kernel<D, 3, 1>), grid, block, 0, h->stream, a, tiles T4_DBG);
+        else hipLaunchKernelGGL((bwd_mv_tile4_kernel<D, 2, 2>), grid, block, 0, h->stream, a, tiles T4_DBG);
+    });
     t.stop();
     RK_HIP(hipGetLastError());
 #ifdef RK_T4_STAMPS

@@ -25,6 +25,7 @@
 #include "philox.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
+#include "solve_paths.hpp"
 #include "solve_tilen_kernels.hpp"
 
 namespace rk {
@@ -959,10 +960,6 @@ static int launch_fwd_tilen(rk_handle h, const rk_solve_cfg* c, const SolveArgs&
     return tilen_nb(c->n_bstate) == 1 ? launch_fwd_tilen_nb<RHS, 1>(h, c, a, tiles) : launch_fwd_tilen_nb<RHS, 2>(h, c, a, tiles);
 }
 
-bool is_user_rhs(int rhs_id);
-bool user_tile_available(const rk_solve_cfg* c, int which);
-int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int which);
-
 bool tilen_supported(const rk_solve_cfg* c, int mode) {
     if (c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) return false;
     if (c->kalman_type != RK_KALMAN_STANDARD || c->n_bmeas != 1) return false;
@@ -971,7 +968,7 @@ bool tilen_supported(const rk_solve_cfg* c, int mode) {
     if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) return c->n_block == 2;
     if (c->rhs_id == RK_RHS_LORENZ63) return c->n_block == 3;
     if (c->rhs_id == RK_RHS_HIGHER_ORDER) return c->n_block == 1;
-    if (is_user_rhs(c->rhs_id)) return user_tile_available(c, 5);       // hiprtc build of fwd_tilen_kernel (rhs_jit.hip)
+    if (is_user_rhs(c->rhs_id)) return user_tile_available(c, JIT_TILEN);       // hiprtc build of fwd_tilen_kernel (rhs_jit.hip)
     return false;
 }
 
@@ -994,11 +991,9 @@ int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
         RK_REQUIRE(need == 0 || (ws && ws_bytes >= need), RK_ERR_INVALID,
                    "blocked tile path: out->workspace_bytes = %zu, this call needs %zu (rk_solve_workspace_bytes)", ws_bytes, need);
     }
-    int rc;
-    if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) rc = launch_fwd_tilen<FitzHughNagumo>(h, c, a, tiles);
-    else if (c->rhs_id == RK_RHS_LORENZ63) rc = launch_fwd_tilen<Lorenz63>(h, c, a, tiles);
-    else if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, 5);
-    else rc = launch_fwd_tilen<HigherOrder>(h, c, a, tiles);
+    int rc = RK_ERR_UNSUPPORTED;
+    if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, JIT_TILEN);
+    else with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_tilen<decltype(rhs)>(h, c, a, tiles); });     // (tilen_supported: a built-in id)
     if (rc || mode == RK_MODE_FILTER) return rc;
     const bool sim = mode == RK_MODE_SIM;
     const int bps = div_up(n_units, 64);
@@ -1006,13 +1001,10 @@ int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
         RK_REQUIRE((size_t)bps * (size_t)n_count < 0x7fffffffull, RK_ERR_UNSUPPORTED,
                    "blocked tile path: n_steps * n_traj * n_block too large for one launch");
         const dim3 grid((unsigned)(bps * n_count)), block(64);
-#define RK_GAIN(P_)                                                                                     \
-    case P_:                                                                                            \
-        if (sim) hipLaunchKernelGGL((tilen_gain_kernel<P_, true>), grid, block, 0, st, a, tiles, ws, bps, n_first);   \
-        else hipLaunchKernelGGL((tilen_gain_kernel<P_, false>), grid, block, 0, st, a, tiles, ws, bps, n_first);      \
-        break;
-        switch (P) { RK_GAIN(4) RK_GAIN(5) RK_GAIN(6) RK_GAIN(7) RK_GAIN(8) }
-#undef RK_GAIN
+        dispatch_int<4, 8>(P, [&](auto P_) {
+            if (sim) hipLaunchKernelGGL((tilen_gain_kernel<P_, true>), grid, block, 0, st, a, tiles, ws, bps, n_first);
+            else hipLaunchKernelGGL((tilen_gain_kernel<P_, false>), grid, block, 0, st, a, tiles, ws, bps, n_first);
+        });
         RK_HIP(hipGetLastError());
         return RK_OK;
     };
@@ -1043,9 +1035,9 @@ int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
             if (tilen_nb(P) == 1) hipLaunchKernelGGL((bwd_mv_tilen_kernel<1>), cgrid, cblock, 0, h->stream, a, tiles, ws, P, n_top, n_bot);
             else hipLaunchKernelGGL((bwd_mv_tilen_kernel<2>), cgrid, cblock, 0, h->stream, a, tiles, ws, P, n_top, n_bot);
         } else {
-#define RK_ROWS(P_) case P_: hipLaunchKernelGGL((bwd_mv_tilen_rows_kernel<P_>), cgrid, cblock, 0, h->stream, a, tiles, ws, n_top, n_bot); break;
-            switch (P) { RK_ROWS(4) RK_ROWS(5) RK_ROWS(6) RK_ROWS(7) RK_ROWS(8) }
-#undef RK_ROWS
+            dispatch_int<4, 8>(P, [&](auto P_) {
+                hipLaunchKernelGGL((bwd_mv_tilen_rows_kernel<P_>), cgrid, cblock, 0, h->stream, a, tiles, ws, n_top, n_bot);
+            });
         }
         RK_HIP(hipGetLastError());
         return RK_OK;
@@ -1065,13 +1057,10 @@ int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
         double* const dbg = getenv("RK_TILEN_STAMPS") ? ws : nullptr;        // (the two-kernel form's workspace is free here)
         const dim3 fgrid(div_up(n_units, 4)), fblock(64 * (1 + (nprod == 2 ? 2 : 4)));
         LaunchTimer t(h, "bwd_mv_tilen_fused_kernel");
-#define RK_FUSED(P_)                                                                                                         \
-    case P_:                                                                                                                 \
-        if (nprod == 2) hipLaunchKernelGGL((bwd_mv_tilen_fused_kernel<P_, 2>), fgrid, fblock, 0, h->stream, a, tiles, a.N - 1, 1, dbg);   \
-        else hipLaunchKernelGGL((bwd_mv_tilen_fused_kernel<P_, 4>), fgrid, fblock, 0, h->stream, a, tiles, a.N - 1, 1, dbg);      \
-        break;
-        switch (P) { RK_FUSED(5) RK_FUSED(6) RK_FUSED(7) RK_FUSED(8) }
-#undef RK_FUSED
+        dispatch_int<5, 8>(P, [&](auto P_) {
+            if (nprod == 2) hipLaunchKernelGGL((bwd_mv_tilen_fused_kernel<P_, 2>), fgrid, fblock, 0, h->stream, a, tiles, a.N - 1, 1, dbg);
+            else hipLaunchKernelGGL((bwd_mv_tilen_fused_kernel<P_, 4>), fgrid, fblock, 0, h->stream, a, tiles, a.N - 1, 1, dbg);
+        });
         t.stop();
         RK_HIP(hipGetLastError());
         return RK_OK;
@@ -1085,9 +1074,9 @@ int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
         constexpr int CHUNK = 32;                          // time steps per wave: the block constants are loaded once per chunk
         const dim3 ggrid(div_up(n_units, 4), div_up(steps, CHUNK));
         LaunchTimer t(h, "tilen_gain_cols_kernel");
-#define RK_COLS(P_) case P_: hipLaunchKernelGGL((tilen_gain_cols_kernel<P_>), ggrid, cblock, 0, h->stream, a, tiles, ws, 1, steps, CHUNK); break;
-        switch (P) { RK_COLS(4) RK_COLS(5) RK_COLS(6) RK_COLS(7) RK_COLS(8) }
-#undef RK_COLS
+        dispatch_int<4, 8>(P, [&](auto P_) {
+            hipLaunchKernelGGL((tilen_gain_cols_kernel<P_>), ggrid, cblock, 0, h->stream, a, tiles, ws, 1, steps, CHUNK);
+        });
         t.stop();
         RK_HIP(hipGetLastError());
     } else {

@@ -13,7 +13,7 @@ the device buffers are reused by the next call with the same configuration, afte
 """
 import numpy as np
 from .. import _lib
-from ..solve import cached_plan
+from ..solve import TILE_LAYOUTS, cached_plan
 from .logpost import gauss_obs_logpost, obs_index
 
 
@@ -69,12 +69,8 @@ def basic(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate
     # generic callable: fetch only the observed time slices
     rows = []
     for n in ind:
-        if plan.layout == _lib.LAYOUT_TILE3:
-            rows.append(plan.var_state.slice0_host(int(n))[..., 3])            # (B, d, 3) means
-        elif plan.layout == _lib.LAYOUT_TILE4:
-            rows.append(plan.var_state.slice0_host(int(n))[..., 16:])          # (B, d, 4) means
-        elif plan.layout == _lib.LAYOUT_TILEP:
-            rows.append(plan.var_state.slice0_host(int(n))[..., plan.p * plan.p:])   # (B, d, p) means
+        if plan.layout in TILE_LAYOUTS:
+            rows.append(plan.records_mean_var(plan.var_state.slice0_host(int(n)))[0])   # (B, d, p) means
         elif plan.layout == _lib.LAYOUT_TRAJ_MAJOR:
             rows.append(plan.mean_state.to_host()[:, int(n)])
         else:

@@ -11,6 +11,7 @@ Only B doubles leave the GPU instead of the (B, N+1, d, p) path.
 import ctypes as C
 import numpy as np
 from .. import _lib
+from ..solve import TILE_LAYOUTS
 
 
 def obs_index(t_min, t_max, n_steps, obs_times):
@@ -40,7 +41,7 @@ def gauss_obs_logpost(plan, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10
         state, layout = plan.x_state, _lib.LAYOUT_BATCH_MINOR
     else:
         layout = plan.layout
-        state = plan.var_state if layout in (_lib.LAYOUT_TILE3, _lib.LAYOUT_TILE4, _lib.LAYOUT_TILEP) else plan.mean_state
+        state = plan.var_state if layout in TILE_LAYOUTS else plan.mean_state
     # observations / indices / output live on the plan and are re-uploaded only when they change (a pseudo-marginal
     # chain calls this once per step with the same data): per call one upload (upars) and one kernel
     cache = plan.__dict__.setdefault("_logpost_cache", {})

@@ -28,6 +28,8 @@ from .device import default_device, batch_minor as _bm
 from .ode import DeviceODE
 
 _KALMAN = {"standard": _lib.KALMAN_STANDARD, "square-root": _lib.KALMAN_SQRT}
+# layouts whose var_state holds the filtered / smoothed moments as tile records (mean_state unused)
+TILE_LAYOUTS = (_lib.LAYOUT_TILE3, _lib.LAYOUT_TILE4, _lib.LAYOUT_TILEP)
 
 
 def _interrogate_id(interrogate):
@@ -234,20 +236,18 @@ class SolvePlan:
         a = arr.batch_first()                       # (B, N+1, ...)
         return a if self.batched else a[0]
 
+    def records_mean_var(self, t):
+        """(mean, var) views of tile records t (..., d, record) in this plan's layout: RK_LAYOUT_TILE3 rows [Sigma | mu]
+        (3, 4); RK_LAYOUT_TILE4 and RK_LAYOUT_TILEP one format, [Sigma row-major (p*p) | mu (p)]."""
+        if self.layout == _lib.LAYOUT_TILE3:
+            return t[..., 3], t[..., :3]
+        p = self.p
+        return t[..., p * p:], t[..., :p * p].reshape(t.shape[:-1] + (p, p))
+
     def state_host(self):
         """(mean, var) of the last filter() / mv() in the reference layout (views of one download, no transposes)."""
-        if self.layout == _lib.LAYOUT_TILE3:
-            t = np.moveaxis(self.var_state.to_host(), 1, 0)         # (B, N+1, d, 3, 4): rows [Sigma | mu]
-            mean, var = t[..., 3], t[..., :3]
-            return (mean, var) if self.batched else (mean[0], var[0])
-        if self.layout == _lib.LAYOUT_TILE4:
-            t = np.moveaxis(self.var_state.to_host(), 1, 0)         # (B, N+1, d, 20): [Sigma (16) | mu (4)]
-            mean, var = t[..., 16:], t[..., :16].reshape(t.shape[:-1] + (4, 4))
-            return (mean, var) if self.batched else (mean[0], var[0])
-        if self.layout == _lib.LAYOUT_TILEP:
-            p = self.p
-            t = np.moveaxis(self.var_state.to_host(), 1, 0)         # (B, N+1, d, p*p + p): [Sigma row-major | mu]
-            mean, var = t[..., p * p:], t[..., :p * p].reshape(t.shape[:-1] + (p, p))
+        if self.layout in TILE_LAYOUTS:
+            mean, var = self.records_mean_var(np.moveaxis(self.var_state.to_host(), 1, 0))     # (B, N+1, d, ...)
             return (mean, var) if self.batched else (mean[0], var[0])
         if self.layout == _lib.LAYOUT_TRAJ_MAJOR:                    # already the reference layout
             mean, var = self.mean_state.to_host(), self.var_state.to_host()

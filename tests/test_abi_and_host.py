@@ -231,3 +231,47 @@ def test_optional_workspace_allocation_failure_falls_back():
     d = plan_for(_lib.KALMAN_STANDARD, 40, 8, 1, _lib.RHS_LINEAR_DENSE)          # the dense path NEEDS its workspace
     with pytest.raises(MemoryError):
         d._prepare_out(_lib.MODE_MV)
+
+
+def _user_fitz(X, t, **params):
+    a, b, c = params["theta"]
+    V, R = X[:, 0]
+    return np.array([[c * (V - V * V * V / 3 + R)], [-1 / c * (V - a + b * R)]])
+
+
+def solve_route_table():
+    """rk_solve_layout / rk_solve_workspace_bytes / rk_solve_sizes (return codes and values) over the configuration grid of
+    tests/golden/solve_routes.npz: every built-in right-hand side, then one traced user right-hand side (n_block = 2) at
+    n_bstate 3 and 4, whose tile routes depend on a hiprtc build.  Host-only: no device is touched."""
+    import itertools
+    import rodeo_amd as ra
+    from rodeo_amd import _lib
+    lib = _lib.load()
+    user = ra.ode.from_python(_user_fitz, 2, theta=3)
+    grids = [((_lib.RHS_FITZHUGH_NAGUMO, _lib.RHS_LORENZ63, _lib.RHS_HIGHER_ORDER, _lib.RHS_LINEAR_DENSE), range(1, 11)),
+             ((user.rhs_id,), (3, 4))]
+    rows = []
+    for rhs_ids, bstates in grids:
+        for rhs, n_block, n_bstate, n_bmeas, itg, kalman, flags, mode in itertools.product(
+                rhs_ids, (1, 2, 3), bstates, (1, 2), range(4), (_lib.KALMAN_STANDARD, _lib.KALMAN_SQRT),
+                (0, _lib.FLAG_STORE_PRED, _lib.FLAG_BATCH_MINOR), (_lib.MODE_FILTER, _lib.MODE_MV, _lib.MODE_SIM)):
+            cfg = _lib.SolveCfg(n_traj=37, n_steps=11, n_block=n_block, n_bstate=n_bstate, n_bmeas=n_bmeas, rhs_id=rhs,
+                                interrogate=itg, kalman_type=kalman, n_theta=3, flags=flags, t_min=0.0, t_max=1.0, seed=0,
+                                traj_offset=0)
+            layout, ws, mb, vb = ctypes.c_int32(-1), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+            rc_l = lib.rk_solve_layout(ctypes.byref(cfg), mode, ctypes.byref(layout))
+            rc_w = lib.rk_solve_workspace_bytes(ctypes.byref(cfg), mode, ctypes.byref(ws))
+            rc_s = lib.rk_solve_sizes(ctypes.byref(cfg), layout.value, ctypes.byref(mb), ctypes.byref(vb))
+            rows.append((-1 if rhs >= _lib.RHS_USER_BASE else rhs, n_block, n_bstate, n_bmeas, itg, kalman, flags, mode,
+                         rc_l, layout.value, rc_w, ws.value, rc_s, mb.value, vb.value))
+    return np.array(rows, dtype=np.int64)
+
+
+def test_solve_routes_match_the_recorded_table():
+    """The path every configuration takes (its output layout, workspace and buffer sizes) is the one recorded in
+    tests/golden/solve_routes.npz (tests/golden/make_solve_routes.py)."""
+    want = np.load(os.path.join(ROOT, "tests", "golden", "solve_routes.npz"))["routes"]
+    got = solve_route_table()
+    assert got.shape == want.shape
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, f"{bad.size} configurations differ, first: got {got[bad[0]].tolist()} want {want[bad[0]].tolist()}"
