@@ -253,6 +253,28 @@ int rk_fenrir_workspace_bytes(const rk_solve_cfg* cfg, size_t* bytes);
 int rk_fenrir_solve_mv(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out,
                        const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
                        int32_t n_obs, int32_t n_bobs, void* workspace);
+
+/* DALTON for Gaussian observations (src/rodeo/inference/dalton.py:39-545, kalman_type = standard).  Observations as for
+ * rk_fenrir_backward (n_bobs = 1..3), obs_ind strictly increasing up to n_steps; an observation at grid index 0 enters the
+ * joint density only, indices above n_steps never match.  Served: n_bmeas = 1, n_bstate 2..6 (2..5 with three or more
+ * blocks), interrogate rodeo / schober / kramer, any built-in right-hand side or a user one with n_bmeas = 1.  Routes: the
+ * p = 3 MFMA tiles (n_bobs = 1, n_block 1..4, a configuration of the tile solver; dalton_tile3_kernels.hpp) unless
+ * RK_DALTON_LANES=1, else the lane-per-trajectory kernels (dalton_kernels.hpp).
+ * rk_dalton_layout: the layout that rk_dalton_solve writes for this cfg / mode / n_bobs (RK_LAYOUT_TILE3 on the tiles,
+ * RK_LAYOUT_BATCH_MINOR on the lanes; the cfg's flags do not enter), or RK_ERR_UNSUPPORTED (+ message) if not served.
+ * rk_dalton_loglik: log p(Y | Z = 0) = logdens_joint - logdens_marg per trajectory into logdens (B); both filters of all B
+ * trajectories run in one launch and nothing else is written (`out` is not needed).
+ * rk_dalton_solve: the joint filter (RK_MODE_FILTER), + the smoothing pass (RK_MODE_MV) or + the sampler (RK_MODE_SIM) of
+ * rk_solve_mv / rk_solve_sim into `out`, in exactly the layout rk_solve_layout(cfg, mode) reports -- refused unless that
+ * equals rk_dalton_layout (set RK_FLAG_BATCH_MINOR where they differ).  RK_FLAG_STORE_PRED (lanes) also writes the
+ * predictions.  On the tiles out->var_state holds the records (rk_solve_sizes) and out->mean_state is not used.            */
+int rk_dalton_layout(const rk_solve_cfg* cfg, int32_t mode, int32_t n_bobs, int32_t* layout);
+int rk_dalton_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in,
+                     const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
+                     int32_t n_obs, int32_t n_bobs, double* logdens);
+int rk_dalton_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                    const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
+                    int32_t n_obs, int32_t n_bobs);
 /* The same on the records of the blocked-tile forward pass (kalman_type standard, n_bstate 4 .. 8, rk_solve_filter WITHOUT
  * RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR: out->var_state = the records): predicted moments are re-evaluated, nothing but the
  * filtered records is read; the result goes to mean_out (N+1, d, p, B) and var_out (N+1, d, p, p, B), batch-minor.

@@ -97,6 +97,9 @@ SIGNATURES = {
     "rk_fenrir_workspace_bytes": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "rk_fenrir_solve_mv": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "rk_fenrir_solve_mv_tiles": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "rk_dalton_layout": (C.c_int, [_P, _I, _I, C.POINTER(C.c_int32)]),
+    "rk_dalton_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "rk_dalton_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I]),
     "rk_kalman_predict_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 7),
     "rk_kalman_update_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 8),
     "rk_kalman_filter_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 13),

@@ -82,6 +82,11 @@ static std::string kernel_expr(const UserRhs& u, int P, int itg, JitKind kind) {
         snprintf(buf, sizeof buf, "rk::fwd_kernel_m<rk::UserRhsT, %d, %d, %s>", P, itg, kind == JIT_FWD_M_STORE_PRED ? "true" : "false");
     else if (kind == JIT_SQRT) snprintf(buf, sizeof buf, "rk::fwd_sqrt_kernel<rk::UserRhsT, %d, %d>", P, itg);
     else if (kind == JIT_DENSE_ITG) snprintf(buf, sizeof buf, "rk::dense_interrogate_kernel<rk::UserRhsT::Inner, %d, %d>", P, itg);
+    else if (kind == JIT_DALTON || kind == JIT_DALTON_STORE)      // P key = n_bstate + 16 n_bobs (user_dalton)
+        snprintf(buf, sizeof buf, "rk::dalton_fwd_kernel<rk::UserRhsT, %d, %d, %d, %s>", P % 16, itg, P / 16,
+                 kind == JIT_DALTON_STORE ? "true" : "false");
+    else if (kind == JIT_DALTON_TILE3 || kind == JIT_DALTON_TILE3_STORE)
+        snprintf(buf, sizeof buf, "rk::dalton_fwd_tile3_kernel<rk::UserRhsT, %d, %s>", itg, kind == JIT_DALTON_TILE3_STORE ? "true" : "false");
     else if (kind == JIT_TILEN) snprintf(buf, sizeof buf, "rk::fwd_tilen_kernel<rk::UserRhsT, %d, %d>", itg, P);  // P here = NB
     else snprintf(buf, sizeof buf, "rk::fwd_kernel<rk::UserRhsT, %d, %d, %s>", P, itg, kind == JIT_FWD_STORE_PRED ? "true" : "false");
     return buf;
@@ -92,8 +97,11 @@ static int jit_compile(const UserRhs& u, int P, int itg, JitKind kind, std::vect
     const std::string src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n"
                                         "#include \"solve_tile3_kernels.hpp\"\n#include \"solve_tile4_kernels.hpp\"\n"
                                         "#include \"solve_tilen_kernels.hpp\"\n#include \"solve_sqrt_kernels.hpp\"\n"
-                                        "#include \"solve_small_m_kernels.hpp\"\n#include \"solve_dense_itg_kernels.hpp\"\nnamespace rk {\n") +
-                            u.source + "\nusing UserRhsT = " + u.type_name + ";\n}  // namespace rk\n";
+                                        "#include \"solve_small_m_kernels.hpp\"\n#include \"solve_dense_itg_kernels.hpp\"\n") +
+                            // (only the DALTON kinds include its header: the source of every other build is unchanged)
+                            (kind == JIT_DALTON || kind == JIT_DALTON_STORE ? "#include \"dalton_kernels.hpp\"\n" : "") +
+                            (kind == JIT_DALTON_TILE3 || kind == JIT_DALTON_TILE3_STORE ? "#include \"dalton_tile3_kernels.hpp\"\n" : "") +
+                            "namespace rk {\n" + u.source + "\nusing UserRhsT = " + u.type_name + ";\n}  // namespace rk\n";
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "rk_user_rhs.hip", kJitNumHeaders, kJitHeaderSources, kJitHeaderNames) !=
         HIPRTC_SUCCESS) {
@@ -286,6 +294,29 @@ int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     void* params[] = {&args};
     LaunchTimer t(h, "fwd_kernel<user>");
     RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, 64), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
+    t.stop();
+    return RK_OK;
+}
+
+// DALTON's forward filters around a user right-hand side.  Lanes (dalton_kernels.hpp): the log-likelihood form (32
+// trajectories per wave, joint and marginal filter in its two halves) or the joint filter's store form (64 per wave).
+// Tiles (dalton_tile3_kernels.hpp, n_bstate = 3, n_bobs = 1): 2 B or B filter instances of n_block tiles.
+int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, int n_bobs, bool store,
+                bool tile, double* out) {
+    int rc = user_rhs_check(c);
+    if (rc) return rc;
+    RK_REQUIRE(user_n_bmeas(c->rhs_id) == 1, RK_ERR_UNSUPPORTED, "dalton: n_bmeas = 1 only");
+    hipFunction_t fn;
+    if (tile) rc = jit_get(h, c->rhs_id, 3, c->interrogate, store ? JIT_DALTON_TILE3_STORE : JIT_DALTON_TILE3, &fn);
+    else rc = jit_get(h, c->rhs_id, c->n_bstate + 16 * n_bobs, c->interrogate, store ? JIT_DALTON_STORE : JIT_DALTON, &fn);
+    if (rc) return rc;
+    SolveArgs args = a;
+    const DaltonObs* op = &o;
+    void* params[] = {&args, (void*)op, &out};
+    const int grid = tile ? div_up((store ? a.B : 2 * a.B) * c->n_block, c->n_block == 3 ? 3 : 4) : div_up(a.B, store ? 64 : 32);
+    LaunchTimer t(h, tile ? (store ? "dalton_fwd_tile3_kernel<store, user>" : "dalton_fwd_tile3_kernel<loglik, user>")
+                          : (store ? "dalton_fwd_kernel<store, user>" : "dalton_fwd_kernel<loglik, user>"));
+    RK_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
     t.stop();
     return RK_OK;
 }

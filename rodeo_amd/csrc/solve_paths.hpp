@@ -14,6 +14,13 @@ namespace rk {
 
 struct DenseItgArgs;
 struct SimLogpost;
+struct DaltonObs;
+
+// ---- lane-per-trajectory solver (solve_small.hip): helpers that DALTON (dalton.hip) shares ------------------------------
+int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in);
+int make_args(const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, SolveArgs& a);
+int begin_solve(rk_handle h);
+int small_backward_pass(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode);
 
 // ---- dense large-block path (solve_dense.hip) ----------------------------------------------------------------------
 bool dense_supported(const rk_solve_cfg* c, int mode);
@@ -35,12 +42,19 @@ enum JitKind : int {
     JIT_FWD_M_STORE_PRED = 8, // fwd_kernel_m<.., true>
     JIT_DENSE_ITG = 9,        // dense_interrogate_kernel
     JIT_ITG_M = 10,           // interrogate_kernel_m     (n_bmeas > 1)
+    JIT_DALTON = 11,          // dalton_fwd_kernel<.., false> (log-likelihood; P key = n_bstate + 16 n_bobs)
+    JIT_DALTON_STORE = 12,    // dalton_fwd_kernel<.., true>  (joint filter's moments; same P key)
+    JIT_DALTON_TILE3 = 13,    // dalton_fwd_tile3_kernel<.., false> (log-likelihood on the p = 3 tiles)
+    JIT_DALTON_TILE3_STORE = 14,  // dalton_fwd_tile3_kernel<.., true> (RK_LAYOUT_TILE3 records)
 };
 bool is_user_rhs(int rhs_id);
 bool user_tile_available(const rk_solve_cfg* c, JitKind tile);
 int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, JitKind tile);
 int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
 int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
+int user_rhs_check(const rk_solve_cfg* c);
+int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, int n_bobs, bool store,
+                bool tile, double* out);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 bool user_dense_wanted(const rk_solve_cfg* c);
@@ -56,6 +70,7 @@ int fenrir_sqrt_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, c
 // ---- MFMA-tile paths: n_bstate = 3 (solve_tile3.hip), 4 (solve_tile4.hip), blocked 4 .. 8 (solve_tilen.hip) ----------
 bool tile3_supported(const rk_solve_cfg* c, int mode);
 int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp = nullptr);
+int tile3_backward(rk_handle h, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp = nullptr);
 bool tile3_sim_logpost_supported(const rk_solve_cfg* c, int n_obs);
 int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, const double* obs,
                             const int32_t* obs_ind, int n_obs, double noise_sd, const double* upars, int n_prior, double prior_sd,

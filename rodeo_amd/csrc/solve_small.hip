@@ -425,7 +425,7 @@ __global__ void __launch_bounds__(64) fenrir_smooth_kernel(SolveArgs a, const do
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------
-static int make_args(const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, SolveArgs& a) {
+int make_args(const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, SolveArgs& a) {
     a.B = c->n_traj; a.N = c->n_steps; a.D = c->n_block;
     a.t_min = c->t_min; a.t_max = c->t_max; a.seed = c->seed; a.traj_offset = c->traj_offset;
     a.W = in->ode_weight; a.W_b = in->ode_weight_batched;
@@ -439,7 +439,7 @@ static int make_args(const rk_solve_cfg* c, const rk_solve_in* in, const rk_solv
     return RK_OK;
 }
 
-static int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in) {
+int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in) {
     RK_REQUIRE(c && in, RK_ERR_INVALID, "null cfg / in");
     RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1,
                RK_ERR_INVALID, "non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)",
@@ -499,6 +499,11 @@ static int small_backward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a
     return RK_OK;
 }
 
+// the lane-per-trajectory smoothing (RK_MODE_MV) or sampling (RK_MODE_SIM) pass over batch-minor filtered moments
+int small_backward_pass(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode) {
+    return mode == RK_MODE_SIM ? small_backward<true>(h, c, a) : small_backward<false>(h, c, a);
+}
+
 template <class RHS>
 static int launch_itg_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step,
                           const double* mp, const double* vp, double* wm, double* mm_, double* vm) {
@@ -540,7 +545,7 @@ static void launch_fenrir_smooth(rk_handle h, const rk_solve_cfg* c, const Solve
     });
 }
 
-static int begin_solve(rk_handle h) {
+int begin_solve(rk_handle h) {
     RK_HIP(hipSetDevice(h->device));
     if (!h->profile_keep) { h->prof.clear(); h->event_used = 0; }
     return RK_OK;

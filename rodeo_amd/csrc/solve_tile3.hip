@@ -775,6 +775,11 @@ int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
     if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, JIT_TILE3);
     else with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_tile<decltype(rhs)>(h, c, a, tiles); });     // (tile3_supported: a built-in id)
     if (rc || mode == RK_MODE_FILTER) return rc;
+    return tile3_backward(h, a, tiles, mode, lp);
+}
+
+// the smoothing (RK_MODE_MV) or sampling (RK_MODE_SIM) pass over RK_LAYOUT_TILE3 records
+int tile3_backward(rk_handle h, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp) {
     if (mode == RK_MODE_SIM) {
         LaunchTimer t(h, "bwd_sim_tile3_kernel");
         if (lp) hipLaunchKernelGGL(bwd_sim_tile3_kernel<true>, dim3(div_up(a.B * a.D, 4)), dim3(256), 0, h->stream, a, tiles, a.D, *lp);
@@ -783,7 +788,7 @@ int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
         RK_HIP(hipGetLastError());
         return RK_OK;
     }
-    if (a.N < 2) return rc;
+    if (a.N < 2) return RK_OK;
     LaunchTimer t(h, "bwd_mv_tile3_kernel");
     hipLaunchKernelGGL(bwd_mv_tile3_kernel, dim3(div_up(a.B * a.D, 4)), dim3(256), 0, h->stream, a, tiles, a.D);
     t.stop();
