@@ -283,6 +283,36 @@ int rk_fenrir_solve_mv_tiles(rk_handle h, const rk_solve_cfg* cfg, const rk_solv
                              const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
                              int32_t n_obs, int32_t n_bobs, void* workspace, double* mean_out, double* var_out);
 
+/* MAGI log-density (src/rodeo/inference/magi.py:6-99): the Kalman filter of the prior X_n = Q X_{n-1} + N(0, R) per block,
+ * started from the known state x_0 = ode_state[0], that measures the first n_active components of every X_n exactly
+ * (W = eye(n_active, p), no measurement offset or noise); logdens[b] = the sum over steps and blocks of the forecast's
+ * Gaussian log-density (Cholesky form, not the eigenvalue rule of rk_fenrir_backward) at x_meas.  No right-hand side, no
+ * interrogation: the caller supplies the data.  kalman_type = RK_KALMAN_STANDARD (LU gain of standard.py:93-102) or
+ * RK_KALMAN_SQRT (square_root.py:30-101, 317-345: prior_var holds lower factors).  Served: n_bstate 2..6 (standard) or
+ * 2..7 (square-root; beyond, the lane kernel spills), n_active 1..n_bstate, any n_block; n_steps = 0 gives 0.  One lane per
+ * (trajectory, block); with n_block > 1 the block sums go to the handle's grow-only device scratch (n_block * B doubles,
+ * allocated when it grows) and a second kernel adds them in block order (no atomics): the result is the same bits from
+ * run to run.  logdens (B) is overwritten.  With n_active >= 2 and a coupled prior_weight (IBM priors included) the
+ * standard form's covariance loses its symmetry by amplified rounding, as in the reference: RK_KALMAN_SQRT is the form
+ * to use there.                                                                                                        */
+typedef struct {
+    int32_t n_traj;       /* B                                                                             */
+    int32_t n_steps;      /* N: ode_state has N + 1 time points                                            */
+    int32_t n_block;      /* d = n_vars                                                                    */
+    int32_t n_bstate;     /* p = n_deriv                                                                   */
+    int32_t n_active;     /* measured components per block, 1 .. p                                         */
+    int32_t kalman_type;  /* RK_KALMAN_*                                                                   */
+} rk_magi_cfg;
+
+typedef struct {
+    const double* x0;            int32_t x0_batched;            /* ode_state[0]  (d, p [,B])                   */
+    const double* x_meas;        int32_t x_meas_batched;        /* ode_state[1:, :, :n_active]  (N, d, n_active [,B]) */
+    const double* prior_weight;  int32_t prior_weight_batched;  /* Q  (d, p, p [,B])   prior_pars[0]            */
+    const double* prior_var;     int32_t prior_var_batched;     /* R or its lower factor (d, p, p [,B])         */
+} rk_magi_in;
+
+int rk_magi_logdens(rk_handle h, const rk_magi_cfg* cfg, const rk_magi_in* in, double* logdens);
+
 /* ---- per-step operator boundary -------------------------------------------------------------------------
  * Batched versions of the nine functions of src/rodeo/kalmantv/standard.py (kalman_type = RK_KALMAN_STANDARD)
  * and src/rodeo/kalmantv/square_root.py (RK_KALMAN_SQRT).  n = batch size (the reference's vmap axis);

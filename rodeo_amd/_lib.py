@@ -52,6 +52,18 @@ class SolveOut(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+class MagiCfg(C.Structure):
+    _fields_ = [("n_traj", C.c_int32), ("n_steps", C.c_int32), ("n_block", C.c_int32), ("n_bstate", C.c_int32),
+                ("n_active", C.c_int32), ("kalman_type", C.c_int32)]
+
+
+class MagiIn(C.Structure):
+    _fields_ = [("x0", C.c_void_p), ("x0_batched", C.c_int32),
+                ("x_meas", C.c_void_p), ("x_meas_batched", C.c_int32),
+                ("prior_weight", C.c_void_p), ("prior_weight_batched", C.c_int32),
+                ("prior_var", C.c_void_p), ("prior_var_batched", C.c_int32)]
+
+
 class OpCfg(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_state", C.c_int32), ("n_meas", C.c_int32), ("kalman_type", C.c_int32)]
 
@@ -100,6 +112,7 @@ SIGNATURES = {
     "rk_dalton_layout": (C.c_int, [_P, _I, _I, C.POINTER(C.c_int32)]),
     "rk_dalton_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "rk_dalton_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I]),
+    "rk_magi_logdens": (C.c_int, [_H, C.POINTER(MagiCfg), C.POINTER(MagiIn), _P]),
     "rk_kalman_predict_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 7),
     "rk_kalman_update_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 8),
     "rk_kalman_filter_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 13),

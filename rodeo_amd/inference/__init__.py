@@ -5,11 +5,14 @@ Gaussian observation log-posterior reduction used by pseudo-marginal log-posteri
 kernels of src/rodeo/inference/pseudo_marginal.py for many chains in lock-step (SURVEY.md section 8f "next-2").
 ``fenrir``: the Fenrir likelihood (src/rodeo/inference/fenrir.py:261-327, "next-4").  ``dalton``: the DALTON likelihood
 for Gaussian observations and its data-adaptive solver (src/rodeo/inference/dalton.py:39-545; ``rodeo_amd.inference.dalton``
-holds ``solve_mv`` / ``solve_sim``).  ``daltonng`` (non-Gaussian observations: derivatives of a user log-likelihood) and
-``magi`` are out of scope.
+holds ``solve_mv`` / ``solve_sim``).  ``magi_logdens``: the MAGI log-density (src/rodeo/inference/magi.py:6-99;
+``rodeo_amd.inference.magi`` is its module).  ``daltonng`` (non-Gaussian observations: derivatives of a user
+log-likelihood) is out of scope.
 """
 from .basic import basic
 from .logpost import gauss_obs_logpost, obs_index, sim_logpost, stage_upars
 from . import pseudo_marginal
 from .fenrir import fenrir
 from .dalton import dalton
+from . import magi
+from .magi import magi_logdens
