@@ -313,6 +313,28 @@ typedef struct {
 
 int rk_magi_logdens(rk_handle h, const rk_magi_cfg* cfg, const rk_magi_in* in, double* logdens);
 
+/* Laplace approximation of a k-parameter log-posterior by central differences (rodeo_amd/inference/laplace.py replaces
+ * jax.grad / jax.hessian of docs/examples/parameter.md:239-275).  Device arrays, row-major, centre axis first; k <= 12
+ * (RK_ERR_UNSUPPORTED beyond).  S = 2 k^2 + 1 stencil points per centre, in this order:
+ *     s = 0                        u
+ *     s = 1 + 2 i,  2 + 2 i        u + h_i e_i,  u - h_i e_i                                 i = 0 .. k-1
+ *     s = 1 + 2 k + 4 q + 0 .. 3   u + h_i e_i + h_j e_j, u + h_i e_i - h_j e_j, u - h_i e_i + h_j e_j, u - h_i e_i - h_j e_j
+ *                                  for the pairs i < j in row-major order (0,1), (0,2), .., (k-2,k-1), q = 0, 1, ..
+ * rk_fd_stencil writes the points: u (C, k), step (k) -> out (C, S, k).
+ * rk_fd_grad_hess turns the values vals (C, S) of the log-posterior at those points into grad (C, k) =
+ * (f(+i) - f(-i)) / (2 h_i) and hess (C, k, k): diagonal ((f(+i) - f(0)) + (f(-i) - f(0))) / h_i^2, off the diagonal
+ * ((f(++) - f(+-)) - (f(-+) - f(--))) / (4 h_i h_j), both triangles from the same expression.  Each entry is one fixed
+ * expression (no atomics): identical bits from call to call.  n_bad (C) counts the centre's non-finite values; where it is
+ * not 0 the centre's grad and hess are NaN.
+ * rk_newton_step: per centre the Cholesky factor of -hess + damping[c] I, delta (C, k) = (-hess + damping I)^{-1} grad,
+ * logdet (C) = log det(-hess + damping I), ok (C) = 1; a pivot that is not positive gives ok = 0 and NaN in delta and
+ * logdet.  The three kernels are latency-bound and not tuned.                                                        */
+int rk_fd_stencil(rk_handle h, int32_t n_centre, int32_t k, const double* u, const double* step, double* out);
+int rk_fd_grad_hess(rk_handle h, int32_t n_centre, int32_t k, const double* vals, const double* step, double* grad,
+                    double* hess, int32_t* n_bad);
+int rk_newton_step(rk_handle h, int32_t n_centre, int32_t k, const double* grad, const double* hess, const double* damping,
+                   double* delta, double* logdet, int32_t* ok);
+
 /* ---- per-step operator boundary -------------------------------------------------------------------------
  * Batched versions of the nine functions of src/rodeo/kalmantv/standard.py (kalman_type = RK_KALMAN_STANDARD)
  * and src/rodeo/kalmantv/square_root.py (RK_KALMAN_SQRT).  n = batch size (the reference's vmap axis);

@@ -113,6 +113,9 @@ SIGNATURES = {
     "rk_dalton_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "rk_dalton_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I]),
     "rk_magi_logdens": (C.c_int, [_H, C.POINTER(MagiCfg), C.POINTER(MagiIn), _P]),
+    "rk_fd_stencil": (C.c_int, [_H, _I, _I, _P, _P, _P]),
+    "rk_fd_grad_hess": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P]),
+    "rk_newton_step": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P, _P]),
     "rk_kalman_predict_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 7),
     "rk_kalman_update_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 8),
     "rk_kalman_filter_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 13),

@@ -1,0 +1,140 @@
+// Device pieces of the Laplace driver (rodeo_amd/inference/laplace.py): the central-difference stencil of a k-parameter
+// log-posterior around C centres, its reduction to gradient and Hessian, and one damped Newton step per centre.
+//
+// Stencil order, S = 2 k^2 + 1 points per centre (tests/laplace_oracle.py restates it):
+//     s = 0                       u
+//     s = 1 + 2 i,  2 + 2 i       u + h_i e_i,  u - h_i e_i                                   i = 0 .. k-1
+//     s = 1 + 2 k + 4 q + 0 .. 3  u + h_i e_i + h_j e_j,  u + h_i e_i - h_j e_j,
+//                                 u - h_i e_i + h_j e_j,  u - h_i e_i - h_j e_j               pairs i < j in row-major
+//                                                                                            order, q = 0 .. k(k-1)/2 - 1
+// All three kernels are small and latency-bound (k <= 12: at most 289 points and 144 Hessian entries per centre); they
+// are written for clarity and are not tuned.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "linalg_small.hpp"
+
+namespace rk {
+
+constexpr int LAPLACE_KMAX = 12;
+
+// The q-th pair (i, j), i < j, of the row-major enumeration (0,1), (0,2), .., (0,k-1), (1,2), ..
+__device__ __forceinline__ void fd_pair(int q, int k, int& i, int& j) {
+    i = 0;
+    int row = k - 1;                      // pairs in row i
+    while (q >= row) {
+        q -= row;
+        ++i;
+        --row;
+    }
+    j = i + 1 + q;
+}
+
+// index of the pair (i, j), i < j
+__device__ __forceinline__ int fd_pair_index(int i, int j, int k) { return i * (2 * k - i - 1) / 2 + (j - i - 1); }
+
+// One lane per element of out (C, S, k).
+__global__ void __launch_bounds__(256) fd_stencil_kernel(const double* __restrict__ u, const double* __restrict__ step,
+                                                         int C, int k, double* __restrict__ out) {
+    const int S = 2 * k * k + 1;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)C * S * k) return;
+    const int d = (int)(e % k);
+    const int s = (int)((e / k) % S);
+    const int c = (int)(e / ((long long)k * S));
+    int i = -1, j = -1;
+    double si = 0.0, sj = 0.0;
+    if (s >= 1 && s <= 2 * k) {
+        i = (s - 1) >> 1;
+        si = ((s - 1) & 1) ? -1.0 : 1.0;
+    } else if (s > 2 * k) {
+        const int r = s - 1 - 2 * k;
+        fd_pair(r >> 2, k, i, j);
+        si = (r & 2) ? -1.0 : 1.0;
+        sj = (r & 1) ? -1.0 : 1.0;
+    }
+    double v = u[(size_t)c * k + d];
+    if (d == i) v += si * step[d];
+    if (d == j) v += sj * step[d];
+    out[e] = v;
+}
+
+// One workgroup per centre, one lane per Hessian entry (i, j); the lanes of the diagonal also write the gradient.
+// Every entry is one fixed expression of at most five stencil values (no sums across lanes, no atomics): the same bits
+// from call to call, and hess[i][j] == hess[j][i] because both lanes evaluate the same expression.  The count of
+// non-finite stencil values is an integer reduction over the workgroup.
+__global__ void __launch_bounds__(256) fd_grad_hess_kernel(const double* __restrict__ vals, const double* __restrict__ step,
+                                                           int k, double* __restrict__ grad, double* __restrict__ hess,
+                                                           int* __restrict__ n_bad) {
+    const int S = 2 * k * k + 1;
+    const int c = blockIdx.x, t = threadIdx.x;
+    const double* f = vals + (size_t)c * S;
+    int bad = 0;
+    for (int s0 = 0; s0 < S; s0 += 256) {           // the trip count is the same in every lane
+        const int s = s0 + t;
+        bad += __syncthreads_count(s < S && !isfinite(f[s < S ? s : 0]));
+    }
+    if (t == 0) n_bad[c] = bad;
+    if (t >= k * k) return;
+    const int i = t / k, j = t % k;
+    const double nan = __builtin_nan("");
+    if (i == j) {
+        const double f0 = f[0], fp = f[1 + 2 * i], fm = f[2 + 2 * i], h = step[i];
+        hess[((size_t)c * k + i) * k + i] = bad ? nan : ((fp - f0) + (fm - f0)) / (h * h);
+        grad[(size_t)c * k + i] = bad ? nan : (fp - fm) / (2.0 * h);
+    } else {
+        const int a = i < j ? i : j, b = i < j ? j : i;
+        const double* g = f + 1 + 2 * k + 4 * fd_pair_index(a, b, k);
+        hess[((size_t)c * k + i) * k + j] = bad ? nan : ((g[0] - g[1]) - (g[2] - g[3])) / ((4.0 * step[a]) * step[b]);
+    }
+}
+
+// One lane per centre: Cholesky L L^T = -hess + damping I in registers (psd_factor reads the lower triangle), delta =
+// (L L^T)^{-1} grad, logdet = 2 sum log L_ii.  A pivot that is not positive (NaN included) gives ok = 0 and NaN outputs.
+template <int K>
+__global__ void __launch_bounds__(64) newton_step_kernel(const double* __restrict__ grad, const double* __restrict__ hess,
+                                                         const double* __restrict__ damping, int C,
+                                                         double* __restrict__ delta, double* __restrict__ logdet,
+                                                         int* __restrict__ ok_out) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    double A[K][K], L[K][K], y[K];
+    const double lam = damping[c];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) A[i][j] = j <= i ? -hess[((size_t)c * K + i) * K + j] : 0.0;
+        A[i][i] += lam;
+        y[i] = grad[(size_t)c * K + i];
+    }
+    psd_factor<K>(A, L);
+    bool ok = true;
+    double ld = 0.0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        ok = ok && L[i][i] > 0.0;
+        ld += log(ok ? L[i][i] : 1.0);
+    }
+    // L z = grad, then L^T delta = z.  The substitutions divide by L_ii; the factor itself is psd_factor's (its
+    // reciprocal pivots are fast_rcp, <= 1 ulp)
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        double s = y[i];
+#pragma unroll
+        for (int m = 0; m < i; ++m) s = fma(-L[i][m], y[m], s);
+        y[i] = s / (ok ? L[i][i] : 1.0);
+    }
+#pragma unroll
+    for (int i = K - 1; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int m = i + 1; m < K; ++m) s = fma(-L[m][i], y[m], s);
+        y[i] = s / (ok ? L[i][i] : 1.0);
+    }
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int i = 0; i < K; ++i) delta[(size_t)c * K + i] = ok ? y[i] : nan;
+    logdet[c] = ok ? 2.0 * ld : nan;
+    ok_out[c] = ok ? 1 : 0;
+}
+
+}  // namespace rk

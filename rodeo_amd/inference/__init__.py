@@ -7,7 +7,9 @@ kernels of src/rodeo/inference/pseudo_marginal.py for many chains in lock-step (
 for Gaussian observations and its data-adaptive solver (src/rodeo/inference/dalton.py:39-545; ``rodeo_amd.inference.dalton``
 holds ``solve_mv`` / ``solve_sim``).  ``magi_logdens``: the MAGI log-density (src/rodeo/inference/magi.py:6-99;
 ``rodeo_amd.inference.magi`` is its module).  ``daltonng`` (non-Gaussian observations: derivatives of a user
-log-likelihood) is out of scope.
+log-likelihood) is out of scope.  ``laplace``: mode, Hessian and normal approximation of a batched log-posterior by central
+differences on the device (docs/examples/parameter.md:239-275; ``rodeo_amd.inference.laplace`` is the module, its function
+is ``laplace.laplace``).
 """
 from .basic import basic
 from .logpost import gauss_obs_logpost, obs_index, sim_logpost, stage_upars
@@ -16,3 +18,4 @@ from .fenrir import fenrir
 from .dalton import dalton
 from . import magi
 from .magi import magi_logdens
+from . import laplace

@@ -1,0 +1,225 @@
+"""
+Laplace approximation of a parameter posterior: what ``fitz_laplace`` of docs/examples/parameter.md:239-275 does with
+``jaxopt`` (mode), ``jax.jacfwd(jax.jacrev(.))`` (Hessian at the mode) and ``jax.random.multivariate_normal`` (draws), for
+a log-posterior that is built around one BATCHED call of ``fenrir`` / ``dalton`` / ``basic`` / ``magi_logdens``.
+
+There is no automatic differentiation here.  Gradient and Hessian are central differences: for k parameters one
+evaluation of both needs S = 2 k^2 + 1 log-posterior values, and the solver evaluates that many trajectories in one
+launch, so one Newton iteration costs one batched ``logpost`` call.  Results are therefore finite-difference values: with
+the step h the truncation error is O(h^2) and the rounding error of a second difference is about eps |f| / h^2.
+``step=None`` takes h_i = eps^(1/4) max(1, |u_i|) (about 1.2e-4) at the starting point, the usual balance of the two for
+second differences; pass ``step`` (a scalar or (k,)) to override it.  The step is fixed for the whole run.
+
+    laplace(logpost, upars_init, *, step=None, max_iter=50, gtol=1e-5, n_samples=0, key=None) -> LaplaceResult
+
+``logpost(upars (B, k)) -> (B,)`` is the user's batched log-posterior on the unconstrained scale: their constraint
+transform and log-prior in NumPy around one batched solver call.  ``upars_init`` is (k,) or (C, k): C independent starts
+are solved in lock-step, every ``logpost`` call gets the (C S, k) points of all of them.
+
+Each iteration: ``rk_fd_stencil`` (the points, csrc/laplace_kernels.hpp has their order) -> download -> ``logpost`` ->
+upload -> ``rk_fd_grad_hess`` -> ``rk_newton_step``.  The optimiser is a damped Newton iteration (Levenberg-Marquardt
+on ``damping``, per centre): the step solves (-H + damping I) delta = g; the next stencil is centred on the trial point
+u + delta and its centre value is the trial value, so a trial is accepted when that value improved (or is equal within
+eps^(5/8) max(1, |f|), the resolution of the comparison) and its stencil is finite (its gradient and Hessian are then
+already there), and otherwise the kept point's step is retaken with ten times
+the damping -- a rejected step costs one launch, not two.  A Hessian whose negative is not positive definite (``ok = 0``
+from the device) raises the damping in the same way, without a new stencil.  A centre is converged when max |g_i| <
+``gtol`` at a kept point; converged centres stay in the batch unchanged.  Two consequences of the resolution in the
+acceptance rule: ``LaplaceResult.logpost`` is the value at the returned mode and may lie below the best value visited, by at
+most eps^(5/8) max(1, |f|) per accepted step; and where max |g_i| stays above ``gtol`` at that resolution (a very sharp
+posterior, or a ``gtol`` below the rounding of the differences) the iteration may go on accepting such steps until
+``max_iter`` and return ``converged = False`` with a point that is a mode to the precision of the log-density.
+
+Refused before any device work of this module (ValueError): k > 12 (the Newton step keeps its factor in registers), a
+non-finite ``upars_init`` or ``step``, a ``logpost`` that does not return one finite value per row at the starting
+points; ``n_samples > 0`` without an integer ``key``.  A later ``logpost`` result that is not of shape (C S,) is refused
+too.  Non-finite values at later stencil points are not errors: they are counted in ``n_bad`` and the trial is rejected.
+"""
+import ctypes as C
+from typing import NamedTuple
+import numpy as np
+from .. import _lib
+from ..device import default_device
+from .pseudo_marginal import standard_normal
+
+K_MAX = 12                                   # csrc/laplace_kernels.hpp LAPLACE_KMAX
+_DAMP_UP, _DAMP_DOWN, _MAX_DAMP_RAISES = 10.0, 0.1, 40
+# A trial counts as "not worse" down to this relative change of the log-posterior.  Close to the mode of a sharp posterior
+# the gain a Newton step predicts, g^2 / (2 |H|), is far below the rounding of the log-density itself while the gradient is
+# still above gtol, so a strict comparison there compares noise.  Measured on the FitzHugh-Nagumo fit at N = 800 (|H| up to
+# 1.5e6, f = 87.7): the step that took max |g| from 3e-3 to 4e-8 lowered f by 7e-10 (8e-12 relative) and a strict rule
+# threw it away, after which the run stalled at max |g| ~ 1e-3.  eps^(5/8) = 1.6e-10 is an order above that noise and two
+# below eps^(1/2) |f|, the size of the second differences the stencil is built to resolve.
+_F_RESOLUTION = np.finfo(np.float64).eps ** 0.625
+
+
+class LaplaceResult(NamedTuple):
+    """``mode`` (C, k), ``logpost`` (C,), ``hessian`` (C, k, k) of the log-posterior at the mode, ``cov`` (C, k, k) =
+    (-hessian)^-1, ``log_evidence`` (C,) = logpost + k/2 log 2 pi - 1/2 log det(-hessian), ``converged`` (C,) bool,
+    ``n_iter`` (stencils evaluated), ``n_bad`` (C,) non-finite stencil values met on the way, ``samples`` (C, n_samples, k)
+    or None.  ``cov`` and ``log_evidence`` are NaN where -hessian is not positive definite.  For a (k,) start the leading
+    axis is dropped."""
+    mode: np.ndarray
+    logpost: np.ndarray
+    hessian: np.ndarray
+    cov: np.ndarray
+    log_evidence: np.ndarray
+    converged: np.ndarray
+    n_iter: int
+    n_bad: np.ndarray
+    samples: object = None
+
+
+def n_stencil(k):
+    """Number of stencil points per centre."""
+    return 2 * k * k + 1
+
+
+def default_step(upars):
+    """h_i = eps^(1/4) max(1, |u_i|), the largest over the centres: (k,)."""
+    u = np.atleast_2d(np.asarray(upars, dtype=np.float64))
+    return np.finfo(np.float64).eps ** 0.25 * np.maximum(1.0, np.max(np.abs(u), axis=0))
+
+
+def _check(logpost, upars_init, step, n_samples, key):
+    """The refusals that need no device; returns (u (C, k), step (k,), single, f0 (C,))."""
+    u = np.array(upars_init, dtype=np.float64)
+    single = u.ndim == 1
+    if u.ndim not in (1, 2) or u.size == 0:
+        raise ValueError(f"laplace: upars_init must have shape (k,) or (C, k), got {u.shape}")
+    u = np.atleast_2d(u)
+    n_c, k = u.shape
+    if k > K_MAX:
+        raise ValueError(f"laplace: k <= {K_MAX} parameters (the device Newton step keeps its factor in registers), got {k}")
+    if not np.all(np.isfinite(u)):
+        raise ValueError("laplace: upars_init is not finite")
+    h = default_step(u) if step is None else np.broadcast_to(np.asarray(step, dtype=np.float64), (k,)).copy()
+    if not (np.all(np.isfinite(h)) and np.all(h > 0)):
+        raise ValueError("laplace: step must be positive and finite")
+    if n_samples < 0 or (n_samples > 0 and not isinstance(key, (int, np.integer))):
+        raise ValueError("laplace: n_samples > 0 needs an integer key (the seed of the Philox stream)")
+    f0 = np.asarray(logpost(u.copy()), dtype=np.float64)
+    if f0.shape != (n_c,):
+        raise ValueError(f"laplace: logpost must return one value per row, shape ({n_c},) for {n_c} rows, got {f0.shape}")
+    if not np.all(np.isfinite(f0)):
+        raise ValueError(f"laplace: logpost is not finite at upars_init: {f0}")
+    return u, h, single, f0
+
+
+class DeviceSteps:
+    """The three device calls (``stencil``, ``grad_hess``, ``newton``) on buffers that live for one run, host arrays in and
+    out.  ``laplace`` is built on it; it is public so that one iteration can be taken apart (scripts/laplace_times.py times
+    its parts, tests/test_gpu_laplace.py checks each call against the NumPy restatement).  ``newton`` uploads gradient and
+    Hessian again although ``grad_hess`` has just produced them on the device: the driver steps from the KEPT point of
+    each centre, which after a rejected trial is not the one the last stencil was taken at."""
+
+    def __init__(self, n_c, k, h):
+        self.dev = dev = default_device()
+        self.n_c, self.k, self.S = n_c, k, n_stencil(k)
+        self.step = dev.to_device(h)
+        self.u = dev.empty((n_c, k))
+        self.pts = dev.empty((n_c, self.S, k))
+        self.vals = dev.empty((n_c, self.S))
+        self.grad, self.hess = dev.empty((n_c, k)), dev.empty((n_c, k, k))
+        self.n_bad, self.ok = dev.empty((n_c,), np.int32), dev.empty((n_c,), np.int32)
+        self.damping, self.delta, self.logdet = dev.empty((n_c,)), dev.empty((n_c, k)), dev.empty((n_c,))
+
+    def stencil(self, u):
+        """(C, k) -> the (C S, k) points on the host."""
+        self.u.upload(u)
+        _lib.check(self.dev.lib.rk_fd_stencil(self.dev.h, self.n_c, self.k, self.u.ptr, self.step.ptr, self.pts.ptr))
+        return self.pts.to_host().reshape(self.n_c * self.S, self.k)
+
+    def grad_hess(self, vals):
+        """(C S,) -> grad (C, k), hess (C, k, k), n_bad (C,)."""
+        self.vals.upload(vals.reshape(self.n_c, self.S))
+        _lib.check(self.dev.lib.rk_fd_grad_hess(self.dev.h, self.n_c, self.k, self.vals.ptr, self.step.ptr, self.grad.ptr,
+                                                self.hess.ptr, self.n_bad.ptr))
+        return self.grad.to_host(), self.hess.to_host(), self.n_bad.to_host()
+
+    def newton(self, grad, hess, damping):
+        """delta (C, k), logdet (C,), ok (C,) of the kept gradient / Hessian at the given damping."""
+        self.grad.upload(grad)
+        self.hess.upload(hess)
+        self.damping.upload(damping)
+        _lib.check(self.dev.lib.rk_newton_step(self.dev.h, self.n_c, self.k, self.grad.ptr, self.hess.ptr, self.damping.ptr,
+                                               self.delta.ptr, self.logdet.ptr, self.ok.ptr))
+        return self.delta.to_host(), self.logdet.to_host(), self.ok.to_host().astype(bool)
+
+
+def _first_damping(hess):
+    """Where damping starts when it is first needed: 2^-9 of the Hessian's largest diagonal entry (of 1 at least)."""
+    d = np.max(np.abs(np.diagonal(hess, axis1=-2, axis2=-1)), axis=-1)
+    return 2.0 ** -9 * np.maximum(1.0, np.where(np.isfinite(d), d, 1.0))
+
+
+def _raise_damping(damping, hess, which):
+    first = _first_damping(hess)
+    damping[which] = np.where(damping[which] > 0, damping[which] * _DAMP_UP, first[which])
+
+
+def laplace(logpost, upars_init, *, step=None, max_iter=50, gtol=1e-5, n_samples=0, key=None):
+    """Mode, Hessian and normal approximation of ``logpost`` from the start(s) ``upars_init`` (module docstring)."""
+    u, h, single, f_keep = _check(logpost, upars_init, step, n_samples, key)
+    n_c, k = u.shape
+    S = n_stencil(k)
+    dv = DeviceSteps(n_c, k, h)
+    grad, hess = np.full((n_c, k), np.nan), np.full((n_c, k, k), np.nan)
+    damping = np.zeros(n_c)
+    converged, failed = np.zeros(n_c, bool), np.zeros(n_c, bool)
+    n_bad = np.zeros(n_c, np.int64)
+    trial = u.copy()
+    n_iter = 0
+    while n_iter < max_iter:
+        pts = dv.stencil(trial)
+        vals = np.asarray(logpost(pts), dtype=np.float64)
+        if vals.shape != (n_c * S,):
+            raise ValueError(f"laplace: logpost returned shape {vals.shape} for {n_c * S} points ({n_c} centres x {S})")
+        g_t, h_t, bad_t = dv.grad_hess(vals)
+        f_t = vals.reshape(n_c, S)[:, 0]
+        live = ~(converged | failed)
+        n_bad += np.where(live, bad_t, 0)
+        first = n_iter == 0
+        n_iter += 1
+        with np.errstate(invalid="ignore"):
+            accept = live & (bad_t == 0) & (first | (f_t > f_keep - _F_RESOLUTION * np.maximum(1.0, np.abs(f_keep))))
+        if first:
+            failed |= live & ~accept                     # a start whose stencil is not finite has nothing to fall back on
+        u[accept], f_keep[accept], grad[accept], hess[accept] = trial[accept], f_t[accept], g_t[accept], h_t[accept]
+        damping[accept] *= _DAMP_DOWN
+        damping[damping < 1e-12] = 0.0
+        rejected = live & ~accept & ~failed
+        _raise_damping(damping, hess, rejected)
+        converged |= accept & (np.max(np.abs(grad), axis=1) < gtol)
+        live = ~(converged | failed)
+        if not live.any():
+            break
+        # the step of every kept point; an indefinite -H + damping I raises that centre's damping until the factor exists
+        g_in, h_in = np.where(live[:, None], grad, 0.0), np.where(live[:, None, None], hess, -np.eye(k))
+        for _ in range(_MAX_DAMP_RAISES):
+            delta, _, ok = dv.newton(g_in, h_in, damping)
+            if ok[live].all():
+                break
+            _raise_damping(damping, hess, live & ~ok)
+        failed |= live & ~ok
+        trial = np.where((live & ok)[:, None], u + np.nan_to_num(delta), u)
+    # curvature at the kept points, without damping
+    good = np.all(np.isfinite(hess), axis=(1, 2))
+    _, logdet, ok = dv.newton(np.zeros((n_c, k)), np.where(good[:, None, None], hess, -np.eye(k)), np.zeros(n_c))
+    ok &= good
+    cov = np.full((n_c, k, k), np.nan)
+    for c in np.flatnonzero(ok):
+        cov[c] = np.linalg.inv(-hess[c])
+        cov[c] = 0.5 * (cov[c] + cov[c].T)
+    log_ev = np.where(ok, f_keep + 0.5 * k * np.log(2 * np.pi) - 0.5 * np.where(ok, logdet, 0.0), np.nan)
+    samples = None
+    if n_samples > 0:
+        z = standard_normal(int(key), (n_c, n_samples, k))
+        samples = np.full((n_c, n_samples, k), np.nan)
+        for c in np.flatnonzero(ok):
+            samples[c] = u[c] + z[c] @ np.linalg.cholesky(cov[c]).T
+    res = (u, f_keep, hess, cov, log_ev, converged)
+    if single:
+        res = tuple(a[0] for a in res)
+        n_bad, samples = n_bad[0], (samples[0] if samples is not None else None)
+    return LaplaceResult(*res, n_iter, n_bad, samples)
