@@ -111,29 +111,56 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
     double M = r < 3 ? (c == 3 ? ld(a.x0, (size_t)blk * P + r, a.x0_b, a.B, b) : 0.0) : (c == 3 ? 1.0 : 0.0);
     // lanes without a slot in the 3 x 4 tile: row 3, or tiles past the end
     const bool st = tc.valid && r < 3;
-    const size_t tstride_all = (size_t)n_tiles * TILE_DOUBLES;
-    // In the loop every lane stores through a buffer window on this wave's part of the time row (scalar base, no
-    // per-lane pointer arithmetic: every VALU instruction lengthens the dependent chain); slot-less lanes are out of
-    // range and dropped by the hardware.
-    const char* row = (const char*)(tiles + (NW == 1 ? (size_t)blockIdx.x * TPW : (size_t)blockIdx.x * D + (size_t)wave_in_wg * 4) * TILE_DOUBLES);
+    const size_t row_bytes = (size_t)n_tiles * TILE_DOUBLES * sizeof(double);       // one time row of the tile array
+    // In the loop every lane stores through a buffer window on this wave's part of the time rows (no per-lane pointer
+    // arithmetic: every VALU instruction lengthens the dependent chain); slot-less lanes are out of range and dropped by
+    // the hardware.  The descriptor is built ONCE in front of the loop: its base is the wave's SLICE bytes of the
+    // window's first time row, the time row travels in the store's scalar offset (one s_add per step; a descriptor
+    // rebuilt from a moving 64-bit pointer cost two SALU instructions between the step's first two MFMAs and two
+    // more behind the store).  A window of k rows has (k - 1) row_bytes + SLICE records, below 2^31: every slot
+    // of every row is in range whether or not the range check counts the scalar offset (the LLVM intrinsic
+    // documents it as excluded, older GCN ISA texts as included), and the slot-less lanes' offset 2^31 is out of
+    // range either way.  Tile arrays of 2 GiB and more take several windows (WIN_ROWS rows each; wave-uniform, decided
+    // here and not in the loop).
+    constexpr uint32_t SLICE = TPW * TILE_DOUBLES * sizeof(double), WIN_MAX = 0x7fffffffu - SLICE;
+    const int WIN_ROWS = row_bytes <= WIN_MAX ? (int)(WIN_MAX / (uint32_t)row_bytes) : 1;
+    // (the wave index is uniform, but not to the compiler: without readfirstlane every store is a waterfall loop)
+    const int wave_u = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane(wave_in_wg);
+    const char* const row0 = (const char*)(tiles + (NW == 1 ? (size_t)blockIdx.x * TPW : (size_t)blockIdx.x * D + (size_t)wave_u * 4) * TILE_DOUBLES);
     const int bvoff = st ? (int)((tc.g * TILE_DOUBLES + r * 4 + c) * sizeof(double)) : (int)0x80000000;
-    auto store_row = [&](double v) {
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)row, 0, TPW * TILE_DOUBLES * 8, 0x00020000);
+    __amdgpu_buffer_rsrc_t rsrc;
+    uint32_t soff = 0;
+    // opens the window that starts at time row n0 and returns the row behind it (at most a.N: row N is stored on its own)
+    auto open_window = [&](int n0) {
+        const int n1 = a.N - n0 < WIN_ROWS ? a.N : n0 + WIN_ROWS;
+        rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(row0 + (size_t)n0 * row_bytes), 0,
+                                                 (int)((uint32_t)(n1 - n0 - 1) * (uint32_t)row_bytes + SLICE), 0x00020000);
+        soff = 0;
+        return n1;
+    };
+    auto store_last_row = [&](double v) {               // time N, through a window of its own
+        const __amdgpu_buffer_rsrc_t last = __builtin_amdgcn_make_buffer_rsrc((void*)(row0 + (size_t)a.N * row_bytes), 0, (int)SLICE, 0x00020000);
         u32x2 bits;
         __builtin_memcpy(&bits, &v, 8);
-        __builtin_amdgcn_raw_buffer_store_b64(bits, rsrc, bvoff, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(bits, last, bvoff, 0, 0);
     };
     // The state of time n goes out one step LATE, behind the first MFMA of step n + 1: a store issued right behind the
     // instruction that produced its data holds the wave's (in-order) issue until that result can be read by the memory
     // path -- 22 cycles on a bare add-MFMA-MFMA chain against 8 when the value is a step old
     // (profiles/r02_probe13_store_cost.log); on the headline kernel 0.483 -> 0.432 ms.  The empty asm makes the stored
     // value "depend" on that MFMA, so the scheduler keeps the store behind it; no instruction or wait state is emitted
-    // (a macro, not a lambda: with a by-value copy of M hipcc's schedule of the headline step loses the whole gain).
-#define RK_STORE_BEHIND(M_, mfma_result)                              \
-    do {                                                              \
-        asm("" : "+v"(M_) : "v"(mfma_result));                        \
-        store_row(M_);                                                \
-        row += tstride_all * sizeof(double);                          \
+    // (a macro, not a lambda over M: with a by-value copy of M hipcc's schedule of the headline step loses the whole gain).
+    // The store goes to row soff / row_bytes of the open window and moves soff on by one row.  The second asm hands
+    // the MFMA's result on to its readers and clobbers memory: the store stays in front of them, in its own step
+    // (in an unrolled loop hipcc otherwise collects the stores of several steps behind the last one's first MFMA).
+#define RK_STORE_BEHIND(M_, mfma_result)                                               \
+    do {                                                                               \
+        asm("" : "+v"(M_) : "v"(mfma_result));                                         \
+        u32x2 bits_;                                                                   \
+        __builtin_memcpy(&bits_, &M_, 8);                                              \
+        __builtin_amdgcn_raw_buffer_store_b64(bits_, rsrc, bvoff, (int)soff, 0);       \
+        soff += (uint32_t)row_bytes;                                                   \
+        asm volatile("" : "+v"(mfma_result) : : "memory");                             \
     } while (0)
 
     if constexpr (rhs_has_tile_form<RHS>::value && D == 2 && ITG != RK_INTERROGATE_CHKREBTII) {
@@ -151,7 +178,9 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
         // wait states, and the stream no longer changes with unrelated edits (sched_barriers cost 12-24 cycles per
         // step; of 220 random valid orders in profiles/r01_probe9_fwd_order_search.log this one was the fastest).
 #define RK_AFTER(in, res) asm("" : "+v"(in) : "v"(res))
-        for (int n = 0; n < a.N; ++n) {
+        // One step, written once: the time loop below runs it four times per iteration (the loop's counter, compare and
+        // taken branch -- behind which this SIMD's only wave refetches -- once per four steps) and a tail of up to three.
+        auto step = [&]() __attribute__((always_inline)) {
             double U = MF(M, Qt, 0.0);                              // (Q~ M)^T                         (standard.py:57-59)
             RK_STORE_BEHIND(M, U);                                  // the state of time n
             double B0 = MF(Y0, M, 0.0);                             // row 0 of Q~ M in every row: mu-_0 in column 3
@@ -177,13 +206,20 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
             const double e = fma(-S, y0, 1.0);
             const double y = fma(y0, fma(e, e, e), y0);             // 1 / S (linalg_small.hpp, fast_rcp_cubic)
             M = fma(-PW, y, Mp);                                    // [Sigma- - K (W~ Sigma-) | mu- - K yhat]  (standard.py:98-102)
+        };
+        for (int n0 = 0; n0 < a.N;) {
+            const int n1 = open_window(n0);
+            const uint32_t soff_quads = (uint32_t)((n1 - n0) & ~3) * (uint32_t)row_bytes;   // soff counts the loop
+            while (soff != soff_quads) { step(); step(); step(); step(); }
+            for (int i = (n1 - n0) & 3; i > 0; --i) step();
+            n0 = n1;
         }
-        store_row(M);                                               // time N
+        store_last_row(M);
 #undef RK_AFTER
 #ifdef RK_PLACEMENT_DEBUG
         // experiment build only (scripts/placement_probe.py): where this wave ran, into its slice of the scratch tail
         if (lane == 0) {
-            double* tail = tiles + (size_t)(a.N + 1) * tstride_all + (size_t)blockIdx.x * 64;
+            double* tail = tiles + (size_t)(a.N + 1) * n_tiles * TILE_DOUBLES + (size_t)blockIdx.x * 64;
             tail[0] = (double)__builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_REG_HW_ID
             tail[1] = (double)__builtin_amdgcn_s_getreg((31 << 11) | 20);       // HW_REG_XCC_ID
         }
@@ -211,7 +247,8 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
         RHS::tile_consts(blk, th, tk);
         const double ac3 = -tk[1], ac1 = -tk[0], aco = -tk[2], ac0 = -tk[3];      // a = -f as the cubic of the generic path's row 3
         const double e3c = c == 3 ? 1.0 : 0.0;
-        for (int n = 0; n < a.N; ++n) {
+        for (int n = 0, n1 = 0; n < a.N; ++n) {
+            if (n == n1) n1 = open_window(n);
             // z_0 of this step first: its LDS latency hides behind the MFMAs
 #if defined(RK_T3_ABLATE) && RK_T3_ABLATE >= 1            // experiment builds (scripts/c4_ablation.sh): no generator
             const double zn = 0.25;
@@ -223,7 +260,7 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
             }
             const double zn = zbuf[tc.g * 16 + (n & 15)];
 #endif
-            const double U = MF(M, Qt, 0.0);
+            double U = MF(M, Qt, 0.0);
             RK_STORE_BEHIND(M, U);
             const double Mp = MF(U, Qt, Rt);
             const double MpT = MF(Qt0, U, RtT);
@@ -247,7 +284,7 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
             const double PW = Z0 * WS;
             M = fma(-PW, rS, Mp);                           // standard.py:98-102
         }
-        store_row(M);
+        store_last_row(M);
         return;
     }
     double l0 = 0.0, l1 = 0.0, l2 = 0.0, l3 = 0.0, l4 = 0.0, XwL = 0.0;
@@ -258,11 +295,12 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
         l0 = jac ? 0.0 : -kk[0]; l1 = -kk[1]; l2 = -kk[2]; l3 = -kk[3]; l4 = -kk[4];          // a = -f + J0 own
         XwL = fma(jac ? -kk[0] : 0.0, E0, Wr);                                                  // W~ = W - J: constant rows
     }
-    for (int n = 0; n < a.N; ++n) {
+    for (int n = 0, n1 = 0; n < a.N; ++n) {
+        if (n == n1) n1 = open_window(n);
         // ---- predict (standard.py:57-59): U = (Q~ M)^T, M- = Q~ M Q~^T + R~; B0 = row 0 of Q~ M in every row ----
         // (a 4x4x4 fp64 MFMA blocks this wave's issue for ~17 cycles = 4 fp64 VALU ops, and nothing overlaps it --
         //  profiles/r01_probe3_mfma_valu_serialize.log -- so the step is written with the fewest MFMAs: seven)
-        const double U = MF(M, Qt, 0.0);
+        double U = MF(M, Qt, 0.0);
         RK_STORE_BEHIND(M, U);
         double v_own;                                  // the point the ODE is evaluated at: X[b][0] of this tile's block
         if constexpr (ITG != RK_INTERROGATE_CHKREBTII) v_own = quad_bcast3(MF(Y0, M, 0.0));   // mu-_0 in all 16 lanes
@@ -345,7 +383,7 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
         const double K = Z0 * fast_rcp_cubic(S);
         M = fma(-K, WS, Mp);
     }
-    store_row(M);
+    store_last_row(M);
 #undef RK_STORE_BEHIND
 }
 
