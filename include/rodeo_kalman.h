@@ -275,6 +275,33 @@ int rk_dalton_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in
 int rk_dalton_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
                     const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
                     int32_t n_obs, int32_t n_bobs);
+/* DALTON for non-Gaussian observations (src/rodeo/inference/dalton.py:547-1039, kalman_type = standard, n_bmeas = 1,
+ * n_bstate 2..6 (2..5 with three or more blocks), interrogate rodeo / schober / kramer, any built-in or user right-hand side
+ * with n_bmeas = 1).  The observation log-likelihood is HIP source, like a user right-hand side:
+ * rk_register_obs_source: `source` defines, inside namespace rk, a struct `type_name` with constants D, P, NY, NTHETA, MO,
+ * NACT[D], ACT[D][3] (the state components of each block that the log-likelihood reads, at most n_active = MO <= 3 per
+ * block) and `template <class T> static T loglik(const double (&y)[D][NY], const T (&X)[D][P], double ind, const double
+ * (&th)[NTHETA])` (rodeo_amd.trace.trace_obs_source writes it from a Python function); returns obs_id.  n_theta is the
+ * solver's cfg.n_theta: the log-likelihood reads the same packed parameters as the right-hand side.  Every call registers a
+ * new model, kept with its compiled kernels for the life of the process (nothing is pruned or compared): register a source
+ * once and reuse its obs_id (the Python wrapper keys its models by a hash of the source).
+ * Observations: obs (n_obs, n_block, n_ycols) and obs_ind (n_obs) on the device, grid indices strictly increasing and at
+ * most n_steps; an observation at grid index 0 enters the log-likelihood term only.
+ * rk_daltonng_loglik: logy_x + logx_z - logx_yhat per trajectory into logdens (B); needs a device workspace of
+ * rk_daltonng_workspace_bytes (two filters' moments, the gain records, the smoothed means at the observations); a point
+ * where the log-likelihood is not concave in a block's active components yields NaN, not an error.
+ * rk_daltonng_solve: the joint filter (RK_MODE_FILTER) + the smoothing pass of rk_solve_mv (RK_MODE_MV) into `out` in the
+ * batch-minor layout (refused unless rk_solve_layout reports it: set RK_FLAG_BATCH_MINOR).                               */
+int rk_register_obs_source(const char* type_name, const char* source, int32_t n_block, int32_t n_bstate, int32_t n_ycols,
+                           int32_t n_theta, int32_t n_active, int32_t* obs_id);
+/* compiles the three kernels around obs_id (both forward forms for this right-hand side and interrogation, and the
+ * observation kernel) without loading them (needs no GPU); compiler errors via rk_last_error() */
+int rk_obs_compile_check(int32_t obs_id, int32_t rhs_id, int32_t interrogate);
+int rk_daltonng_workspace_bytes(const rk_solve_cfg* cfg, int32_t n_obs, size_t* bytes);
+int rk_daltonng_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, int32_t obs_id, const double* obs,
+                       const int32_t* obs_ind, int32_t n_obs, void* workspace, size_t workspace_bytes, double* logdens);
+int rk_daltonng_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                      int32_t obs_id, const double* obs, const int32_t* obs_ind, int32_t n_obs);
 /* The same on the records of the blocked-tile forward pass (kalman_type standard, n_bstate 4 .. 8, rk_solve_filter WITHOUT
  * RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR: out->var_state = the records): predicted moments are re-evaluated, nothing but the
  * filtered records is read; the result goes to mean_out (N+1, d, p, B) and var_out (N+1, d, p, p, B), batch-minor.

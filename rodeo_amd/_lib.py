@@ -112,6 +112,11 @@ SIGNATURES = {
     "rk_dalton_layout": (C.c_int, [_P, _I, _I, C.POINTER(C.c_int32)]),
     "rk_dalton_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "rk_dalton_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I]),
+    "rk_register_obs_source": (C.c_int, [C.c_char_p, C.c_char_p, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "rk_obs_compile_check": (C.c_int, [_I, _I, _I]),
+    "rk_daltonng_workspace_bytes": (C.c_int, [_P, _I, C.POINTER(C.c_size_t)]),
+    "rk_daltonng_loglik": (C.c_int, [_H, _P, _P, _I, _P, _P, _I, _P, C.c_size_t, _P]),
+    "rk_daltonng_solve": (C.c_int, [_H, _P, _P, _P, _I, _I, _P, _P, _I]),
     "rk_magi_logdens": (C.c_int, [_H, C.POINTER(MagiCfg), C.POINTER(MagiIn), _P]),
     "rk_fd_stencil": (C.c_int, [_H, _I, _I, _P, _P, _P]),
     "rk_fd_grad_hess": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P]),

@@ -21,6 +21,7 @@
 #include "solve_args.hpp"
 #include "solve_dense_itg_kernels.hpp"
 #include "solve_paths.hpp"
+#include "daltonng_kernels.hpp"
 #include "build/embedded_sources.inc"
 
 namespace rk {
@@ -92,6 +93,9 @@ static std::string kernel_expr(const UserRhs& u, int P, int itg, JitKind kind) {
     return buf;
 }
 
+static int jit_compile_src(const std::string& src, const std::string& expr, const std::string& what, std::vector<char>& code,
+                           std::string& lowered, const char* role = "user right-hand side");
+
 // compile one instantiation; returns code object in `code` and the mangled name in `lowered`
 static int jit_compile(const UserRhs& u, int P, int itg, JitKind kind, std::vector<char>& code, std::string& lowered) {
     const std::string src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n"
@@ -102,13 +106,18 @@ static int jit_compile(const UserRhs& u, int P, int itg, JitKind kind, std::vect
                             (kind == JIT_DALTON || kind == JIT_DALTON_STORE ? "#include \"dalton_kernels.hpp\"\n" : "") +
                             (kind == JIT_DALTON_TILE3 || kind == JIT_DALTON_TILE3_STORE ? "#include \"dalton_tile3_kernels.hpp\"\n" : "") +
                             "namespace rk {\n" + u.source + "\nusing UserRhsT = " + u.type_name + ";\n}  // namespace rk\n";
+    return jit_compile_src(src, kernel_expr(u, P, itg, kind), u.type_name, code, lowered);
+}
+
+// one hiprtc build of `src` for the kernel named by `expr`; `role` and `what` name the user's code in the error message
+static int jit_compile_src(const std::string& src, const std::string& expr, const std::string& what, std::vector<char>& code,
+                           std::string& lowered, const char* role) {
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "rk_user_rhs.hip", kJitNumHeaders, kJitHeaderSources, kJitHeaderNames) !=
         HIPRTC_SUCCESS) {
         set_error("hiprtcCreateProgram failed");
         return RK_ERR_HIP;
     }
-    const std::string expr = kernel_expr(u, P, itg, kind);
     hiprtcAddNameExpression(prog, expr.c_str());
     // (Makefile: why aligned loops; MFMA results in VGPRs like the ahead-of-time build -- without it every MFMA result of the
     // tile kernels goes through an AGPR and two v_accvgpr_read, 12 extra instructions per step of the p = 3 forward kernel:
@@ -124,7 +133,7 @@ static int jit_compile(const UserRhs& u, int P, int itg, JitKind kind, std::vect
         std::string log(ls, '\0');
         if (ls) hiprtcGetProgramLog(prog, &log[0]);
         if (log.size() > 800) log.resize(800);
-        set_error("hiprtc could not compile the user right-hand side '%s': %s", u.type_name.c_str(), log.c_str());
+        set_error("hiprtc could not compile the %s '%s': %s", role, what.c_str(), log.c_str());
         hiprtcDestroyProgram(&prog);
         return RK_ERR_INVALID;
     }
@@ -338,6 +347,142 @@ int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, dou
     return RK_OK;
 }
 
+// ---- DALTON for non-Gaussian observations (daltonng_kernels.hpp): the observation log-likelihood is always user code
+// (rodeo_amd.trace.trace_obs_source), so its forward filter is a hiprtc build around EITHER kind of right-hand side -- a
+// built-in one is named through the embedded rhs.hpp.
+struct UserObs {
+    std::string type_name, source;
+    int n_block, n_bstate, n_ycols, n_theta, n_active;
+};
+static std::vector<UserObs> g_obs;                                   // id = index
+static std::map<std::tuple<int, int, int, int, int>, JitCode> g_ng_code;        // (rhs, obs, P, itg, kind)
+static std::map<std::tuple<int, int, int, int, int, int>, JitEntry> g_ng_cache;  // (device, rhs, obs, P, itg, kind)
+
+static const char* builtin_rhs_type(int rhs_id) {
+    switch (rhs_id) {
+        case RK_RHS_FITZHUGH_NAGUMO: return "FitzHughNagumo";
+        case RK_RHS_LORENZ63: return "Lorenz63";
+        case RK_RHS_HIGHER_ORDER: return "HigherOrder";
+    }
+    return nullptr;
+}
+
+int ng_obs_info(int obs_id, NgObsInfo* info) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    RK_REQUIRE(obs_id >= 0 && obs_id < (int)g_obs.size(), RK_ERR_INVALID, "unknown obs_id %d", obs_id);
+    const UserObs& u = g_obs[obs_id];
+    info->n_block = u.n_block; info->n_bstate = u.n_bstate; info->n_ycols = u.n_ycols; info->n_theta = u.n_theta;
+    info->n_active = u.n_active;
+    return RK_OK;
+}
+
+// the code object of one kernel around observation model obs_id (compiled once, failures remembered).  The source is put
+// together under the registry's lock and hiprtc runs outside it (as in rk_rhs_compile_check: a build takes seconds and must
+// not hold up registrations or other handles); two threads that miss at once both compile and the first result is kept.
+static int ng_code(int rhs_id, int obs_id, int P, int itg, JitKind kind, const JitCode** out) {
+    const auto ckey = std::make_tuple(rhs_id, obs_id, P, itg, (int)kind);
+    std::string src, name;
+    char expr[512];
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        RK_REQUIRE(obs_id >= 0 && obs_id < (int)g_obs.size(), RK_ERR_INVALID, "unknown obs_id %d", obs_id);
+        auto ci = g_ng_code.find(ckey);
+        if (ci != g_ng_code.end()) { *out = &ci->second; return RK_OK; }
+        const UserObs& ob = g_obs[obs_id];
+        src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n") +
+              (is_user_rhs(rhs_id) ? "" : "#include \"rhs.hpp\"\n") +        // (a user's names stay free)
+              "#include \"daltonng_kernels.hpp\"\nnamespace rk {\n";
+        if (kind == JIT_DALTONNG_OBS) {
+            snprintf(expr, sizeof expr, "rk::daltonng_obs_kernel<rk::UserObsT>");
+        } else {
+            if (is_user_rhs(rhs_id)) {
+                const int idx = rhs_id - RK_RHS_USER_BASE;
+                RK_REQUIRE(idx >= 0 && idx < (int)g_rhs.size(), RK_ERR_INVALID, "unknown user rhs_id %d", rhs_id);
+                src += g_rhs[idx].source + "\nusing UserRhsT = " + g_rhs[idx].type_name + ";\n";
+            } else {
+                const char* t = builtin_rhs_type(rhs_id);
+                RK_REQUIRE(t, RK_ERR_UNSUPPORTED, "daltonng: rhs %d has no lane-per-trajectory form", rhs_id);
+                src += std::string("using UserRhsT = ") + t + ";\n";
+            }
+            snprintf(expr, sizeof expr, "rk::daltonng_fwd_kernel<rk::UserRhsT, rk::UserObsT, %d, %d, %d, %s>", P, itg,
+                     ob.n_active, kind == JIT_DALTONNG_BOTH ? "true" : "false");
+        }
+        src += ob.source + "\nusing UserObsT = " + ob.type_name + ";\n}  // namespace rk\n";
+        name = ob.type_name;
+    }
+    JitCode c;
+    c.rc = jit_compile_src(src, expr, name, c.code, c.lowered, "observation log-likelihood");
+    if (c.rc) c.error = rk_last_error();
+    std::lock_guard<std::mutex> lk(g_mu);
+    *out = &g_ng_code.emplace(ckey, std::move(c)).first->second;      // (map nodes do not move: the pointer stays valid)
+    return RK_OK;
+}
+
+static int ng_jit_get(rk_handle h, int rhs_id, int obs_id, int P, int itg, JitKind kind, hipFunction_t* fn) {
+    if (kind == JIT_DALTONNG_OBS) rhs_id = 0;                         // (the observation kernel has no right-hand side)
+    const auto key = std::make_tuple(h->device, rhs_id, obs_id, P, itg, (int)kind);
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = g_ng_cache.find(key);
+        if (it != g_ng_cache.end()) { *fn = it->second.fn; return RK_OK; }
+    }
+    const JitCode* cp = nullptr;
+    const int rc = ng_code(rhs_id, obs_id, P, itg, kind, &cp);
+    if (rc) return rc;
+    const JitCode& c = *cp;
+    if (c.rc) { set_error("%s", c.error.c_str()); return c.rc; }
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_ng_cache.find(key);
+    if (it == g_ng_cache.end()) {
+        JitEntry e;
+        RK_HIP(hipModuleLoadData(&e.mod, c.code.data()));
+        RK_HIP(hipModuleGetFunction(&e.fn, e.mod, c.lowered.c_str()));
+        if (getenv("RK_JIT_VERBOSE")) {
+            int regs = 0, scratch = 0;
+            (void)hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, e.fn);
+            (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, e.fn);
+            fprintf(stderr, "[rk] jit kernel %s: %d registers, %d B scratch per lane\n", c.lowered.c_str(), regs, scratch);
+        }
+        it = g_ng_cache.emplace(key, e).first;
+    }
+    *fn = it->second.fn;
+    return RK_OK;
+}
+
+// the forward filter(s): joint moments into a.mean / a.var, with `both` the Z filter's into zm / zv
+int ng_forward(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, bool both, double* zm,
+               double* zv) {
+    if (is_user_rhs(c->rhs_id)) {
+        const int rc = user_rhs_check(c);
+        if (rc) return rc;
+    }
+    hipFunction_t fn;
+    const int rc = ng_jit_get(h, c->rhs_id, obs_id, c->n_bstate, c->interrogate, both ? JIT_DALTONNG_BOTH : JIT_DALTONNG, &fn);
+    if (rc) return rc;
+    SolveArgs args = a;
+    NgObs obs = o;
+    void* params[] = {&args, &obs, &zm, &zv};
+    LaunchTimer t(h, both ? "daltonng_fwd_kernel<both>" : "daltonng_fwd_kernel<store>");
+    RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, both ? 32 : 64), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
+    t.stop();
+    return RK_OK;
+}
+
+// logy_x on the smoothed means and the final sum into out (B)
+int ng_obs_eval(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, const double* sm,
+                const double* part, double* out) {
+    hipFunction_t fn;
+    const int rc = ng_jit_get(h, 0, obs_id, c->n_bstate, 0, JIT_DALTONNG_OBS, &fn);
+    if (rc) return rc;
+    int B = a.B, n_obs = o.n_obs, theta_b = a.theta_b;
+    const double *y = o.y, *theta = a.theta;
+    void* params[] = {&B, &n_obs, &y, &sm, &theta, &theta_b, &part, &out};
+    LaunchTimer t(h, "daltonng_obs_kernel");
+    RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, 64), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
+    t.stop();
+    return RK_OK;
+}
+
 }  // namespace rk
 
 using namespace rk;
@@ -358,6 +503,34 @@ int rk_register_rhs_source_m(const char* type_name, const char* source, int32_t 
 
 int rk_register_rhs_source(const char* type_name, const char* source, int32_t n_block, int32_t n_theta, int32_t* rhs_id) {
     return rk_register_rhs_source_m(type_name, source, n_block, 1, n_theta, rhs_id);
+}
+
+int rk_register_obs_source(const char* type_name, const char* source, int32_t n_block, int32_t n_bstate, int32_t n_ycols,
+                           int32_t n_theta, int32_t n_active, int32_t* obs_id) {
+    RK_REQUIRE(type_name && source && obs_id, RK_ERR_INVALID, "rk_register_obs_source: null argument");
+    RK_REQUIRE(n_block >= 1 && n_block <= 64 && n_bstate >= 2 && n_bstate <= 6 && n_ycols >= 1 && n_ycols <= 4 && n_theta >= 0 &&
+               n_active >= 1 && n_active <= 3, RK_ERR_INVALID,
+               "rk_register_obs_source: bad n_block / n_bstate (2..6) / n_ycols (1..4) / n_theta / n_active (1..3)");
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_obs.push_back(UserObs{type_name, source, n_block, n_bstate, n_ycols, n_theta, n_active});
+    *obs_id = (int)g_obs.size() - 1;
+    return RK_OK;
+}
+
+int rk_obs_compile_check(int32_t obs_id, int32_t rhs_id, int32_t interrogate) {
+    NgObsInfo info;
+    int rc0 = ng_obs_info(obs_id, &info);
+    if (rc0) return rc0;
+    const int P = info.n_bstate;
+    const JitKind kinds[] = {JIT_DALTONNG_BOTH, JIT_DALTONNG, JIT_DALTONNG_OBS};
+    for (JitKind k : kinds) {
+        const JitCode* c = nullptr;
+        const bool tail = k == JIT_DALTONNG_OBS;
+        const int rc = ng_code(tail ? 0 : rhs_id, obs_id, P, tail ? 0 : interrogate, k, &c);
+        if (rc) return rc;
+        if (c->rc) { set_error("%s", c->error.c_str()); return c->rc; }
+    }
+    return RK_OK;
 }
 
 int rk_rhs_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {

@@ -46,6 +46,9 @@ enum JitKind : int {
     JIT_DALTON_STORE = 12,    // dalton_fwd_kernel<.., true>  (joint filter's moments; same P key)
     JIT_DALTON_TILE3 = 13,    // dalton_fwd_tile3_kernel<.., false> (log-likelihood on the p = 3 tiles)
     JIT_DALTON_TILE3_STORE = 14,  // dalton_fwd_tile3_kernel<.., true> (RK_LAYOUT_TILE3 records)
+    JIT_DALTONNG = 15,        // daltonng_fwd_kernel<.., false> (joint filter's moments; cached per (rhs, obs model))
+    JIT_DALTONNG_BOTH = 16,   // daltonng_fwd_kernel<.., true>  (joint filter and the filter on Z alone)
+    JIT_DALTONNG_OBS = 17,    // daltonng_obs_kernel (logy_x and the final sum; no right-hand side)
 };
 bool is_user_rhs(int rhs_id);
 bool user_tile_available(const rk_solve_cfg* c, JitKind tile);
@@ -57,6 +60,14 @@ int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Da
                 bool tile, double* out);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
+// observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them
+struct NgObs;
+struct NgObsInfo { int n_block, n_bstate, n_ycols, n_theta, n_active; };
+int ng_obs_info(int obs_id, NgObsInfo* info);
+int ng_forward(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, bool both, double* zm,
+               double* zv);
+int ng_obs_eval(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, const double* sm,
+                const double* part, double* out);
 bool user_dense_wanted(const rk_solve_cfg* c);
 int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a);
 

@@ -6,8 +6,9 @@ kernels of src/rodeo/inference/pseudo_marginal.py for many chains in lock-step (
 ``fenrir``: the Fenrir likelihood (src/rodeo/inference/fenrir.py:261-327, "next-4").  ``dalton``: the DALTON likelihood
 for Gaussian observations and its data-adaptive solver (src/rodeo/inference/dalton.py:39-545; ``rodeo_amd.inference.dalton``
 holds ``solve_mv`` / ``solve_sim``).  ``magi_logdens``: the MAGI log-density (src/rodeo/inference/magi.py:6-99;
-``rodeo_amd.inference.magi`` is its module).  ``daltonng`` (non-Gaussian observations: derivatives of a user
-log-likelihood) is out of scope.  ``laplace``: mode, Hessian and normal approximation of a batched log-posterior by central
+``rodeo_amd.inference.magi`` is its module).  ``daltonng`` and ``solve_mv_nn`` (non-Gaussian observations, dalton.py:547-1039) live in
+``rodeo_amd.inference.dalton`` and are imported from there (``from rodeo_amd.inference.dalton import daltonng``); they are not
+re-exported here.  ``laplace``: mode, Hessian and normal approximation of a batched log-posterior by central
 differences on the device (docs/examples/parameter.md:239-275; ``rodeo_amd.inference.laplace`` is the module, its function
 is ``laplace.laplace``).
 """

@@ -24,6 +24,7 @@ built.  Divergences from the reference:
     forecast variance lies within utils.py:60-78's 1e-8 threshold.
 """
 import ctypes as C
+import hashlib
 import os
 import numpy as np
 from .. import _lib
@@ -123,6 +124,149 @@ def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrog
     with a leading batch axis for batched inputs."""
     plan = _solve(_lib.MODE_MV, key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
                   obs_data, obs_times, obs_weight, obs_var, kalman_type, params)
+    return plan.state_host()
+
+
+# --- non-Gaussian observations (src/rodeo/inference/dalton.py:547-1039) -------------------------------------------------
+#
+# ``daltonng`` and ``solve_mv_nn`` take an ordinary Python ``obs_loglik_i(obs_data_i, ode_data_i, ind, **params)`` written with
+# NumPy (``rodeo_amd.trace.gammaln`` for log-factorials); it is traced once into scalar-generic device code
+# (``trace.trace_obs_source``), differentiated twice by forward-mode duals (csrc/dual2.hpp) inside the forward filter and
+# evaluated on plain doubles for logy_x.  What is built where the reference's text cannot be taken literally, and the other
+# divergences, are listed in DESIGN.md section 7 (the selector of a block's active components as the weight; the block index
+# where the reference has the observation index; NaN at a non-concave point; strictly increasing grid indices; no observation
+# beyond t_max).  Neither name is re-exported from ``rodeo_amd.inference``: import them from this module.
+#
+# The function is run once per call, on symbols (plain Python, no device work; a function with side effects shows them once
+# a call), and the traced models are kept by the hash of the generated source: a lambda or closure built anew per call finds
+# its compiled kernels again, and nothing is registered twice.  Python values the function closes over (or reads from globals) are constants of the generated code -- a changed value
+# is a different source, hence another model and another hiprtc build; what should vary between calls without a rebuild goes
+# through ``**params``.
+
+_obs_models = {}
+_NG_PLACEHOLDER = "TracedObs_0000000000"                            # the struct's name until the source's hash is known
+
+
+def _ng_param_spec(ode_fun, params):
+    """How **params are packed: the right-hand side's own rule (the log-likelihood reads the same vector)."""
+    spec = getattr(ode_fun, "param_spec", None)
+    if spec is None:                                                # a Python right-hand side: SolvePlan's rule
+        spec = tuple((k, int(np.shape(v)[-1]) if np.ndim(v) >= 1 else 1) for k, v in params.items())
+    return tuple(spec)
+
+
+def _ng_refusals(ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_times, obs_loglik_i, t_min, t_max, n_steps,
+                 params):
+    """Everything this build does not serve, raised before any device work; returns (obs, obs_ind, traced model)."""
+    from ..trace import trace_obs_source
+    if kalman_type == "square-root":
+        raise NotImplementedError("daltonng: the square-root form is not built on the device (kalman_type='standard' only)")
+    if kalman_type != "standard":
+        raise NotImplementedError                                   # dalton.py:884-889
+    itg, _ = _interrogate_id(interrogate)
+    if itg == _lib.INTERROGATE_CHKREBTII:
+        raise NotImplementedError("daltonng: interrogate_chkrebtii is not supported (rodeo, schober, kramer)")
+    W = np.shape(ode_weight)
+    if len(W) not in (3, 4):
+        raise ValueError("ode_weight must have shape (n_block, n_bmeas, n_bstate) [+ a leading batch axis]")
+    if W[-2] != 1:
+        raise NotImplementedError("daltonng on the device: n_bmeas = 1 only")
+    if not 2 <= W[-1] <= 6:
+        raise NotImplementedError("daltonng on the device: n_bstate in 2..6")
+    d, p = int(W[-3]), int(W[-1])
+    if d >= 3 and p > 5:                                            # (daltonng.hip ng_check: the lane kernel spills)
+        raise NotImplementedError("daltonng on the device: n_bstate up to 5 with three or more blocks")
+    rid = getattr(ode_fun, "rhs_id", None)
+    if rid is not None and rid < _lib.RHS_USER_BASE:                # a built-in right-hand side: the hiprtc unit has to name it
+        if rid not in (_lib.RHS_FITZHUGH_NAGUMO, _lib.RHS_LORENZ63, _lib.RHS_HIGHER_ORDER):
+            raise NotImplementedError(f"daltonng on the device: the built-in right-hand side {getattr(ode_fun, 'name', rid)!r} "
+                                      "has no lane-per-trajectory form (fitzhugh_nagumo, lorenz63, higher_order, or a "
+                                      "Python / from_source right-hand side)")
+        if getattr(ode_fun, "n_block", d) != d:
+            raise NotImplementedError(f"daltonng on the device: the right-hand side {ode_fun.name!r} has {ode_fun.n_block} "
+                                      f"blocks, ode_weight has {d}")
+    obs = np.ascontiguousarray(obs_data, dtype=np.float64)
+    if obs.ndim != 3 or obs.shape[1] != d:
+        raise ValueError(f"obs_data must have shape (n_obs, {d}, n_ycols), got {obs.shape}")
+    if not callable(obs_loglik_i):
+        raise TypeError("obs_loglik_i must be a Python function obs_loglik_i(obs_data_i, ode_data_i, ind, **params)")
+    times = np.asarray(obs_times, dtype=np.float64)
+    if times.shape != (obs.shape[0],):
+        raise ValueError(f"obs_times must have shape ({obs.shape[0]},), got {times.shape}")
+    if np.any(times > float(t_max)):
+        raise ValueError("daltonng: an observation time lies beyond t_max")
+    ind = obs_index(t_min, t_max, n_steps, times)
+    if np.any(np.diff(ind) <= 0):
+        raise ValueError("daltonng: the observations' grid indices must be strictly increasing (one observation per grid "
+                         "point, in time order)")
+    spec = _ng_param_spec(ode_fun, params)
+    probe, active = trace_obs_source(obs_loglik_i, d, p, obs.shape[2], spec, _NG_PLACEHOLDER)       # the one run on symbols
+    key = hashlib.sha1(repr((probe, d, p, obs.shape[2], spec)).encode()).hexdigest()
+    if key not in _obs_models:
+        struct = "TracedObs_" + key[:10]
+        _obs_models[key] = dict(source=probe.replace(_NG_PLACEHOLDER, struct), struct=struct, active=active,
+                                n_theta=sum(s for _, s in spec), obs_id=None)
+    return obs, ind, _obs_models[key]
+
+
+def _ng_obs_id(model, d, p, n_ycols):
+    """The library's id of a traced observation model (registered once; no device is needed for that)."""
+    if model["obs_id"] is None:
+        oid = C.c_int32(0)
+        _lib.check(_lib.load().rk_register_obs_source(model["struct"].encode(), model["source"].encode(), d, p, n_ycols,
+                                                      model["n_theta"], max(len(a) for a in model["active"]), C.byref(oid)))
+        model["obs_id"] = oid.value
+    return model["obs_id"]
+
+
+def _ng_obs_on_device(plan, obs, ind):
+    """The observations uploaded once per plan and reused while they do not change (a few kilobytes, as in _obs_on_device)."""
+    cache = plan.__dict__.setdefault("_daltonng_obs", {})
+    sig = (obs.tobytes(), ind.tobytes())
+    if cache.get("sig") != sig:
+        cache["sig"] = sig
+        cache["dev"] = (plan.dev.to_device(obs), plan.dev.to_device(np.ascontiguousarray(ind.astype(np.int32))))
+    return cache["dev"]
+
+
+def daltonng(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
+             obs_data, obs_times, obs_loglik_i, kalman_type="standard", **params):
+    """logy_x + logx_z - logx_yhat, the DALTON log-likelihood for non-Gaussian observations (dalton.py:851-949): a float, or
+    an array (B,) for batched inputs.  The workspace (rk_daltonng_workspace_bytes: about 3.8 MB per trajectory at 4000 steps,
+    two blocks, n_bstate = 3) lives for the call only; the plan keeps the uploaded observations and nothing else."""
+    obs, ind, model = _ng_refusals(ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_times, obs_loglik_i, t_min,
+                                   t_max, n_steps, params)
+    plan = cached_plan(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type,
+                       batch_minor=True, **params)
+    oid = _ng_obs_id(model, plan.d, plan.p, obs.shape[2])
+    d_obs, d_ind = _ng_obs_on_device(plan, obs, ind)
+    need = C.c_size_t(0)
+    _lib.check(plan.dev.lib.rk_daltonng_workspace_bytes(C.byref(plan.cfg), int(ind.shape[0]), C.byref(need)))
+    ws = plan.dev.empty((need.value // 8,))                         # two stored filters + the gain records: released on return
+    plan.cfg.seed = _seed(key)
+    out = plan.dev.empty((plan.B,))
+    _lib.check(plan.dev.lib.rk_daltonng_loglik(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), oid, d_obs.ptr, d_ind.ptr,
+                                               int(ind.shape[0]), ws.ptr, ws.nbytes, out.ptr))
+    ll = out.to_host()
+    return ll if plan.batched else float(ll[0])
+
+
+def solve_mv_nn(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
+                obs_data, obs_times, obs_loglik_i, kalman_type="standard", **params):
+    """Mean and variance of p(X_{0:N} | Yhat_{0:M}, Z_{1:N}) for non-Gaussian observations (dalton.py:955-1039):
+    ``(mean (N+1, d, p), var (N+1, d, p, p))`` with a leading batch axis for batched inputs."""
+    obs, ind, model = _ng_refusals(ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_times, obs_loglik_i, t_min,
+                                   t_max, n_steps, params)
+    plan = cached_plan(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type,
+                       batch_minor=True, **params)
+    oid = _ng_obs_id(model, plan.d, plan.p, obs.shape[2])
+    d_obs, d_ind = _ng_obs_on_device(plan, obs, ind)
+    plan.generation += 1               # whatever is in the output buffers now belongs to an earlier call
+    plan._prepare_out(_lib.MODE_MV)
+    plan.last_mode = _lib.MODE_MV
+    plan.cfg.seed = _seed(key)
+    _lib.check(plan.dev.lib.rk_daltonng_solve(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out),
+                                              _lib.MODE_MV, oid, d_obs.ptr, d_ind.ptr, int(ind.shape[0])))
     return plan.state_host()
 
 

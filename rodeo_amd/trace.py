@@ -35,10 +35,11 @@ def _lit(v):
 class Sym:
     """A traced scalar: a C++ expression string."""
     __array_priority__ = 1000.0
-    __slots__ = ("code",)
+    __slots__ = ("code", "dep")
 
-    def __init__(self, code):
+    def __init__(self, code, dep=False):
         self.code = code
+        self.dep = dep                                   # does the value depend on the state?  (trace_obs_source marks X)
 
     @staticmethod
     def _c(x):
@@ -49,8 +50,10 @@ class Sym:
         raise TypeError(f"cannot trace an operation with {type(x).__name__}")
 
     def _bin(self, other, op, swap=False):
+        if isinstance(other, np.ndarray):                # symbol (op) array: element by element, like a NumPy scalar
+            return np.frompyfunc(lambda o: self._bin(o, op, swap), 1, 1)(other)
         a, b = (Sym._c(other), self.code) if swap else (self.code, Sym._c(other))
-        return Sym(f"({a} {op} {b})")
+        return Sym(f"({a} {op} {b})", self.dep or getattr(other, "dep", False))
 
     def __add__(self, o): return self._bin(o, "+")
     def __radd__(self, o): return self._bin(o, "+", True)
@@ -60,7 +63,7 @@ class Sym:
     def __rmul__(self, o): return self._bin(o, "*", True)
     def __truediv__(self, o): return self._bin(o, "/")
     def __rtruediv__(self, o): return self._bin(o, "/", True)
-    def __neg__(self): return Sym(f"(-{self.code})")
+    def __neg__(self): return Sym(f"(-{self.code})", self.dep)
     def __pos__(self): return self
 
     def __pow__(self, n):
@@ -95,7 +98,7 @@ class Sym:
 
 def _make_fun(cname):
     def method(self):
-        return Sym(f"{cname}({self.code})")
+        return Sym(f"{cname}({self.code})", self.dep)
     return method
 
 
@@ -164,6 +167,73 @@ struct {struct_name} {{
 }};
 """
     return src, ndep, n_bmeas
+
+
+def gammaln(x):
+    """log Gamma(x) for floats and for traced symbols (device ``lgamma``), e.g. the ``log y!`` of a Poisson log-pmf.  A symbol
+    that depends on the state is refused: the device has no digamma / trigamma to differentiate it with."""
+    if isinstance(x, np.ndarray) and x.dtype == object:
+        return np.frompyfunc(gammaln, 1, 1)(x)
+    if isinstance(x, Sym):
+        if x.dep:
+            raise ValueError("gammaln of a value that depends on the state cannot be differentiated on the device (no "
+                             "digamma / trigamma); only the data, the index and the parameters may enter gammaln")
+        return Sym(f"lgamma({x.code})")
+    import math
+    return np.vectorize(math.lgamma, otypes=[float])(x) if np.ndim(x) else math.lgamma(float(x))
+
+
+MAX_ACTIVE = 3            # largest active set of a block (Dual2<K>, csrc/dual2.hpp)
+
+
+def trace_obs_source(fun, n_block, n_bstate, n_ycols, param_spec, struct_name):
+    """Run the observation log-likelihood ``fun(obs_data_i, ode_data_i, ind, **params)`` (src/rodeo/inference/dalton.py:872) on
+    symbols: ``obs_data_i`` (n_block, n_ycols), ``ode_data_i`` (n_block, n_bstate), ``ind`` a scalar, ``params`` as for a
+    right-hand side.  Returns (source, active): the scalar-generic struct of csrc/daltonng_kernels.hpp and, per block, the
+    tuple of state components that occur.  ``fun`` must return a scalar (ValueError otherwise)."""
+    if not 1 <= n_ycols <= 4:
+        raise ValueError(f"obs_data must have 1 .. 4 columns per block, got {n_ycols}")
+    X = _symbols((n_block, n_bstate), lambda b, j: f"X[{b}][{j}]")
+    for s in X.ravel():
+        s.dep = True
+    y = _symbols((n_block, n_ycols), lambda b, k: f"y[{b}][{k}]")
+    params, off = {}, 0
+    for name, size in param_spec:
+        params[name] = _symbols((size,), lambda k, off=off: f"th[{off + k}]")
+        off += size
+    out = fun(y, X, Sym("ind"), **params)
+    if isinstance(out, np.ndarray) and out.ndim == 0:
+        out = out.item()
+    if np.ndim(out) != 0 or not isinstance(out, (Sym, numbers.Real)):
+        raise ValueError(f"obs_loglik_i must return a scalar, got shape {np.shape(out)}")
+    code = Sym._c(out)
+    active = tuple(tuple(j for j in range(n_bstate) if f"X[{b}][{j}]" in code) for b in range(n_block))
+    if max(len(a) for a in active) > MAX_ACTIVE:
+        raise ValueError(f"obs_loglik_i reads more than {MAX_ACTIVE} state components of one block: {active}")
+    if not any(active):
+        raise ValueError("obs_loglik_i does not depend on the state: there is nothing to condition on")
+    mo = max(len(a) for a in active)
+    nact = ", ".join(str(len(a)) for a in active)
+    act = ", ".join("{%s}" % ", ".join(str(j) for j in (a + (0,) * MAX_ACTIVE)[:MAX_ACTIVE]) for a in active)
+    src = f"""
+// generated by rodeo_amd.trace from the Python function {getattr(fun, '__name__', 'obs_loglik_i')!r}
+struct {struct_name} {{
+    static constexpr int D = {n_block};
+    static constexpr int P = {n_bstate};
+    static constexpr int NY = {n_ycols};
+    static constexpr int NTHETA = {max(off, 1)};
+    static constexpr int MO = {mo};
+    // the state components of each block that the log-likelihood reads (padded with 0)
+    static constexpr int NACT[D] = {{{nact}}};
+    static constexpr int ACT[D][{MAX_ACTIVE}] = {{{act}}};
+    template <class T>
+    __device__ __forceinline__ static T loglik(const double (&y)[D][NY], const T (&X)[D][P], double ind,
+                                               const double (&th)[NTHETA]) {{
+        return {code};
+    }}
+}};
+"""
+    return src, active
 
 
 def _host_twin(fun, n_vars, n_bmeas=1):
