@@ -204,6 +204,30 @@ int rk_solve_mv(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, con
 /* forward + backward sampler: src/rodeo/solve.py:125-205 (solve_sim).  out->x_state <- one draw per traj. */
 int rk_solve_sim(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out);
 
+/* The solver's posterior at arbitrary times (an addition: the reference returns its posterior on the grid only).  `filt`
+ * holds the records of rk_solve_filter and `smooth` those of rk_solve_mv for the SAME cfg / in / seed, both in `layout` =
+ * rk_solve_layout(cfg, RK_MODE_FILTER) = rk_solve_layout(cfg, RK_MODE_MV) (two buffers: rk_solve_mv smooths in place).  Only
+ * var_state (and mean_state in RK_LAYOUT_BATCH_MINOR) of the two are read.  Per query k the device array `query` (T, 3) holds
+ * the node n, an on-node flag and the slot of its prior quadruple: with the flag set the smoothed record n is copied (the
+ * bits of rk_solve_mv); without it the time lies in (t_n, t_{n+1}), n < N, and by the prior's Markov property
+ *     (mu_t, Sigma_t) = predict(filt[n]; Q1, R1),  (mu', Sigma') = predict((mu_t, Sigma_t); Q2, R2)   standard.py:57-59
+ *     G = Sigma_t Q2^T Sigma'^{-1}                                                                     standard.py:175-176
+ *     mu = mu_t + G (mu^s[n+1] - mu'),  Sigma = Sigma_t + G (Sigma^s[n+1] - Sigma') G^T                 standard.py:213-216
+ * with (Q1, R1) / (Q2, R2) the prior over t - t_n / t_{n+1} - t: trans (n_quad, 2, d, p, p [,B]) = (Q1, Q2) and noise
+ * likewise = (R1, R2) per slot, batch-minor where batched.  Indices are clamped to the buffers.  Results in the reference's
+ * layout with the batch axis first: mean_out (B, T, d, p), var_out (B, T, d, p, p).  One lane per (query, trajectory,
+ * block), no time loop.  Served: kalman_type = RK_KALMAN_STANDARD, n_bstate 3..5 (at 6 the lane kernel spills), every
+ * layout but RK_LAYOUT_TRAJ_MAJOR (RK_ERR_UNSUPPORTED otherwise, before the handle is looked at).                       */
+typedef struct {
+    int32_t        n_query;                              /* T                                                    */
+    int32_t        n_quad;                               /* quadruple slots (at least 1, also when none is used)  */
+    const int32_t* query;                                /* (T, 3) on the device: node, on-node flag, slot        */
+    const double*  trans;   int32_t trans_batched;       /* (n_quad, 2, d, p, p [,B]): Q1, Q2                     */
+    const double*  noise;   int32_t noise_batched;       /* (n_quad, 2, d, p, p [,B]): R1, R2                     */
+} rk_eval_at_in;
+int rk_eval_at(rk_handle h, const rk_solve_cfg* cfg, int32_t layout, const rk_solve_out* filt, const rk_solve_out* smooth,
+               const rk_eval_at_in* q, double* mean_out, double* var_out);
+
 /* Gather x[obs_ind[k], :, 0] and reduce the Gaussian observation log-likelihood + N(0, prior_sd^2) log-prior
  * per trajectory: the tail of the user log-posterior of docs/examples/parameter.md:188-210,331-354 (and of
  * src/rodeo/inference/basic.py:47-62 with a Gaussian obs_loglik).

@@ -11,7 +11,7 @@ from . import kalmantv
 from . import ode
 from . import utils
 from . import inference
-from .solve import solve_sim, solve_mv, SolvePlan
+from .solve import solve_sim, solve_mv, solve_mv_at, SolvePlan
 from .prior.ibm import ibm_init
 from .prior.indep_init import indep_init
 from .device import Device, DeviceArray, default_device

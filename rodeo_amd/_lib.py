@@ -64,6 +64,12 @@ class MagiIn(C.Structure):
                 ("prior_var", C.c_void_p), ("prior_var_batched", C.c_int32)]
 
 
+class EvalAtIn(C.Structure):
+    _fields_ = [("n_query", C.c_int32), ("n_quad", C.c_int32), ("query", C.c_void_p),
+                ("trans", C.c_void_p), ("trans_batched", C.c_int32),
+                ("noise", C.c_void_p), ("noise_batched", C.c_int32)]
+
+
 class OpCfg(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_state", C.c_int32), ("n_meas", C.c_int32), ("kalman_type", C.c_int32)]
 
@@ -102,6 +108,7 @@ SIGNATURES = {
     "rk_solve_filter": (C.c_int, [_H, C.POINTER(SolveCfg), C.POINTER(SolveIn), C.POINTER(SolveOut)]),
     "rk_solve_mv": (C.c_int, [_H, C.POINTER(SolveCfg), C.POINTER(SolveIn), C.POINTER(SolveOut)]),
     "rk_solve_sim": (C.c_int, [_H, C.POINTER(SolveCfg), C.POINTER(SolveIn), C.POINTER(SolveOut)]),
+    "rk_eval_at": (C.c_int, [_H, C.POINTER(SolveCfg), _I, C.POINTER(SolveOut), C.POINTER(SolveOut), C.POINTER(EvalAtIn), _P, _P]),
     "rk_gauss_obs_logpost": (C.c_int, [_H, _I, _I, _I, _I, _I, _P, _P, _P, _I, _D, _P, _I, _D, _P]),
     "rk_solve_sim_logpost": (C.c_int, [_H, C.POINTER(SolveCfg), C.POINTER(SolveIn), C.POINTER(SolveOut), _P, _P, _I, _D, _P, _I,
                                        _D, _P]),

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <rccl/rccl.h>
 #include "common.hpp"
+#include "solve_paths.hpp"
 
 namespace rk {
 constexpr size_t RK_PROFILE_KEEP_MAX = 1 << 16;
@@ -231,8 +232,36 @@ int rk_profile_last(rk_handle h, int cap, const char** names, double* ms, int* n
     return RK_OK;
 }
 
+// ---- the posterior at arbitrary times: refusals here, launch in eval_at.hip --------------------------------
+int rk_eval_at(rk_handle h, const rk_solve_cfg* c, int32_t layout, const rk_solve_out* filt, const rk_solve_out* smooth,
+               const rk_eval_at_in* q, double* mean_out, double* var_out) {
+    RK_REQUIRE(c && q, RK_ERR_INVALID, "rk_eval_at: null cfg or query block");
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED,
+               "eval_at: kalman_type %d not built (the standard form only)", c->kalman_type);
+    RK_REQUIRE(layout != RK_LAYOUT_TRAJ_MAJOR, RK_ERR_UNSUPPORTED,
+               "eval_at: the dense path's trajectory-major records are not served");
+    RK_REQUIRE(c->n_bstate >= EVAL_AT_PMIN && c->n_bstate <= EVAL_AT_PMAX, RK_ERR_UNSUPPORTED,
+               "eval_at: n_bstate in %d..%d (2 by padding to 3; beyond, the lane kernel spills), got %d", EVAL_AT_PMIN,
+               EVAL_AT_PMAX, c->n_bstate);
+    const bool fits = layout == RK_LAYOUT_BATCH_MINOR || (layout == RK_LAYOUT_TILE3 && c->n_bstate == 3) ||
+                      (layout == RK_LAYOUT_TILE4 && c->n_bstate == 4) || (layout == RK_LAYOUT_TILEP && c->n_bstate >= 5);
+    RK_REQUIRE(fits, RK_ERR_INVALID, "eval_at: layout %d does not hold n_bstate = %d records", layout, c->n_bstate);
+    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && q->n_query >= 1 && q->n_quad >= 1, RK_ERR_INVALID,
+               "eval_at: n_traj, n_steps, n_block, n_query and n_quad must be at least 1, got %d, %d, %d, %d, %d", c->n_traj,
+               c->n_steps, c->n_block, q->n_query, q->n_quad);
+    const int64_t lanes = (int64_t)c->n_traj * c->n_block;
+    RK_REQUIRE(lanes <= 0x7fffffff && (lanes + 63) / 64 * q->n_query <= 0x7fffffff, RK_ERR_INVALID,
+               "eval_at: n_query * ceil(n_traj * n_block / 64) must fit a grid (%d, %d, %d)", q->n_query, c->n_traj, c->n_block);
+    RK_REQUIRE(h && filt && smooth && mean_out && var_out && q->query && q->trans && q->noise, RK_ERR_INVALID,
+               "rk_eval_at: null handle or array");
+    RK_REQUIRE(filt->var_state && smooth->var_state &&
+                   (layout != RK_LAYOUT_BATCH_MINOR || (filt->mean_state && smooth->mean_state)),
+               RK_ERR_INVALID, "eval_at: the records of both solver calls are needed");
+    return eval_at_launch(h, c, layout, filt, smooth, q, mean_out, var_out);
+}
+
 // ---- RCCL -------------------------------------------------------------------------------------------------
-#define RK_NCCL(call)                                                                         \
+#define RK_NCCL(call)                                                                        \
     do {                                                                                      \
         ncclResult_t r__ = (call);                                                            \
         if (r__ != ncclSuccess) {                                                             \

@@ -96,6 +96,13 @@ int tilen_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
 size_t tilen_tile_doubles(const rk_solve_cfg* c);
 size_t tilen_ws_doubles(const rk_solve_cfg* c, int mode);
 
+// ---- the posterior at arbitrary times (eval_at.hip; rk_eval_at and its refusals are in api.hip) ------------------------
+// n_bstate served by eval_at_kernel: at 6 the lane kernel holds five 6 x 6 matrices through the pivoted LU and spills (4 to 14
+// registers, 20 to 60 B of scratch per lane, with all 512 registers in use)
+constexpr int EVAL_AT_PMIN = 3, EVAL_AT_PMAX = 5;
+int eval_at_launch(rk_handle h, const rk_solve_cfg* c, int layout, const rk_solve_out* filt, const rk_solve_out* smooth,
+                   const rk_eval_at_in* q, double* mean_out, double* var_out);
+
 // ---- the device path of a configuration -----------------------------------------------------------------------------
 enum class SolvePath { Dense, Sqrt, Tile3, Tile4, TileN, Small };
 

@@ -6,7 +6,8 @@ Stochastic block solver for ODE initial value problems on MI355X -- the drop-in 
               kalman_type="standard", **params) -> (mean (N+1, d, p), var (N+1, d, p, p))     solve.py:208-302
     solve_sim(... same ...)                     -> x (N+1, d, p)                              solve.py:125-205
 
-plus ONE extension: ``ode_init``, ``prior_pars`` (either matrix), ``ode_weight`` and every ODE parameter may carry a
+plus ``solve_mv_at`` (an addition, below): the same posterior at arbitrary times instead of on the whole grid;
+and ONE extension: ``ode_init``, ``prior_pars`` (either matrix), ``ode_weight`` and every ODE parameter may carry a
 leading batch axis B of independent trajectories (what a rodeo user writes as ``jax.vmap`` of the solver); outputs
 then have a leading B as well.  The forward scan, the interrogation and the backward scan of ALL trajectories run
 inside fused HIP kernels (rodeo_amd/csrc/solve_small.hip); nothing is computed on the host and there is no CPU
@@ -59,6 +60,21 @@ def _seed(key):
     raise TypeError("key must be None, an int seed, or a 2-word uint32 array")
 
 
+def _device_ode(ode_fun, ode_weight, params):
+    """``ode_fun`` as a ``DeviceODE``: an ordinary Python right-hand side, like the reference's, is traced once into device
+    code (rodeo_amd/trace.py)."""
+    if isinstance(ode_fun, DeviceODE):
+        return ode_fun
+    if not callable(ode_fun):
+        raise TypeError("ode_fun must be a rodeo_amd.ode.DeviceODE or a traceable Python function: the time loop "
+                        "runs on the GPU and needs device code for the right-hand side (see rodeo_amd/ode.py); "
+                        "there is no CPU fallback")
+    from .trace import from_python
+    skip = {"kalman_type"}
+    sizes = {k: int(np.shape(v)[-1]) if np.ndim(v) >= 1 else 1 for k, v in params.items() if k not in skip}
+    return from_python(ode_fun, int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1]), **sizes)
+
+
 class SolvePlan:
     """
     Device-resident form of one solver call: inputs uploaded once in the batch-minor layout, outputs allocated once.
@@ -70,16 +86,7 @@ class SolvePlan:
                  kalman_type="standard", device=None, traj_offset=0, store_pred=False, batch_minor=False, **params):
         if kalman_type not in _KALMAN:
             raise NotImplementedError                    # src/rodeo/solve.py:142-143, 240-241
-        if not isinstance(ode_fun, DeviceODE):
-            if not callable(ode_fun):
-                raise TypeError("ode_fun must be a rodeo_amd.ode.DeviceODE or a traceable Python function: the time loop "
-                                "runs on the GPU and needs device code for the right-hand side (see rodeo_amd/ode.py); "
-                                "there is no CPU fallback")
-            # an ordinary Python right-hand side, like the reference's: traced once into device code (rodeo_amd/trace.py)
-            from .trace import from_python
-            skip = {"kalman_type"}
-            sizes = {k: int(np.shape(v)[-1]) if np.ndim(v) >= 1 else 1 for k, v in params.items() if k not in skip}
-            ode_fun = from_python(ode_fun, int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1]), **sizes)
+        ode_fun = _device_ode(ode_fun, ode_weight, params)
         self.dev = device if device is not None else default_device()
         self._ode_fun = ode_fun
         itg_id, bound = _interrogate_id(interrogate)
@@ -365,3 +372,183 @@ def solve_sim(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interro
                      **params)
     plan.sim(key)
     return plan.x_host()
+
+
+# ---- the posterior at arbitrary times ---------------------------------------------------------------------------------
+EVAL_AT_NODE_TOL = 1e-10      # a time within this many steps of a node is that node
+EVAL_AT_PRIOR_TOL = 1e-10     # Chapman-Kolmogorov residual of prior_at, relative to each matrix's largest entry
+EVAL_AT_BSTATE = (3, 5)       # n_bstate served by rk_eval_at (2 runs padded to 3); at 6 the lane kernel spills
+
+
+def eval_at_nodes(t_eval, t_min, t_max, n_steps):
+    """
+    Where the times ``t_eval`` sit on the solver's grid t_n = t_min + (t_max - t_min) n / N: ``(node, on_node, h1, h2)``.
+    A time within 1e-10 of a step from a node is that node (``on_node``, h1 = h2 = 0); any other lies in
+    (t_node, t_node+1) with h1 = t - t_node and h2 = t_node+1 - t.  Empty, non-finite and outside times raise ValueError.
+    """
+    t = np.asarray(t_eval, dtype=np.float64)
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError(f"t_eval must be a non-empty 1-D array of times, got shape {t.shape}")
+    if not np.all(np.isfinite(t)):
+        raise ValueError("t_eval holds a non-finite time")
+    if np.any(t < t_min) or np.any(t > t_max):
+        raise ValueError(f"t_eval must lie in [t_min, t_max] = [{t_min}, {t_max}], got [{t.min()}, {t.max()}]")
+    N = int(n_steps)
+    x = (t - t_min) / ((t_max - t_min) / N)
+    near = np.rint(x)
+    on = np.abs(x - near) <= EVAL_AT_NODE_TOL
+    node = np.where(on, np.clip(near, 0, N), np.clip(np.floor(x), 0, N - 1)).astype(np.int64)
+
+    def grid(n):
+        return t_min + (t_max - t_min) * n / N
+    return node, on, np.where(on, 0.0, t - grid(node)), np.where(on, 0.0, grid(node + 1) - t)
+
+
+def check_prior_at(first, second, prior_pars, h1, h2):
+    """
+    Chapman-Kolmogorov consistency of ``first = prior_at(h1)`` and ``second = prior_at(h2)`` with the full step's
+    ``prior_pars``: Q2 Q1 = Q and Q2 R1 Q2^T + R2 = R, each to 1e-10 of the block matrix's largest entry (a ``prior_at``
+    built with another sigma or another prior fails it).  Raises ValueError; returns the two residuals (relative).
+    """
+    (Q1, R1), (Q2, R2) = first, second
+    Q, R = (np.asarray(a, dtype=np.float64) for a in prior_pars)
+    Q2t = np.swapaxes(Q2, -1, -2)
+    res = []
+    for name, got, want in (("Q2 Q1 = Q", np.matmul(Q2, Q1), Q), ("Q2 R1 Q2^T + R2 = R", np.matmul(np.matmul(Q2, R1), Q2t) + R2, R)):
+        scale = np.max(np.abs(want), axis=(-1, -2))
+        err = np.max(np.abs(got - want), axis=(-1, -2))
+        if not np.all(err <= EVAL_AT_PRIOR_TOL * scale):
+            raise ValueError(f"prior_at is inconsistent with prior_pars: {name} fails by {np.max(err / scale):.3e} of the matrix's "
+                             f"largest entry at h1 = {h1}, h2 = {h2} (the bar is {EVAL_AT_PRIOR_TOL}); it must be the prior that "
+                             "prior_pars was built from, over a step of the given length")
+        res.append(float(np.max(err / scale)))
+    return tuple(res)
+
+
+def _prior_at_pair(prior_at, h, d, p, B):
+    out = prior_at(float(h))
+    try:
+        Qh, Rh = (np.asarray(a, dtype=np.float64) for a in out)
+    except (TypeError, ValueError):
+        raise ValueError("prior_at(dt) must return the pair (wgt_state, var_state)") from None
+    for a in (Qh, Rh):
+        if a.ndim not in (3, 4) or a.shape[-3:] != (d, p, p) or (a.ndim == 4 and a.shape[0] != B):
+            raise ValueError(f"prior_at(dt) must return matrices of shape ({d}, {p}, {p}) or (B, {d}, {p}, {p}) with the call's "
+                             f"batch size, got {Qh.shape} and {Rh.shape}")
+    return Qh, Rh
+
+
+def _stack_prior(mats, B):
+    """(n_quad, 2, d, p, p) matrices, each (d, p, p) or (B, d, p, p) -> the array rk_eval_at reads and its batched flag."""
+    batched = any(m.ndim == 4 for pair in mats for m in pair)
+    if not batched:
+        return np.array(mats), 0
+    full = np.array([[np.broadcast_to(m, (B,) + m.shape[-3:]) for m in pair] for pair in mats])     # (n_quad, 2, B, d, p, p)
+    return np.ascontiguousarray(np.moveaxis(full, 2, -1)), 1
+
+
+def solve_mv_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, t_eval, prior_at,
+                kalman_type="standard", **params):
+    """
+    Mean and variance of the solver's posterior at the times ``t_eval`` (an addition: the reference's ``solve_mv`` returns
+    its grid only).  The first nine arguments are ``solve_mv``'s, with the same meaning and batching rules.
+
+    ``t_eval`` (T,) holds times in [t_min, t_max] in any order, repeats allowed; the output follows it.  A time within
+    1e-10 of a step from a grid node is that node and gets ``solve_mv``'s own value, bit for bit.  Any other time t in
+    (t_n, t_n+1) gets the closed form that the prior's Markov property gives -- nothing is interrogated between nodes:
+    predict from the filtered moments at t_n over h1 = t - t_n, then one ``smooth_mv`` step against the smoothed moments at
+    t_n+1 over h2 = t_n+1 - t.  ``prior_at(dt)`` returns the prior ``(wgt_state, var_state)`` for a step of length dt, in
+    the shapes ``prior_pars`` may have (for the IBM prior ``lambda h: ibm_init(h, n_deriv, sigma)``): a sub-step's
+    transition cannot be recovered from the full step's.  It is called for h1 and h2 of every distinct off-grid time (not
+    at all when every time is a node) and checked against ``prior_pars`` (``check_prior_at``).
+
+    Returns ``mean (T, d, p)`` and ``var (T, d, p, p)``, with a leading B under ``solve_mv``'s rule.
+
+    Two plans run on the device, ``filter()`` and ``mv()`` with the same key (``mv()`` overwrites its filter records in
+    place, and the counter RNG keys draws by trajectory and step, so interrogate_chkrebtii sees the same draws in both):
+    TWO sets of (N+1)-point records are held on the device at once; ``eval_at_kernel`` reads them there and only the T
+    records per trajectory are downloaded.  Served: kalman_type "standard", n_bstate 2..5, every route of ``solve_mv`` but the
+    dense one; everything else raises before any device work.  ``batch_minor=True`` (a keyword of the plan, not an ODE
+    parameter) forces the batch-minor kernels where a tile route exists, as in ``SolvePlan``.
+    """
+    if kalman_type not in _KALMAN:
+        raise NotImplementedError                        # src/rodeo/solve.py:240-241
+    if kalman_type != "standard":
+        raise NotImplementedError("solve_mv_at: kalman_type='square-root' is not built")
+    batch_minor = bool(params.pop("batch_minor", False))
+    node, on, h1, h2 = eval_at_nodes(t_eval, t_min, t_max, n_steps)
+    W, x0 = np.asarray(ode_weight, dtype=np.float64), np.asarray(ode_init, dtype=np.float64)
+    Q, R = (np.asarray(a, dtype=np.float64) for a in prior_pars)
+    if W.ndim not in (3, 4) or x0.ndim not in (2, 3) or Q.ndim not in (3, 4) or R.ndim not in (3, 4):
+        raise ValueError("ode_weight (d,m,p), ode_init (d,p), prior_pars (d,p,p) [+ optional leading batch axis]")
+    d, m, p = W.shape[-3:]
+    if x0.shape[-2:] != (d, p) or Q.shape[-3:] != (d, p, p) or R.shape[-3:] != (d, p, p):
+        raise ValueError(f"shape mismatch: ode_weight {W.shape}, ode_init {x0.shape}, prior {Q.shape} / {R.shape}")
+    two = _two_state_on_tiles(W, kalman_type)
+    if not (two or EVAL_AT_BSTATE[0] <= p <= EVAL_AT_BSTATE[1]):
+        raise NotImplementedError(f"solve_mv_at: n_bstate = {p} is outside the served range 2..{EVAL_AT_BSTATE[1]} (2 with "
+                                  "n_bmeas = 1 only; beyond, the lane kernel spills)")
+    ode_fun = _device_ode(ode_fun, W, params)
+    itg_id, _ = _interrogate_id(interrogate)
+    theta, Bt = ode_fun.pack_params({k: v for k, v in params.items() if k != "kalman_type"})
+    sizes = [a.shape[0] for a, nd in ((W, 4), (x0, 3), (Q, 4), (R, 4)) if a.ndim == nd] + ([Bt] if Bt is not None else [])
+    if len(set(sizes)) > 1:
+        raise ValueError(f"inconsistent batch sizes {sizes}")
+    B = sizes[0] if sizes else 1
+    cfg = _lib.SolveCfg(n_traj=B, n_steps=int(n_steps), n_block=d, n_bstate=3 if two else p, n_bmeas=m, rhs_id=ode_fun.rhs_id,
+                        interrogate=itg_id, kalman_type=_KALMAN[kalman_type], n_theta=ode_fun.n_theta,
+                        flags=_lib.FLAG_BATCH_MINOR if batch_minor else 0, t_min=float(t_min), t_max=float(t_max), seed=0,
+                        traj_offset=0)
+    lay = C.c_int32(0)
+    _lib.check(_lib.load().rk_solve_layout(C.byref(cfg), _lib.MODE_MV, C.byref(lay)))
+    if lay.value == _lib.LAYOUT_TRAJ_MAJOR:
+        raise NotImplementedError("solve_mv_at: the dense (indep_init) route keeps trajectory-major records, which eval_at_kernel "
+                                  "does not read")
+    # one (Q1, R1, Q2, R2) quadruple per distinct off-grid time
+    slot = np.zeros(len(node), dtype=np.int64)
+    trans, noise = [], []
+    if not np.all(on):
+        times = np.asarray(t_eval, dtype=np.float64)
+        _, first, inverse = np.unique(times[~on], return_index=True, return_inverse=True)
+        slot[~on] = inverse
+        for k in first:
+            a1, a2 = h1[~on][k], h2[~on][k]
+            one, other = _prior_at_pair(prior_at, a1, d, p, B), _prior_at_pair(prior_at, a2, d, p, B)
+            check_prior_at(one, other, (Q, R), a1, a2)
+            if two:
+                one, other = (_pad_two_to_three(W, x0, pair)[2] for pair in (one, other))
+            trans.append((one[0], other[0]))
+            noise.append((one[1], other[1]))
+    else:
+        pp = 3 if two else p
+        trans = noise = [(np.zeros((d, pp, pp)),) * 2]                   # one slot that no query reads
+    if two:
+        W, x0, (Q, R) = _pad_two_to_three(W, x0, (Q, R))
+    mean, var = _eval_at_device(key, ode_fun, W, x0, t_min, t_max, n_steps, interrogate, (Q, R), kalman_type, node, on, slot,
+                                _stack_prior(trans, B), _stack_prior(noise, B), batch_minor, params)
+    if two:
+        return np.ascontiguousarray(mean[..., :2]), np.ascontiguousarray(var[..., :2, :2])
+    return mean, var
+
+
+def _eval_at_device(key, ode_fun, W, x0, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type, node, on, slot, trans,
+                    noise, batch_minor, params):
+    """The device side of ``solve_mv_at``: the two plans, the query upload, rk_eval_at and the download of T records."""
+    plans = [SolvePlan(ode_fun, W, x0, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type, batch_minor=batch_minor,
+                       **params) for _ in range(2)]
+    filt, smooth = plans
+    filt.filter(key)
+    smooth.mv(key)
+    if filt.layout != smooth.layout:
+        raise NotImplementedError(f"solve_mv_at: filter and mv records in different layouts ({filt.layout}, {smooth.layout})")
+    dev = filt.dev
+    query = dev.to_device(np.stack([node, on.astype(np.int64), slot], axis=1).astype(np.int32))
+    trans_dev, noise_dev = dev.to_device(trans[0]), dev.to_device(noise[0])
+    T = len(node)
+    mean, var = dev.empty((filt.B, T, filt.d, filt.p)), dev.empty((filt.B, T, filt.d, filt.p, filt.p))
+    q = _lib.EvalAtIn(n_query=T, n_quad=int(trans[0].shape[0]), query=query.ptr, trans=trans_dev.ptr, trans_batched=trans[1],
+                      noise=noise_dev.ptr, noise_batched=noise[1])
+    _lib.check(dev.lib.rk_eval_at(dev.h, C.byref(filt.cfg), filt.layout, C.byref(filt._out), C.byref(smooth._out), C.byref(q),
+                                  mean.ptr, var.ptr))
+    m, v = mean.to_host(), var.to_host()
+    return (m, v) if filt.batched else (m[0], v[0])
