@@ -299,6 +299,30 @@ int rk_dalton_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in
 int rk_dalton_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
                     const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
                     int32_t n_obs, int32_t n_bobs);
+
+/* dalton_at: rk_dalton_loglik for observations whose times need not be grid nodes (an addition: the reference places every
+ * observation by searchsorted on the grid).  obs / obs_weight / obs_var as for rk_dalton_loglik, in time order.  The device
+ * array `table` (n_obs, 4) holds per observation: node, off-grid flag, pre slot, post slot or -1.  With the flag clear the
+ * observation sits on grid node `node` (0..n_steps) and is handled as by rk_dalton_loglik (node 0: the joint density only).
+ * With it set the time lies in (t_node, t_node+1): the joint filter predicts over the gap since the previous event (node or
+ * observation) with the prior pair (pre_trans, pre_noise)[pre slot], conditions on y, and after the interval's last
+ * observation -- the one whose fourth entry is not -1 -- predicts on to t_node+1 with (post_trans, post_noise)[post slot];
+ * the interrogation and the z update at node + 1 follow as always.  The marginal filter takes the same split predictions
+ * without the conditioning.  Entries must be ordered in time, the off-grid ones of an interval adjacent.  Pairs are
+ * (n, d, p, p) row-major, or (n, d, p, p, B) batch-minor with prior_batched; n_pre and n_post are at least 1 (also when
+ * no slot is used) and slots are clamped to them.  Served range, routes and RK_DALTON_LANES as for rk_dalton_loglik
+ * (kernels: dalton_at_tile3_kernels.hpp / dalton_at_kernels.hpp); logdens (B) is overwritten.                           */
+typedef struct {
+    const int32_t* table;                                /* (n_obs, 4) on the device                              */
+    int32_t        n_pre, n_post;                        /* pairs in pre_* / post_* (each at least 1)             */
+    const double  *pre_trans, *pre_noise;                /* (n_pre, d, p, p [,B]): Q, R over the gap before an observation   */
+    const double  *post_trans, *post_noise;              /* (n_post, d, p, p [,B]): Q, R from the last observation to the node */
+    int32_t        prior_batched;
+} rk_dalton_at_in;
+int rk_dalton_loglik_at(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in,
+                        const double* obs, const double* obs_weight, const double* obs_var, const rk_dalton_at_in* at,
+                        int32_t n_obs, int32_t n_bobs, double* logdens);
+
 /* DALTON for non-Gaussian observations (src/rodeo/inference/dalton.py:547-1039, kalman_type = standard, n_bmeas = 1,
  * n_bstate 2..6 (2..5 with three or more blocks), interrogate rodeo / schober / kramer, any built-in or user right-hand side
  * with n_bmeas = 1).  The observation log-likelihood is HIP source, like a user right-hand side:

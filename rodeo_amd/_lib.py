@@ -70,6 +70,12 @@ class EvalAtIn(C.Structure):
                 ("noise", C.c_void_p), ("noise_batched", C.c_int32)]
 
 
+class DaltonAtIn(C.Structure):
+    _fields_ = [("table", C.c_void_p), ("n_pre", C.c_int32), ("n_post", C.c_int32),
+                ("pre_trans", C.c_void_p), ("pre_noise", C.c_void_p), ("post_trans", C.c_void_p), ("post_noise", C.c_void_p),
+                ("prior_batched", C.c_int32)]
+
+
 class OpCfg(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_state", C.c_int32), ("n_meas", C.c_int32), ("kalman_type", C.c_int32)]
 
@@ -119,6 +125,7 @@ SIGNATURES = {
     "rk_dalton_layout": (C.c_int, [_P, _I, _I, C.POINTER(C.c_int32)]),
     "rk_dalton_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "rk_dalton_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I]),
+    "rk_dalton_loglik_at": (C.c_int, [_H, _P, _P, _P, _P, _P, C.POINTER(DaltonAtIn), _I, _I, _P]),
     "rk_register_obs_source": (C.c_int, [C.c_char_p, C.c_char_p, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "rk_obs_compile_check": (C.c_int, [_I, _I, _I]),
     "rk_daltonng_workspace_bytes": (C.c_int, [_P, _I, C.POINTER(C.c_size_t)]),

@@ -88,6 +88,9 @@ static std::string kernel_expr(const UserRhs& u, int P, int itg, JitKind kind) {
                  kind == JIT_DALTON_STORE ? "true" : "false");
     else if (kind == JIT_DALTON_TILE3 || kind == JIT_DALTON_TILE3_STORE)
         snprintf(buf, sizeof buf, "rk::dalton_fwd_tile3_kernel<rk::UserRhsT, %d, %s>", itg, kind == JIT_DALTON_TILE3_STORE ? "true" : "false");
+    else if (kind == JIT_DALTON_AT)                               // P key = n_bstate + 16 n_bobs (user_dalton_at)
+        snprintf(buf, sizeof buf, "rk::dalton_fwd_at_kernel<rk::UserRhsT, %d, %d, %d>", P % 16, itg, P / 16);
+    else if (kind == JIT_DALTON_AT_TILE3) snprintf(buf, sizeof buf, "rk::dalton_fwd_at_tile3_kernel<rk::UserRhsT, %d>", itg);
     else if (kind == JIT_TILEN) snprintf(buf, sizeof buf, "rk::fwd_tilen_kernel<rk::UserRhsT, %d, %d>", itg, P);  // P here = NB
     else snprintf(buf, sizeof buf, "rk::fwd_kernel<rk::UserRhsT, %d, %d, %s>", P, itg, kind == JIT_FWD_STORE_PRED ? "true" : "false");
     return buf;
@@ -105,6 +108,8 @@ static int jit_compile(const UserRhs& u, int P, int itg, JitKind kind, std::vect
                             // (only the DALTON kinds include its header: the source of every other build is unchanged)
                             (kind == JIT_DALTON || kind == JIT_DALTON_STORE ? "#include \"dalton_kernels.hpp\"\n" : "") +
                             (kind == JIT_DALTON_TILE3 || kind == JIT_DALTON_TILE3_STORE ? "#include \"dalton_tile3_kernels.hpp\"\n" : "") +
+                            (kind == JIT_DALTON_AT ? "#include \"dalton_at_kernels.hpp\"\n" : "") +
+                            (kind == JIT_DALTON_AT_TILE3 ? "#include \"dalton_at_tile3_kernels.hpp\"\n" : "") +
                             "namespace rk {\n" + u.source + "\nusing UserRhsT = " + u.type_name + ";\n}  // namespace rk\n";
     return jit_compile_src(src, kernel_expr(u, P, itg, kind), u.type_name, code, lowered);
 }
@@ -325,6 +330,28 @@ int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Da
     const int grid = tile ? div_up((store ? a.B : 2 * a.B) * c->n_block, c->n_block == 3 ? 3 : 4) : div_up(a.B, store ? 64 : 32);
     LaunchTimer t(h, tile ? (store ? "dalton_fwd_tile3_kernel<store, user>" : "dalton_fwd_tile3_kernel<loglik, user>")
                           : (store ? "dalton_fwd_kernel<store, user>" : "dalton_fwd_kernel<loglik, user>"));
+    RK_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
+    t.stop();
+    return RK_OK;
+}
+
+// dalton_at's forward filters around a user right-hand side (dalton_at_kernels.hpp / dalton_at_tile3_kernels.hpp): the
+// log-likelihood form only, launched like user_dalton's.
+int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const DaltonAt& s, int n_bobs,
+                   bool tile, double* out) {
+    int rc = user_rhs_check(c);
+    if (rc) return rc;
+    RK_REQUIRE(user_n_bmeas(c->rhs_id) == 1, RK_ERR_UNSUPPORTED, "dalton_at: n_bmeas = 1 only");
+    hipFunction_t fn;
+    if (tile) rc = jit_get(h, c->rhs_id, 3, c->interrogate, JIT_DALTON_AT_TILE3, &fn);
+    else rc = jit_get(h, c->rhs_id, c->n_bstate + 16 * n_bobs, c->interrogate, JIT_DALTON_AT, &fn);
+    if (rc) return rc;
+    SolveArgs args = a;
+    const DaltonObs* op = &o;
+    const DaltonAt* sp = &s;
+    void* params[] = {&args, (void*)op, (void*)sp, &out};
+    const int grid = tile ? div_up(2 * a.B * c->n_block, c->n_block == 3 ? 3 : 4) : div_up(a.B, 32);
+    LaunchTimer t(h, tile ? "dalton_fwd_at_tile3_kernel<user>" : "dalton_fwd_at_kernel<user>");
     RK_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
     t.stop();
     return RK_OK;

@@ -15,6 +15,7 @@ namespace rk {
 struct DenseItgArgs;
 struct SimLogpost;
 struct DaltonObs;
+struct DaltonAt;
 
 // ---- lane-per-trajectory solver (solve_small.hip): helpers that DALTON (dalton.hip) shares ------------------------------
 int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in);
@@ -49,6 +50,8 @@ enum JitKind : int {
     JIT_DALTONNG = 15,        // daltonng_fwd_kernel<.., false> (joint filter's moments; cached per (rhs, obs model))
     JIT_DALTONNG_BOTH = 16,   // daltonng_fwd_kernel<.., true>  (joint filter and the filter on Z alone)
     JIT_DALTONNG_OBS = 17,    // daltonng_obs_kernel (logy_x and the final sum; no right-hand side)
+    JIT_DALTON_AT = 18,       // dalton_fwd_at_kernel (dalton_at's log-likelihood; P key = n_bstate + 16 n_bobs)
+    JIT_DALTON_AT_TILE3 = 19, // dalton_fwd_at_tile3_kernel (dalton_at's log-likelihood on the p = 3 tiles)
 };
 bool is_user_rhs(int rhs_id);
 bool user_tile_available(const rk_solve_cfg* c, JitKind tile);
@@ -58,6 +61,8 @@ int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a);
 int user_rhs_check(const rk_solve_cfg* c);
 int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, int n_bobs, bool store,
                 bool tile, double* out);
+int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const DaltonAt& s, int n_bobs,
+                   bool tile, double* out);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them

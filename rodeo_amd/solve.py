@@ -75,6 +75,29 @@ def _device_ode(ode_fun, ode_weight, params):
     return from_python(ode_fun, int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1]), **sizes)
 
 
+def _shape_rule(ode_fun, ode_weight, ode_init, prior_pars, params):
+    """
+    The shape and batch-size rule of a solver call, on the host and in one place (``SolvePlan``, ``solve_mv_at``,
+    ``inference.dalton.dalton_at``): ``ode_fun`` is a ``DeviceODE``; returns ``(W, x0, Q, R, theta, Bt, sizes)`` with the arrays
+    as float64, ``(theta, Bt)`` from ``pack_params(params)`` and ``sizes`` the leading batch sizes found (empty: unbatched).
+    """
+    W = np.asarray(ode_weight, dtype=np.float64)
+    x0 = np.asarray(ode_init, dtype=np.float64)
+    Q, R = (np.asarray(a, dtype=np.float64) for a in prior_pars)
+    if W.ndim not in (3, 4) or x0.ndim not in (2, 3) or Q.ndim not in (3, 4) or R.ndim not in (3, 4):
+        raise ValueError("ode_weight (d,m,p), ode_init (d,p), prior_pars (d,p,p) [+ optional leading batch axis]")
+    d, m, p = W.shape[-3:]
+    if x0.shape[-2:] != (d, p) or Q.shape[-3:] != (d, p, p) or R.shape[-3:] != (d, p, p):
+        raise ValueError(f"shape mismatch: ode_weight {W.shape}, ode_init {x0.shape}, prior {Q.shape} / {R.shape}")
+    theta, Bt = ode_fun.pack_params(params)
+    sizes = [a.shape[0] for a, nd in ((W, 4), (x0, 3), (Q, 4), (R, 4)) if a.ndim == nd]
+    if Bt is not None:
+        sizes.append(Bt)
+    if len(set(sizes)) > 1:
+        raise ValueError(f"inconsistent batch sizes {sizes}")
+    return W, x0, Q, R, theta, Bt, sizes
+
+
 class SolvePlan:
     """
     Device-resident form of one solver call: inputs uploaded once in the batch-minor layout, outputs allocated once.
@@ -99,22 +122,8 @@ class SolvePlan:
                 raise NotImplementedError                # src/rodeo/interrogate.py:43-44
             if kt != kalman_type:
                 raise NotImplementedError("interrogate_chkrebtii's kalman_type must equal the solver's kalman_type")
-        prior_weight, prior_var = prior_pars
-        W = np.asarray(ode_weight, dtype=np.float64)
-        x0 = np.asarray(ode_init, dtype=np.float64)
-        Q = np.asarray(prior_weight, dtype=np.float64)
-        R = np.asarray(prior_var, dtype=np.float64)
-        if W.ndim not in (3, 4) or x0.ndim not in (2, 3) or Q.ndim not in (3, 4) or R.ndim not in (3, 4):
-            raise ValueError("ode_weight (d,m,p), ode_init (d,p), prior_pars (d,p,p) [+ optional leading batch axis]")
+        W, x0, Q, R, theta, Bt, sizes = _shape_rule(ode_fun, ode_weight, ode_init, prior_pars, params)
         d, m, p = W.shape[-3:]
-        if x0.shape[-2:] != (d, p) or Q.shape[-3:] != (d, p, p) or R.shape[-3:] != (d, p, p):
-            raise ValueError(f"shape mismatch: ode_weight {W.shape}, ode_init {x0.shape}, prior {Q.shape} / {R.shape}")
-        theta, Bt = ode_fun.pack_params(params)
-        sizes = [a.shape[0] for a, nd in ((W, 4), (x0, 3), (Q, 4), (R, 4)) if a.ndim == nd]
-        if Bt is not None:
-            sizes.append(Bt)
-        if len(set(sizes)) > 1:
-            raise ValueError(f"inconsistent batch sizes {sizes}")
         self.batched = bool(sizes)
         B = sizes[0] if sizes else 1
         if (ode_fun.n_block, ode_fun.n_bmeas) != (d, m):
@@ -477,23 +486,18 @@ def solve_mv_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, inter
         raise NotImplementedError("solve_mv_at: kalman_type='square-root' is not built")
     batch_minor = bool(params.pop("batch_minor", False))
     node, on, h1, h2 = eval_at_nodes(t_eval, t_min, t_max, n_steps)
-    W, x0 = np.asarray(ode_weight, dtype=np.float64), np.asarray(ode_init, dtype=np.float64)
-    Q, R = (np.asarray(a, dtype=np.float64) for a in prior_pars)
-    if W.ndim not in (3, 4) or x0.ndim not in (2, 3) or Q.ndim not in (3, 4) or R.ndim not in (3, 4):
+    W = np.asarray(ode_weight, dtype=np.float64)
+    if W.ndim not in (3, 4):
         raise ValueError("ode_weight (d,m,p), ode_init (d,p), prior_pars (d,p,p) [+ optional leading batch axis]")
+    ode_fun = _device_ode(ode_fun, W, params)
+    W, x0, Q, R, theta, Bt, sizes = _shape_rule(ode_fun, W, ode_init, prior_pars,
+                                                 {k: v for k, v in params.items() if k != "kalman_type"})
     d, m, p = W.shape[-3:]
-    if x0.shape[-2:] != (d, p) or Q.shape[-3:] != (d, p, p) or R.shape[-3:] != (d, p, p):
-        raise ValueError(f"shape mismatch: ode_weight {W.shape}, ode_init {x0.shape}, prior {Q.shape} / {R.shape}")
     two = _two_state_on_tiles(W, kalman_type)
     if not (two or EVAL_AT_BSTATE[0] <= p <= EVAL_AT_BSTATE[1]):
         raise NotImplementedError(f"solve_mv_at: n_bstate = {p} is outside the served range 2..{EVAL_AT_BSTATE[1]} (2 with "
                                   "n_bmeas = 1 only; beyond, the lane kernel spills)")
-    ode_fun = _device_ode(ode_fun, W, params)
     itg_id, _ = _interrogate_id(interrogate)
-    theta, Bt = ode_fun.pack_params({k: v for k, v in params.items() if k != "kalman_type"})
-    sizes = [a.shape[0] for a, nd in ((W, 4), (x0, 3), (Q, 4), (R, 4)) if a.ndim == nd] + ([Bt] if Bt is not None else [])
-    if len(set(sizes)) > 1:
-        raise ValueError(f"inconsistent batch sizes {sizes}")
     B = sizes[0] if sizes else 1
     cfg = _lib.SolveCfg(n_traj=B, n_steps=int(n_steps), n_block=d, n_bstate=3 if two else p, n_bmeas=m, rhs_id=ode_fun.rhs_id,
                         interrogate=itg_id, kalman_type=_KALMAN[kalman_type], n_theta=ode_fun.n_theta,
