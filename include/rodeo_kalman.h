@@ -323,6 +323,23 @@ int rk_dalton_loglik_at(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in*
                         const double* obs, const double* obs_weight, const double* obs_var, const rk_dalton_at_in* at,
                         int32_t n_obs, int32_t n_bobs, double* logdens);
 
+/* fenrir_at: rk_fenrir_backward for observations whose times need not be grid nodes (an addition), after rk_solve_filter with the
+ * same cfg / in.  obs / obs_weight / obs_var as for rk_fenrir_backward, in time order; `at` is rk_dalton_loglik_at's table and
+ * prior pairs.  Fenrir's forward pass is free of data, so an observation in (t_node, t_node+1) adds hops to the backward Markov
+ * chain: with the interval's observations 1..k, the forward moments at their times are predictions from filt[node] over the
+ * pre pairs, hop j (over pre pair j+1, or the post pair for j = k) is the smooth_cond map (standard.py:366-370) between two
+ * neighbouring events, and the chain runs from node+1 down to node through the hops k..0, conditioning on y_j after hop j >= 1.
+ * The hop records are evaluated time-parallel into `workspace` first (rk_fenrir_at_workspace_bytes with n_records = n_pre +
+ * n_post; released by the caller after the call).  Served: kalman_type standard; the RK_LAYOUT_TILE3 records (no flags,
+ * n_bstate = 3, n_bobs = 1) or the batch-minor filtered and predicted moments (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR, n_bstate
+ * 2..6, n_bobs 1..3).  Everything else -- the square-root form, n_bstate 7 and 8, the blocked-tile records -- is refused with
+ * RK_ERR_UNSUPPORTED on the configuration alone, before the handle or any pointer is looked at.  logdens (B) is overwritten.  */
+typedef rk_dalton_at_in rk_fenrir_at_in;
+int rk_fenrir_at_workspace_bytes(const rk_solve_cfg* cfg, int32_t n_bobs, int32_t n_records, size_t* bytes);
+int rk_fenrir_backward_at(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out,
+                          const double* obs, const double* obs_weight, const double* obs_var, const rk_fenrir_at_in* at,
+                          int32_t n_obs, int32_t n_bobs, void* workspace, double* logdens);
+
 /* DALTON for non-Gaussian observations (src/rodeo/inference/dalton.py:547-1039, kalman_type = standard, n_bmeas = 1,
  * n_bstate 2..6 (2..5 with three or more blocks), interrogate rodeo / schober / kramer, any built-in or user right-hand side
  * with n_bmeas = 1).  The observation log-likelihood is HIP source, like a user right-hand side:

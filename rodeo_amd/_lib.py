@@ -126,6 +126,8 @@ SIGNATURES = {
     "rk_dalton_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "rk_dalton_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I]),
     "rk_dalton_loglik_at": (C.c_int, [_H, _P, _P, _P, _P, _P, C.POINTER(DaltonAtIn), _I, _I, _P]),
+    "rk_fenrir_at_workspace_bytes": (C.c_int, [_P, _I, _I, C.POINTER(C.c_size_t)]),
+    "rk_fenrir_backward_at": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, C.POINTER(DaltonAtIn), _I, _I, _P, _P]),
     "rk_register_obs_source": (C.c_int, [C.c_char_p, C.c_char_p, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "rk_obs_compile_check": (C.c_int, [_I, _I, _I]),
     "rk_daltonng_workspace_bytes": (C.c_int, [_P, _I, C.POINTER(C.c_size_t)]),

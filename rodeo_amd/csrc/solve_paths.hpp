@@ -16,6 +16,7 @@ struct DenseItgArgs;
 struct SimLogpost;
 struct DaltonObs;
 struct DaltonAt;
+struct FenrirAt;
 
 // ---- lane-per-trajectory solver (solve_small.hip): helpers that DALTON (dalton.hip) shares ------------------------------
 int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in);
@@ -93,6 +94,7 @@ int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs&
                             double* logpost);
 int tile3_fenrir_backward(rk_handle h, const SolveArgs& a, const double* tiles, const double* obs, const double* obs_w,
                           const double* obs_v, const int32_t* obs_ind, int n_obs, double* logdens);
+int tile3_fenrir_backward_at(rk_handle h, const SolveArgs& a, const double* tiles, const FenrirAt& ob);
 bool tile4_supported(const rk_solve_cfg* c, int mode);
 int tile4_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode);
 size_t tile4_doubles(const rk_solve_cfg* c);

@@ -151,25 +151,26 @@ def _compose(chain):
     return Qc, Rc
 
 
-def _at_layout(times, t_min, t_max, n_steps, prior_at, prior_pars, d, p, B):
+def _at_layout(times, t_min, t_max, n_steps, prior_at, prior_pars, d, p, B, who="dalton_at"):
     """
     Where the observation times sit on the grid and the sub-step priors they need, checked on the host: returns
     ``(table (n_obs, 4) int32, pre, post)`` with table rows (node, off-grid flag, pre slot, post slot or -1) and ``pre`` /
     ``post`` lists of (Q, R) pairs (empty when every time is a node: ``prior_at`` is then never called).  Each interval's
-    chain of sub-steps must compose to ``prior_pars`` (Chapman-Kolmogorov, ``check_prior_at``'s bar).
+    chain of sub-steps must compose to ``prior_pars`` (Chapman-Kolmogorov, ``check_prior_at``'s bar).  ``who`` names the caller
+    in the messages (``fenrir.fenrir_at`` shares this builder).
     """
     t = np.asarray(times, dtype=np.float64)
     if t.ndim != 1 or t.size == 0:
-        raise ValueError(f"dalton_at: obs_times must be a non-empty 1-D array, got shape {t.shape}")
+        raise ValueError(f"{who}: obs_times must be a non-empty 1-D array, got shape {t.shape}")
     if not np.all(np.isfinite(t)):
-        raise ValueError("dalton_at: obs_times holds a non-finite time")
+        raise ValueError(f"{who}: obs_times holds a non-finite time")
     if np.any(np.diff(t) <= 0):
-        raise ValueError("dalton_at: obs_times must be strictly increasing")
+        raise ValueError(f"{who}: obs_times must be strictly increasing")
     if t[0] < t_min or t[-1] > t_max:
-        raise ValueError(f"dalton_at: obs_times must lie in [t_min, t_max] = [{t_min}, {t_max}], got [{t[0]}, {t[-1]}]")
+        raise ValueError(f"{who}: obs_times must lie in [t_min, t_max] = [{t_min}, {t_max}], got [{t[0]}, {t[-1]}]")
     node, on, _, _ = eval_at_nodes(t, t_min, t_max, n_steps)
     if np.any(np.diff(node[on]) == 0):
-        raise ValueError("dalton_at: two observation times are the same grid node (within EVAL_AT_NODE_TOL of a step)")
+        raise ValueError(f"{who}: two observation times are the same grid node (within EVAL_AT_NODE_TOL of a step)")
     N = int(n_steps)
     table = np.zeros((len(t), 4), dtype=np.int32)
     table[:, 0], table[:, 1], table[:, 3] = node, ~on, -1

@@ -14,8 +14,11 @@ vector observations run on the lane-per-trajectory kernels (LU update, eigendeco
 pass is the square-root filter and every backward step map comes from ``square_root.py``; its ``forecast`` squares the
 factor before the log-density sees it (square_root.py:343-344), so the value is the same log-likelihood as in covariance
 form for ``L L^T`` inputs (tests).  Lane-per-trajectory kernels (``fenrir_sqrt.hip``), n_bstate 2 .. 8.
+``fenrir_at`` (an addition; imported from this module, not re-exported by ``rodeo_amd.inference``): ``fenrir`` with the
+observations at their own times, between grid nodes where they fall there (``rk_fenrir_backward_at``).
 """
 import ctypes as C
+import os
 import numpy as np
 from .. import _lib
 from ..solve import cached_plan
@@ -35,6 +38,11 @@ def fenrir(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogat
     else:
         plan = _plan_for(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type, params,
                          tiles_ok=n_bobs == 1)
+    return _backward_on_grid(plan, key, obs, D, Om, n_bobs, ind)
+
+
+def _backward_on_grid(plan, key, obs, D, Om, n_bobs, ind):
+    """The forward filter of `plan` and rk_fenrir_backward with the observations at the grid indices `ind`."""
     if D.shape[1:] != (plan.d, n_bobs, plan.p):
         raise ValueError(f"obs_weight must have shape (n_obs, {plan.d}, n_bobs, {plan.p})")
     plan.filter(key)
@@ -85,6 +93,80 @@ def _plan_for(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate,
     if not on_tiles:
         plan = cached_plan(*args, store_pred=True, batch_minor=True, **params)
     return plan
+
+
+# --- observations between grid nodes (an addition) -----------------------------------------------
+
+def fenrir_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
+              obs_data, obs_times, obs_weight, obs_var, prior_at, kalman_type="standard", **params):
+    """
+    ``fenrir`` with the observations at their own times (an addition: ``fenrir`` snaps every time to the next grid node):
+    log p(Y | Z), a float, or an array (B,) for batched inputs.  The first thirteen arguments and the batching rules are
+    ``fenrir``'s; ``prior_at(dt)`` is ``solve_mv_at``'s, the prior ``(wgt_state, var_state)`` over a step of length dt
+    (``lambda h: ibm_init(h, n_deriv, sigma)``).  Imported from this module, not re-exported by ``rodeo_amd.inference``.
+
+    ``obs_times`` must be strictly increasing, finite and in [t_min, t_max] (ValueError; a time past t_max is an error here).
+    A time within ``EVAL_AT_NODE_TOL`` of a step from a node is that node; two times on one node are an error.  When every
+    time is a node, ``prior_at`` is never called and the call is ``fenrir`` on those node indices, bit for bit (the same
+    kernels run).  Fenrir's forward pass is free of data, so it is unchanged; an observation at t in (t_n, t_n+1) adds hops to
+    the backward Markov chain between the nodes n + 1 and n: the forward moments at the observation times are predictions from
+    the filtered moments at t_n with ``prior_at(gap)``, each hop is the ``smooth_cond`` map between two neighbouring events,
+    and the chain is conditioned on y where it lands on an observation time.  Nothing is interrogated between nodes.  The
+    sub-step priors of every such interval must compose to ``prior_pars`` (``check_prior_at``'s 1e-10 bar).
+
+    Served: ``kalman_type="standard"``; n_bstate = 3 with one observation per block on the MFMA tiles, n_bstate 2 .. 6 with
+    n_bobs 1 .. 3 on the lane-per-trajectory kernels with stored predictions (``RK_FENRIR_AT_LANES=1``, read per call, forces
+    the lanes where the tiles serve).  The square-root form and n_bstate 7, 8 raise NotImplementedError.  All refusals come
+    before any device work.
+    """
+    from ..solve import _device_ode, _shape_rule
+    from .dalton import _at_layout, _stack_pairs                    # (dalton imports _check_obs from this module)
+    if kalman_type == "square-root":
+        raise NotImplementedError("fenrir_at: the square-root form is not built on the device (kalman_type='standard' only)")
+    if kalman_type != "standard":
+        raise NotImplementedError                                   # fenrir.py:293-298
+    W = np.shape(ode_weight)
+    if len(W) not in (3, 4):
+        raise ValueError("ode_weight must have shape (n_block, n_bmeas, n_bstate) [+ a leading batch axis]")
+    if not 2 <= W[-1] <= 6:
+        raise NotImplementedError(f"fenrir_at on the device: n_bstate in 2..6, got {W[-1]}")
+    obs, D, Om, n_bobs = _check_obs(obs_data, obs_weight, obs_var)
+    if D.shape[1:] != (W[-3], n_bobs, W[-1]):
+        raise ValueError(f"obs_weight must have shape (n_obs, {W[-3]}, n_bobs, {W[-1]})")
+    if not callable(prior_at):
+        raise TypeError("fenrir_at: prior_at must be a callable prior_at(dt) -> (wgt_state, var_state)")
+    if np.shape(obs_times) != (obs.shape[0],):
+        raise ValueError(f"fenrir_at: obs_times must have shape ({obs.shape[0]},), got {np.shape(obs_times)}")
+    _, _, Q, R, _, _, sizes = _shape_rule(_device_ode(ode_fun, ode_weight, params), ode_weight, ode_init, prior_pars, params)
+    B = sizes[0] if sizes else 1
+    d, p = int(W[-3]), int(W[-1])
+    table, pre, post = _at_layout(obs_times, t_min, t_max, n_steps, prior_at, (Q, R), d, p, B, who="fenrir_at")
+    args = (ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type, params)
+    if not pre:                                                     # every time is a node: fenrir itself, on those nodes
+        return _backward_on_grid(_plan_for(*args, tiles_ok=n_bobs == 1), key, obs, D, Om, n_bobs, table[:, 0].astype(np.int64))
+    lanes = os.environ.get("RK_FENRIR_AT_LANES", "0") not in ("", "0")
+    plan = _plan_for(*args, tiles_ok=n_bobs == 1 and not lanes, tiles_blocked_ok=False)
+    (pre_q, pre_r), qb = _stack_pairs(pre, B)
+    (post_q, post_r), _ = _stack_pairs(post, B, force=qb)
+    plan.filter(key)
+    dev = plan.dev
+    cache = plan.__dict__.setdefault("_fenrir_at_obs", {})
+    arrays = (obs, D, Om, table, pre_q, pre_r, post_q, post_r)
+    sig = tuple(a.tobytes() for a in arrays)
+    if cache.get("sig") != sig:
+        cache["sig"] = sig
+        cache["dev"] = tuple(dev.to_device(np.ascontiguousarray(a)) for a in arrays)
+    d_obs, d_w, d_v, d_tab, d_pq, d_pr, d_sq, d_sr = cache["dev"]
+    at = _lib.DaltonAtIn(table=d_tab.ptr, n_pre=len(pre), n_post=len(post), pre_trans=d_pq.ptr, pre_noise=d_pr.ptr,
+                         post_trans=d_sq.ptr, post_noise=d_sr.ptr, prior_batched=qb)
+    need = C.c_size_t(0)
+    _lib.check(dev.lib.rk_fenrir_at_workspace_bytes(C.byref(plan.cfg), n_bobs, len(pre) + len(post), C.byref(need)))
+    ws = dev.empty((need.value // 8,))                              # the hop records: released on return
+    out = dev.empty((plan.B,))
+    _lib.check(dev.lib.rk_fenrir_backward_at(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out), d_obs.ptr, d_w.ptr,
+                                             d_v.ptr, C.byref(at), int(table.shape[0]), n_bobs, ws.ptr, out.ptr))
+    ll = out.to_host()
+    return ll if plan.batched else float(ll[0])
 
 
 def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
