@@ -233,7 +233,8 @@ int rk_eval_at(rk_handle h, const rk_solve_cfg* cfg, int32_t layout, const rk_so
  * src/rodeo/inference/basic.py:47-62 with a Gaussian obs_loglik).
  *   state: the solver output holding the path -- layout RK_LAYOUT_BATCH_MINOR: x_state / mean_state (N+1, d, p, B);
  *          layout RK_LAYOUT_TILE3 / RK_LAYOUT_TILE4: the tile buffer (the mean is column 3 / entries 16..19);
- *   obs (n_obs, d) row-major on device; obs_ind (n_obs) int32 on device (clamped to [0, N]);
+ *   obs (n_obs, d) row-major on device; obs_ind (n_obs) int32 on device (clamped to [0, N]), any order; with
+ *   n_obs = 0 (prior only, or zeros without upars) neither is read and both may be NULL -- here and below;
  *   upars (n_prior, B) batch-minor or NULL (no prior term); out logpost (B).                              */
 int rk_gauss_obs_logpost(rk_handle h, int32_t n_traj, int32_t n_steps, int32_t n_block, int32_t n_bstate,
                          int32_t layout, const double* state, const double* obs, const int32_t* obs_ind,
@@ -246,7 +247,12 @@ int rk_gauss_obs_logpost(rk_handle h, int32_t n_traj, int32_t n_steps, int32_t n
  * (src/rodeo/inference/pseudo_marginal.py:135-149).  On the n_bstate = 3 tile path with n_block in {1, 2, 4} the backward
  * sampler reduces the log-posterior itself (no second launch) and out->x_state may be NULL: then no path is stored at
  * all and logpost (B) is the only result.  Any other configuration runs the two kernels back to back and needs x_state.
- * upars / obs / obs_ind must be on the device BEFORE the call (upload them before launching, not between the launches).  */
+ * upars / obs / obs_ind must be on the device BEFORE the call (upload them before launching, not between the launches).
+ * obs_ind is REQUIRED to be ascending (equal neighbours allowed) on the fused route: the sampler walks the indices from the
+ * end and waits for its step index to meet the next one, so an index that is larger than its successor is never met --
+ * its terms and those of every observation before it are left out of logpost, and no error is returned (the indices live
+ * on the device; checking them would cost a download per evaluation).  Sort them, rows of obs along, before the upload
+ * (rodeo_amd.inference.logpost.check_obs does).  The two-kernel route and rk_gauss_obs_logpost accept any order.        */
 int rk_solve_sim_logpost(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out,
                          const double* obs, const int32_t* obs_ind, int32_t n_obs, double noise_sd,
                          const double* upars, int32_t n_prior, double prior_sd, double* logpost);

@@ -661,7 +661,8 @@ int rk_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* 
                          const double* obs, const int32_t* obs_ind, int32_t n_obs, double noise_sd,
                          const double* upars, int32_t n_prior, double prior_sd, double* logpost) {
     RK_REQUIRE(h, RK_ERR_INVALID, "null handle");
-    RK_REQUIRE(obs && obs_ind && logpost && n_obs >= 0, RK_ERR_INVALID, "rk_solve_sim_logpost: null obs / obs_ind / logpost");
+    RK_REQUIRE(logpost && n_obs >= 0 && (n_obs == 0 || (obs && obs_ind)), RK_ERR_INVALID,
+               "rk_solve_sim_logpost: null obs / obs_ind / logpost");      // (no observation: prior only, obs / obs_ind are not read)
     RK_REQUIRE(!upars || n_prior >= 0, RK_ERR_INVALID, "rk_solve_sim_logpost: n_prior < 0");
     int rc = check_cfg(c, in);
     if (rc) return rc;
@@ -712,7 +713,7 @@ int rk_gauss_obs_logpost(rk_handle h, int32_t n_traj, int32_t n_steps, int32_t n
                          int32_t layout, const double* x_state, const double* obs, const int32_t* obs_ind,
                          int32_t n_obs, double noise_sd, const double* upars, int32_t n_prior, double prior_sd,
                          double* logpost) {
-    RK_REQUIRE(h && x_state && obs && obs_ind && logpost, RK_ERR_INVALID, "rk_gauss_obs_logpost: null argument");
+    RK_REQUIRE(h && x_state && logpost && (n_obs <= 0 || (obs && obs_ind)), RK_ERR_INVALID, "rk_gauss_obs_logpost: null argument");
     RK_REQUIRE(layout == RK_LAYOUT_BATCH_MINOR || (layout == RK_LAYOUT_TILE3 && n_bstate == 3) ||
                    (layout == RK_LAYOUT_TILE4 && n_bstate == 4) || (layout == RK_LAYOUT_TILEP && n_bstate >= 4), RK_ERR_INVALID,
                "rk_gauss_obs_logpost: bad layout %d for n_bstate %d", layout, n_bstate);

@@ -20,24 +20,43 @@ def obs_index(t_min, t_max, n_steps, obs_times):
     return np.searchsorted(sim_times, np.asarray(obs_times, dtype=np.float64)).astype(np.int32)
 
 
+def check_obs(obs_data, obs_ind, d, n_steps):
+    """
+    The observations as the kernels read them: ``(obs (n_obs, d) float64, ind (n_obs,) int32)``, both C-contiguous, with
+    ``ind`` ASCENDING.  Raises ``ValueError`` for a shape other than (n_obs, d) / (n_obs,) or an index outside [0, n_steps].
+    Indices may come in any order (the reference's ``Xt[obs_ind]`` takes any): where they descend somewhere they are sorted
+    -- a stable sort, so repeated indices keep their order -- with the rows of ``obs`` carried along.  The sampler that
+    reduces the log-posterior itself (bwd_sim_tile3_kernel<true>) walks the indices from the end and needs them ascending.
+    """
+    obs = np.ascontiguousarray(obs_data, dtype=np.float64)
+    ind = np.ascontiguousarray(obs_ind, dtype=np.int32)
+    if ind.ndim != 1 or obs.shape != (ind.shape[0], d):
+        raise ValueError(f"obs_data must have shape (n_obs, {d}) and obs_ind (n_obs,)")
+    if ind.size and (ind.min() < 0 or ind.max() > n_steps):
+        raise ValueError("obs_ind outside the solver grid")
+    if np.any(np.diff(ind) < 0):
+        order = np.argsort(ind, kind="stable")
+        obs, ind = np.ascontiguousarray(obs[order]), np.ascontiguousarray(ind[order])
+    return obs, ind
+
+
 def gauss_obs_logpost(plan, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10.0, n_prior=None, which="auto",
                       reuse_out=False):
     """
     ``plan``: a ``SolvePlan`` whose ``mv()`` / ``sim()`` has been launched.  ``obs_data`` (n_obs, d), ``obs_ind``
     (n_obs,) int; ``upars`` (B, k) optional unconstrained parameters whose first ``n_prior`` entries get a
     N(0, prior_sd^2) prior.  Returns a DeviceArray of shape (B,) (call ``.to_host()``): a fresh one, or -- with
-    ``reuse_out=True`` -- one of four buffers owned by the plan that later calls overwrite in turn.
+    ``reuse_out=True`` -- one of four buffers owned by the plan that later calls overwrite in turn.  ``obs_ind`` may come in
+    any order (``check_obs``).  ``which``: "x" reduces over the path of the last sampler launch and raises ``RuntimeError``
+    when that launch stored none (a path-less ``sim_logpost``), "mean" over the moments of the last filter() / mv(), "auto"
+    picks "x" after a sampler launch.
     """
     dev = plan.dev
-    obs = np.ascontiguousarray(obs_data, dtype=np.float64)
-    ind = np.ascontiguousarray(obs_ind, dtype=np.int32)
-    if obs.shape != (ind.shape[0], plan.d):
-        raise ValueError(f"obs_data must have shape (n_obs, {plan.d})")
-    if ind.size and (ind.min() < 0 or ind.max() > plan.N):
-        raise ValueError("obs_ind outside the solver grid")
-    if which == "auto":
-        which = "x" if plan.x_state is not None and plan.last_mode == _lib.MODE_SIM else "mean"
+    obs, ind = check_obs(obs_data, obs_ind, plan.d, plan.N)
+    if which == "auto":                  # (after a path-less sim_logpost it is "x" too, and raises: no stale path, no filter mean)
+        which = "x" if plan.last_mode == _lib.MODE_SIM else "mean"
     if which == "x":
+        plan._require_path()
         state, layout = plan.x_state, _lib.LAYOUT_BATCH_MINOR
     else:
         layout = plan.layout
@@ -83,12 +102,7 @@ def gauss_obs_logpost(plan, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10
 def _staged(plan, obs_data, obs_ind, upars, n_prior):
     """Device copies of the observations / indices (cached on the plan while unchanged) and of the transposed parameters."""
     dev = plan.dev
-    obs = np.ascontiguousarray(obs_data, dtype=np.float64)
-    ind = np.ascontiguousarray(obs_ind, dtype=np.int32)
-    if obs.shape != (ind.shape[0], plan.d):
-        raise ValueError(f"obs_data must have shape (n_obs, {plan.d})")
-    if ind.size and (ind.min() < 0 or ind.max() > plan.N):
-        raise ValueError("obs_ind outside the solver grid")
+    obs, ind = check_obs(obs_data, obs_ind, plan.d, plan.N)
     cache = plan.__dict__.setdefault("_logpost_cache", {})
     sig = (obs.shape, obs.tobytes(), ind.tobytes())
     if cache.get("sig") != sig:
@@ -124,6 +138,13 @@ def sim_logpost(plan, key, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10.
     upload between sampler and reduction left the GPU idle for 30 of C4's 275 us per evaluation); on the n_bstate = 3 tile
     path the backward sampler reduces the log-posterior itself and, unless ``keep_path``, stores no path at all.
     Returns a DeviceArray (B,) from a ring of four buffers owned by the plan (overwritten by the fourth call after this one).
+
+    ``obs_ind`` may come in any order, as in the reference's ``Xt[obs_ind]``: unsorted indices are sorted here (stably, rows of
+    ``obs_data`` carried along, ``check_obs``) before they are cached and uploaded, because the fused sampler needs them
+    ascending -- the C entry ``rk_solve_sim_logpost`` REQUIRES ascending indices on that route (include/rodeo_kalman.h).
+    A path-less call (the fused route without ``keep_path``) invalidates ``plan.x_state``: the path an earlier ``plan.sim``
+    left there is not this draw's, so ``plan.x_host()`` and ``gauss_obs_logpost(plan, ..., which="x" / "auto")`` raise
+    ``RuntimeError`` until a ``plan.sim`` or a ``sim_logpost(..., keep_path=True)`` has written a path again.
     """
     from ..solve import _seed
     dev = plan.dev
@@ -148,6 +169,7 @@ def sim_logpost(plan, key, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10.
     plan.cfg.seed = _seed(key)
     so = plan._out
     if fused and not keep_path:
+        plan._x_generation = None          # this launch writes no path: what x_state holds (if anything) is an earlier draw's
         so = _lib.SolveOut(workspace=so.workspace, workspace_bytes=so.workspace_bytes, mean_state=so.mean_state,
                            var_state=so.var_state, mean_pred=so.mean_pred, var_pred=so.var_pred, x_state=None)
     _lib.check(dev.lib.rk_solve_sim_logpost(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(so), d_obs.ptr, d_ind.ptr,

@@ -155,6 +155,7 @@ class SolvePlan:
         self.mean_state = self.var_state = self.mean_pred = self.var_pred = self.x_state = None
         self._out = _lib.SolveOut()
         self.generation = 0                # bumped by every launch and every update(): lazily read results check it
+        self._x_generation = None          # generation of the launch that last wrote x_state; None: the last sampler stored no path
 
     def update(self, ode_init=None, prior_pars=None, **params):
         """
@@ -205,6 +206,8 @@ class SolvePlan:
                 self.mean_pred, self.var_pred = dev.empty((N1, d, p, B)), dev.empty((N1, d, p, p, B))
         if mode == _lib.MODE_SIM and self.x_state is None and not getattr(self, "_no_path", False):
             self.x_state = dev.empty((N1, d, p, B))
+        if mode == _lib.MODE_SIM:          # (inference.sim_logpost resets this to None where its sampler stores no path)
+            self._x_generation = self.generation if self.x_state is not None else None
         wsb = C.c_size_t(0)
         _lib.check(self.dev.lib.rk_solve_workspace_bytes(C.byref(self.cfg), mode, C.byref(wsb)))
         if wsb.value and (self._ws is None or self._ws.nbytes < wsb.value):
@@ -276,7 +279,15 @@ class SolvePlan:
             return (mean, var) if self.batched else (mean[0], var[0])
         return self._host(self.mean_pred), self._host(self.var_pred)
 
+    def _require_path(self):
+        """x_state must hold the path of the last sampler launch (sim(), dalton's solve_sim, sim_logpost with a path)."""
+        if self.x_state is None or self._x_generation is None:
+            raise RuntimeError("this plan holds no path of its last sampler launch: a path-less sim_logpost stores none, "
+                               "and what an earlier sim() left in x_state belongs to another draw; call sim(key) or "
+                               "sim_logpost(..., keep_path=True) before reading the path")
+
     def x_host(self):
+        self._require_path()
         return self._host(self.x_state)
 
     # algorithmic HBM bytes per trajectory-step (SURVEY.md section 8d)
