@@ -30,52 +30,23 @@ import hashlib
 import os
 import numpy as np
 from .. import _lib
-from ..solve import (cached_plan, check_prior_at, eval_at_nodes, _device_ode, _interrogate_id, _prior_at_pair, _seed, _shape_rule)
-from .fenrir import _check_obs
+from ..solve import cached_plan
+from ._obs import _at_inputs, _at_layout, _refuse_config, _served, _stage_at  # noqa: F401  (_at_layout: importable here as before)
 from .logpost import obs_index
 
-
-def _served(who, ode_weight, interrogate, kalman_type, obs_data, obs_weight, obs_var):
-    """What this build does not serve, whatever the observation times; returns (obs, D, Omega, n_bobs)."""
-    if kalman_type == "square-root":
-        raise NotImplementedError(f"{who}: the square-root form is not built on the device (kalman_type='standard' only)")
-    if kalman_type != "standard":
-        raise NotImplementedError                                   # dalton.py:83-88
-    itg, _ = _interrogate_id(interrogate)
-    if itg == _lib.INTERROGATE_CHKREBTII:
-        raise NotImplementedError(f"{who}: interrogate_chkrebtii is not supported (rodeo, schober, kramer)")
-    W = np.shape(ode_weight)
-    if len(W) not in (3, 4):
-        raise ValueError("ode_weight must have shape (n_block, n_bmeas, n_bstate) [+ a leading batch axis]")
-    if W[-2] != 1:
-        raise NotImplementedError(f"{who} on the device: n_bmeas = 1 only (the dense / indep_init form is not served)")
-    if not 2 <= W[-1] <= 6:
-        raise NotImplementedError(f"{who} on the device: n_bstate in 2..6")
-    obs, D, Om, n_bobs = _check_obs(obs_data, obs_weight, obs_var)
-    if D.shape[1:] != (W[-3], n_bobs, W[-1]):
-        raise ValueError(f"obs_weight must have shape (n_obs, {W[-3]}, n_bobs, {W[-1]})")
-    return obs, D, Om, n_bobs
+_BMEAS = " (the dense / indep_init form is not served)"             # what dalton / dalton_at add to "n_bmeas = 1 only"
 
 
 def _refusals(ode_weight, interrogate, kalman_type, obs_data, obs_weight, obs_var, t_min, t_max, n_steps, obs_times):
     """Everything this build does not serve, raised before any device work; returns (obs, D, Omega, n_bobs, obs_ind)."""
-    obs, D, Om, n_bobs = _served("dalton", ode_weight, interrogate, kalman_type, obs_data, obs_weight, obs_var)
+    obs, D, Om, n_bobs = _served("dalton", ode_weight, kalman_type, obs_data, obs_weight, obs_var, interrogate=interrogate,
+                                 bmeas=_BMEAS)
     ind = obs_index(t_min, t_max, n_steps, obs_times)
     on_grid = ind[ind <= int(n_steps)]                              # (later times never match, here or in the reference)
     if np.any(np.diff(ind) < 0) or np.any(np.diff(on_grid) == 0):
         raise ValueError("dalton: the observations' grid indices must be strictly increasing (one observation per grid "
                          "point, in time order)")
     return obs, D, Om, n_bobs, ind
-
-
-def _obs_on_device(plan, obs, D, Om, ind):
-    """The observations uploaded once per plan and reused while they do not change (a sampler calls dalton in a loop)."""
-    cache = plan.__dict__.setdefault("_dalton_obs", {})
-    sig = (obs.tobytes(), D.tobytes(), Om.tobytes(), ind.tobytes())
-    if cache.get("sig") != sig:
-        cache["sig"] = sig
-        cache["dev"] = tuple(plan.dev.to_device(np.ascontiguousarray(a)) for a in (obs, D, Om, ind.astype(np.int32)))
-    return cache["dev"]
 
 
 def _plan(args, params, mode, n_bobs):
@@ -104,30 +75,24 @@ def dalton(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogat
 
 def _loglik_on_grid(plan, key, obs, D, Om, n_bobs, ind):
     """rk_dalton_loglik on `plan` with the observations at the grid indices `ind`."""
-    d_obs, d_w, d_v, d_ind = _obs_on_device(plan, obs, D, Om, ind)
-    plan.cfg.seed = _seed(key)
+    d_obs, d_w, d_v, d_ind = plan.staged("dalton", obs, D, Om, ind)
+    plan.set_seed(key)
     out = plan.dev.empty((plan.B,))
     _lib.check(plan.dev.lib.rk_dalton_loglik(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), d_obs.ptr, d_w.ptr, d_v.ptr,
                                              d_ind.ptr, int(ind.shape[0]), n_bobs, out.ptr))
-    ll = out.to_host()
-    return ll if plan.batched else float(ll[0])
+    return plan.per_traj(out)
 
 
 def _solve(mode, key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
            obs_data, obs_times, obs_weight, obs_var, kalman_type, params):
     """The joint filter + the solver's backward pass for `mode`, on a cached plan whose layout is the one rk_dalton_solve
-    writes; the launch goes through the plan's own bookkeeping (generation, layout, last_mode)."""
+    writes; the launch goes through the plan's own bookkeeping (``SolvePlan.launch``)."""
     obs, D, Om, n_bobs, ind = _refusals(ode_weight, interrogate, kalman_type, obs_data, obs_weight, obs_var, t_min, t_max,
                                         n_steps, obs_times)
     plan = _plan((ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type), params, mode,
                  n_bobs)
-    d_obs, d_w, d_v, d_ind = _obs_on_device(plan, obs, D, Om, ind)
-    plan.generation += 1               # whatever is in the output buffers now belongs to an earlier call
-    plan._prepare_out(mode)
-    plan.last_mode = mode
-    plan.cfg.seed = _seed(key)
-    _lib.check(plan.dev.lib.rk_dalton_solve(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out), mode,
-                                            d_obs.ptr, d_w.ptr, d_v.ptr, d_ind.ptr, int(ind.shape[0]), n_bobs))
+    d_obs, d_w, d_v, d_ind = plan.staged("dalton", obs, D, Om, ind)
+    plan.launch(plan.dev.lib.rk_dalton_solve, key, mode, mode, d_obs.ptr, d_w.ptr, d_v.ptr, d_ind.ptr, int(ind.shape[0]), n_bobs)
     return plan
 
 
@@ -141,53 +106,6 @@ def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrog
 
 
 # --- observations between grid nodes (an addition) -----------------------------------------------
-
-def _compose(chain):
-    """(Q, R) of the sub-steps `chain` applied in order: Q = Q_k .. Q_1, R = Q_k R' Q_k^T + R_k."""
-    Qc, Rc = chain[0]
-    for Qk, Rk in chain[1:]:
-        Rc = np.matmul(np.matmul(Qk, Rc), np.swapaxes(Qk, -1, -2)) + Rk
-        Qc = np.matmul(Qk, Qc)
-    return Qc, Rc
-
-
-def _at_layout(times, t_min, t_max, n_steps, prior_at, prior_pars, d, p, B, who="dalton_at"):
-    """
-    Where the observation times sit on the grid and the sub-step priors they need, checked on the host: returns
-    ``(table (n_obs, 4) int32, pre, post)`` with table rows (node, off-grid flag, pre slot, post slot or -1) and ``pre`` /
-    ``post`` lists of (Q, R) pairs (empty when every time is a node: ``prior_at`` is then never called).  Each interval's
-    chain of sub-steps must compose to ``prior_pars`` (Chapman-Kolmogorov, ``check_prior_at``'s bar).  ``who`` names the caller
-    in the messages (``fenrir.fenrir_at`` shares this builder).
-    """
-    t = np.asarray(times, dtype=np.float64)
-    if t.ndim != 1 or t.size == 0:
-        raise ValueError(f"{who}: obs_times must be a non-empty 1-D array, got shape {t.shape}")
-    if not np.all(np.isfinite(t)):
-        raise ValueError(f"{who}: obs_times holds a non-finite time")
-    if np.any(np.diff(t) <= 0):
-        raise ValueError(f"{who}: obs_times must be strictly increasing")
-    if t[0] < t_min or t[-1] > t_max:
-        raise ValueError(f"{who}: obs_times must lie in [t_min, t_max] = [{t_min}, {t_max}], got [{t[0]}, {t[-1]}]")
-    node, on, _, _ = eval_at_nodes(t, t_min, t_max, n_steps)
-    if np.any(np.diff(node[on]) == 0):
-        raise ValueError(f"{who}: two observation times are the same grid node (within EVAL_AT_NODE_TOL of a step)")
-    N = int(n_steps)
-    table = np.zeros((len(t), 4), dtype=np.int32)
-    table[:, 0], table[:, 1], table[:, 3] = node, ~on, -1
-    pre, post = [], []
-    for n in np.unique(node[~on]):
-        members = np.nonzero(~on & (node == n))[0]
-        left, right = t_min + (t_max - t_min) * n / N, t_min + (t_max - t_min) * (n + 1) / N
-        events = np.concatenate([[left], t[members], [right]])
-        gaps = np.diff(events)
-        chain = [_prior_at_pair(prior_at, h, d, p, B) for h in gaps]
-        check_prior_at(_compose(chain[:-1]), chain[-1], prior_pars, float(events[-2] - left), float(gaps[-1]))
-        table[members, 2] = len(pre) + np.arange(len(members))
-        table[members[-1], 3] = len(post)
-        pre.extend(chain[:-1])
-        post.append(chain[-1])
-    return table, pre, post
-
 
 def dalton_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
               obs_data, obs_times, obs_weight, obs_var, prior_at, kalman_type="standard", **params):
@@ -206,51 +124,20 @@ def dalton_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interro
     priors of every such interval must compose to ``prior_pars`` (``check_prior_at``'s 1e-10 bar).  Served and refused as
     ``dalton``; all refusals come before any device work.
     """
-    obs, D, Om, n_bobs = _served("dalton_at", ode_weight, interrogate, kalman_type, obs_data, obs_weight, obs_var)
-    if not callable(prior_at):
-        raise TypeError("dalton_at: prior_at must be a callable prior_at(dt) -> (wgt_state, var_state)")
-    if np.shape(obs_times) != (obs.shape[0],):
-        raise ValueError(f"dalton_at: obs_times must have shape ({obs.shape[0]},), got {np.shape(obs_times)}")
-    _, _, Q, R, _, _, sizes = _shape_rule(_device_ode(ode_fun, ode_weight, params), ode_weight, ode_init, prior_pars, params)
-    B, pars = (sizes[0] if sizes else 1), (Q, R)
-    d, p = int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1])
-    table, pre, post = _at_layout(obs_times, t_min, t_max, n_steps, prior_at, pars, d, p, B)
+    obs, D, Om, n_bobs = _served("dalton_at", ode_weight, kalman_type, obs_data, obs_weight, obs_var, interrogate=interrogate,
+                                 bmeas=_BMEAS)
+    table, stacked, batched = _at_inputs("dalton_at", ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, prior_pars,
+                                         obs.shape[0], obs_times, prior_at, params)
     plan = _plan((ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type), params,
                  _lib.MODE_FILTER, n_bobs)
-    if not pre:                                                     # every time is a node: dalton itself, on those nodes
-        return _loglik_on_grid(plan, key, obs, D, Om, n_bobs, table[:, 0].copy())
-    (pre_q, pre_r), qb = _stack_pairs(pre, B)
-    (post_q, post_r), _ = _stack_pairs(post, B, force=qb)
-    cache = plan.__dict__.setdefault("_dalton_at_obs", {})
-    arrays = (obs, D, Om, table, pre_q, pre_r, post_q, post_r)
-    sig = tuple(a.tobytes() for a in arrays)
-    if cache.get("sig") != sig:
-        cache["sig"] = sig
-        cache["dev"] = tuple(plan.dev.to_device(np.ascontiguousarray(a)) for a in arrays)
-    d_obs, d_w, d_v, d_tab, d_pq, d_pr, d_sq, d_sr = cache["dev"]
-    at = _lib.DaltonAtIn(table=d_tab.ptr, n_pre=len(pre), n_post=len(post), pre_trans=d_pq.ptr, pre_noise=d_pr.ptr,
-                         post_trans=d_sq.ptr, post_noise=d_sr.ptr, prior_batched=qb)
-    plan.cfg.seed = _seed(key)
+    if stacked is None:                                             # every time is a node: dalton itself, on those nodes
+        return _loglik_on_grid(plan, key, obs, D, Om, n_bobs, table[:, 0])
+    d_obs, d_w, d_v, at = _stage_at(plan, "dalton_at", obs, D, Om, table, stacked, batched)
+    plan.set_seed(key)
     out = plan.dev.empty((plan.B,))
     _lib.check(plan.dev.lib.rk_dalton_loglik_at(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), d_obs.ptr, d_w.ptr, d_v.ptr,
                                                 C.byref(at), int(table.shape[0]), n_bobs, out.ptr))
-    ll = out.to_host()
-    return ll if plan.batched else float(ll[0])
-
-
-def _stack_pairs(pairs, B, force=0):
-    """[(Q, R)] each (d, p, p) or (B, d, p, p) -> ((Qs, Rs), batched): (n, d, p, p), or (n, d, p, p, B) batch-minor when any
-    matrix is batched (``_stack_prior``'s rule: a batched sigma gives a batched R and a shared Q; both are then broadcast)."""
-    batched = int(bool(force) or any(m.ndim == 4 for pair in pairs for m in pair))
-    out = []
-    for k in (0, 1):
-        mats = [pair[k] for pair in pairs]
-        if batched:
-            full = np.array([np.broadcast_to(m, (B,) + m.shape[-3:]) for m in mats])              # (n, B, d, p, p)
-            out.append(np.ascontiguousarray(np.moveaxis(full, 1, -1)))
-        else:
-            out.append(np.ascontiguousarray(np.array(mats)))
-    return tuple(out), batched
+    return plan.per_traj(out)
 
 
 # --- non-Gaussian observations (src/rodeo/inference/dalton.py:547-1039) -------------------------------------------------
@@ -285,21 +172,8 @@ def _ng_refusals(ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_ti
                  params):
     """Everything this build does not serve, raised before any device work; returns (obs, obs_ind, traced model)."""
     from ..trace import trace_obs_source
-    if kalman_type == "square-root":
-        raise NotImplementedError("daltonng: the square-root form is not built on the device (kalman_type='standard' only)")
-    if kalman_type != "standard":
-        raise NotImplementedError                                   # dalton.py:884-889
-    itg, _ = _interrogate_id(interrogate)
-    if itg == _lib.INTERROGATE_CHKREBTII:
-        raise NotImplementedError("daltonng: interrogate_chkrebtii is not supported (rodeo, schober, kramer)")
-    W = np.shape(ode_weight)
-    if len(W) not in (3, 4):
-        raise ValueError("ode_weight must have shape (n_block, n_bmeas, n_bstate) [+ a leading batch axis]")
-    if W[-2] != 1:
-        raise NotImplementedError("daltonng on the device: n_bmeas = 1 only")
-    if not 2 <= W[-1] <= 6:
-        raise NotImplementedError("daltonng on the device: n_bstate in 2..6")
-    d, p = int(W[-3]), int(W[-1])
+    _refuse_config("daltonng", ode_weight, kalman_type, interrogate=interrogate, bmeas="")
+    d, p = int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1])
     if d >= 3 and p > 5:                                            # (daltonng.hip ng_check: the lane kernel spills)
         raise NotImplementedError("daltonng on the device: n_bstate up to 5 with three or more blocks")
     rid = getattr(ode_fun, "rhs_id", None)
@@ -345,16 +219,6 @@ def _ng_obs_id(model, d, p, n_ycols):
     return model["obs_id"]
 
 
-def _ng_obs_on_device(plan, obs, ind):
-    """The observations uploaded once per plan and reused while they do not change (a few kilobytes, as in _obs_on_device)."""
-    cache = plan.__dict__.setdefault("_daltonng_obs", {})
-    sig = (obs.tobytes(), ind.tobytes())
-    if cache.get("sig") != sig:
-        cache["sig"] = sig
-        cache["dev"] = (plan.dev.to_device(obs), plan.dev.to_device(np.ascontiguousarray(ind.astype(np.int32))))
-    return cache["dev"]
-
-
 def daltonng(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
              obs_data, obs_times, obs_loglik_i, kalman_type="standard", **params):
     """logy_x + logx_z - logx_yhat, the DALTON log-likelihood for non-Gaussian observations (dalton.py:851-949): a float, or
@@ -365,16 +229,15 @@ def daltonng(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrog
     plan = cached_plan(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type,
                        batch_minor=True, **params)
     oid = _ng_obs_id(model, plan.d, plan.p, obs.shape[2])
-    d_obs, d_ind = _ng_obs_on_device(plan, obs, ind)
+    d_obs, d_ind = plan.staged("daltonng", obs, ind)
     need = C.c_size_t(0)
     _lib.check(plan.dev.lib.rk_daltonng_workspace_bytes(C.byref(plan.cfg), int(ind.shape[0]), C.byref(need)))
     ws = plan.dev.empty((need.value // 8,))                         # two stored filters + the gain records: released on return
-    plan.cfg.seed = _seed(key)
+    plan.set_seed(key)
     out = plan.dev.empty((plan.B,))
     _lib.check(plan.dev.lib.rk_daltonng_loglik(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), oid, d_obs.ptr, d_ind.ptr,
                                                int(ind.shape[0]), ws.ptr, ws.nbytes, out.ptr))
-    ll = out.to_host()
-    return ll if plan.batched else float(ll[0])
+    return plan.per_traj(out)
 
 
 def solve_mv_nn(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
@@ -386,13 +249,8 @@ def solve_mv_nn(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, inter
     plan = cached_plan(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type,
                        batch_minor=True, **params)
     oid = _ng_obs_id(model, plan.d, plan.p, obs.shape[2])
-    d_obs, d_ind = _ng_obs_on_device(plan, obs, ind)
-    plan.generation += 1               # whatever is in the output buffers now belongs to an earlier call
-    plan._prepare_out(_lib.MODE_MV)
-    plan.last_mode = _lib.MODE_MV
-    plan.cfg.seed = _seed(key)
-    _lib.check(plan.dev.lib.rk_daltonng_solve(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out),
-                                              _lib.MODE_MV, oid, d_obs.ptr, d_ind.ptr, int(ind.shape[0])))
+    d_obs, d_ind = plan.staged("daltonng", obs, ind)
+    plan.launch(plan.dev.lib.rk_daltonng_solve, key, _lib.MODE_MV, _lib.MODE_MV, oid, d_obs.ptr, d_ind.ptr, int(ind.shape[0]))
     return plan.state_host()
 
 

@@ -21,7 +21,8 @@ import ctypes as C
 import os
 import numpy as np
 from .. import _lib
-from ..solve import cached_plan
+from ..solve import SolvePlan, cached_plan
+from ._obs import _at_inputs, _check_obs, _served, _stage_at
 from .logpost import obs_index
 
 
@@ -41,40 +42,23 @@ def fenrir(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogat
     return _backward_on_grid(plan, key, obs, D, Om, n_bobs, ind)
 
 
-def _backward_on_grid(plan, key, obs, D, Om, n_bobs, ind):
-    """The forward filter of `plan` and rk_fenrir_backward with the observations at the grid indices `ind`."""
+def _filter_and_stage(plan, key, obs, D, Om, n_bobs, ind):
+    """The forward filter of `plan`, then the observations at the grid indices `ind` on the device: they live on the plan and
+    are uploaded again only when they change (``SolvePlan.staged``; a sampler calls this once per step)."""
     if D.shape[1:] != (plan.d, n_bobs, plan.p):
         raise ValueError(f"obs_weight must have shape (n_obs, {plan.d}, n_bobs, {plan.p})")
     plan.filter(key)
+    return plan.staged("fenrir", obs, D, Om, ind)
+
+
+def _backward_on_grid(plan, key, obs, D, Om, n_bobs, ind):
+    """The forward filter of `plan` and rk_fenrir_backward with the observations at the grid indices `ind`."""
+    d_obs, d_w, d_v, d_ind = _filter_and_stage(plan, key, obs, D, Om, n_bobs, ind)
     dev = plan.dev
-    # observations live on the plan and are uploaded again only when they change (a sampler calls this once per step)
-    cache = plan.__dict__.setdefault("_fenrir_obs", {})
-    sig = (obs.tobytes(), D.tobytes(), Om.tobytes(), ind.tobytes())
-    if cache.get("sig") != sig:
-        cache["sig"] = sig
-        cache["dev"] = tuple(dev.to_device(np.ascontiguousarray(a)) for a in (obs, D, Om, ind.astype(np.int32)))
-    d_obs, d_w, d_v, d_ind = cache["dev"]
     out = dev.empty((plan.B,))
     _lib.check(dev.lib.rk_fenrir_backward(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out), d_obs.ptr,
                                           d_w.ptr, d_v.ptr, d_ind.ptr, int(ind.shape[0]), n_bobs, out.ptr))
-    ll = out.to_host()
-    return ll if plan.batched else float(ll[0])
-
-
-def _check_obs(obs_data, obs_weight, obs_var):
-    """(obs (n_obs, d, n_bobs), D (n_obs, d, n_bobs, p), Omega (n_obs, d, n_bobs, n_bobs), n_bobs) as contiguous float64."""
-    obs = np.ascontiguousarray(obs_data, dtype=np.float64)
-    D = np.ascontiguousarray(obs_weight, dtype=np.float64)
-    Om = np.ascontiguousarray(obs_var, dtype=np.float64)
-    if D.ndim != 4:
-        raise ValueError("fenrir: obs_weight must have shape (n_obs, n_block, n_bobs, n_bstate)")
-    n_bobs = D.shape[2]
-    if not 1 <= n_bobs <= 3:
-        raise NotImplementedError("fenrir on the device: n_bobs (observations per block) in 1..3")
-    if Om.shape != D.shape[:2] + (n_bobs, n_bobs) or obs.shape != D.shape[:2] + (n_bobs,):
-        raise ValueError("fenrir: obs_data (n_obs, n_block, n_bobs), obs_weight (n_obs, n_block, n_bobs, n_bstate), obs_var "
-                         "(n_obs, n_block, n_bobs, n_bobs)")
-    return obs, D, Om, n_bobs
+    return plan.per_traj(out)
 
 
 def _plan_for(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type, params,
@@ -119,54 +103,24 @@ def fenrir_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interro
     the lanes where the tiles serve).  The square-root form and n_bstate 7, 8 raise NotImplementedError.  All refusals come
     before any device work.
     """
-    from ..solve import _device_ode, _shape_rule
-    from .dalton import _at_layout, _stack_pairs                    # (dalton imports _check_obs from this module)
-    if kalman_type == "square-root":
-        raise NotImplementedError("fenrir_at: the square-root form is not built on the device (kalman_type='standard' only)")
-    if kalman_type != "standard":
-        raise NotImplementedError                                   # fenrir.py:293-298
-    W = np.shape(ode_weight)
-    if len(W) not in (3, 4):
-        raise ValueError("ode_weight must have shape (n_block, n_bmeas, n_bstate) [+ a leading batch axis]")
-    if not 2 <= W[-1] <= 6:
-        raise NotImplementedError(f"fenrir_at on the device: n_bstate in 2..6, got {W[-1]}")
-    obs, D, Om, n_bobs = _check_obs(obs_data, obs_weight, obs_var)
-    if D.shape[1:] != (W[-3], n_bobs, W[-1]):
-        raise ValueError(f"obs_weight must have shape (n_obs, {W[-3]}, n_bobs, {W[-1]})")
-    if not callable(prior_at):
-        raise TypeError("fenrir_at: prior_at must be a callable prior_at(dt) -> (wgt_state, var_state)")
-    if np.shape(obs_times) != (obs.shape[0],):
-        raise ValueError(f"fenrir_at: obs_times must have shape ({obs.shape[0]},), got {np.shape(obs_times)}")
-    _, _, Q, R, _, _, sizes = _shape_rule(_device_ode(ode_fun, ode_weight, params), ode_weight, ode_init, prior_pars, params)
-    B = sizes[0] if sizes else 1
-    d, p = int(W[-3]), int(W[-1])
-    table, pre, post = _at_layout(obs_times, t_min, t_max, n_steps, prior_at, (Q, R), d, p, B, who="fenrir_at")
+    obs, D, Om, n_bobs = _served("fenrir_at", ode_weight, kalman_type, obs_data, obs_weight, obs_var, got=True)
+    table, stacked, batched = _at_inputs("fenrir_at", ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, prior_pars,
+                                         obs.shape[0], obs_times, prior_at, params)
     args = (ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type, params)
-    if not pre:                                                     # every time is a node: fenrir itself, on those nodes
-        return _backward_on_grid(_plan_for(*args, tiles_ok=n_bobs == 1), key, obs, D, Om, n_bobs, table[:, 0].astype(np.int64))
+    if stacked is None:                                             # every time is a node: fenrir itself, on those nodes
+        return _backward_on_grid(_plan_for(*args, tiles_ok=n_bobs == 1), key, obs, D, Om, n_bobs, table[:, 0])
     lanes = os.environ.get("RK_FENRIR_AT_LANES", "0") not in ("", "0")
     plan = _plan_for(*args, tiles_ok=n_bobs == 1 and not lanes, tiles_blocked_ok=False)
-    (pre_q, pre_r), qb = _stack_pairs(pre, B)
-    (post_q, post_r), _ = _stack_pairs(post, B, force=qb)
     plan.filter(key)
     dev = plan.dev
-    cache = plan.__dict__.setdefault("_fenrir_at_obs", {})
-    arrays = (obs, D, Om, table, pre_q, pre_r, post_q, post_r)
-    sig = tuple(a.tobytes() for a in arrays)
-    if cache.get("sig") != sig:
-        cache["sig"] = sig
-        cache["dev"] = tuple(dev.to_device(np.ascontiguousarray(a)) for a in arrays)
-    d_obs, d_w, d_v, d_tab, d_pq, d_pr, d_sq, d_sr = cache["dev"]
-    at = _lib.DaltonAtIn(table=d_tab.ptr, n_pre=len(pre), n_post=len(post), pre_trans=d_pq.ptr, pre_noise=d_pr.ptr,
-                         post_trans=d_sq.ptr, post_noise=d_sr.ptr, prior_batched=qb)
+    d_obs, d_w, d_v, at = _stage_at(plan, "fenrir_at", obs, D, Om, table, stacked, batched)
     need = C.c_size_t(0)
-    _lib.check(dev.lib.rk_fenrir_at_workspace_bytes(C.byref(plan.cfg), n_bobs, len(pre) + len(post), C.byref(need)))
+    _lib.check(dev.lib.rk_fenrir_at_workspace_bytes(C.byref(plan.cfg), n_bobs, at.n_pre + at.n_post, C.byref(need)))
     ws = dev.empty((need.value // 8,))                              # the hop records: released on return
     out = dev.empty((plan.B,))
     _lib.check(dev.lib.rk_fenrir_backward_at(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out), d_obs.ptr, d_w.ptr,
                                              d_v.ptr, C.byref(at), int(table.shape[0]), n_bobs, ws.ptr, out.ptr))
-    ll = out.to_host()
-    return ll if plan.batched else float(ll[0])
+    return plan.per_traj(out)
 
 
 def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
@@ -176,6 +130,7 @@ def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrog
     p(X_{0:N} | Z_{1:N}, Y_{0:M}) -- forward filter, backward filter through the observations, smoothing pass over the
     backward filter (``_smooth_mv``, fenrir.py:333-402).  Same arguments as ``fenrir``; returns ``(mean (N+1, d, p), var
     (N+1, d, p, p))`` with a leading batch axis for batched inputs.  Lane-per-trajectory kernels (``rk_fenrir_solve_mv``).
+    On the blocked-tile route (a cached plan) the observations share ``fenrir``'s upload cache: uploaded when they change.
     """
     if kalman_type not in ("standard", "square-root"):
         raise NotImplementedError                                   # fenrir.py:421-426
@@ -183,7 +138,6 @@ def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrog
     ind = obs_index(t_min, t_max, n_steps, obs_times)
     if np.any(np.diff(ind) < 0):
         raise ValueError("obs_times must be ascending")
-    from ..solve import SolvePlan
     sq = kalman_type == "square-root"                               # (its forward pass is batch-minor and keeps no predictions)
     if not sq:
         # n_bstate = 4 .. 8: forward pass on the blocked MFMA tiles, backward filter and smoothing pass on its records
@@ -195,29 +149,26 @@ def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrog
             return _solve_mv_tiles(tplan, key, obs, D, Om, ind, n_bobs)
     plan = SolvePlan(ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type,
                      store_pred=not sq, batch_minor=not sq, **params)
-    if D.shape[1:] != (plan.d, n_bobs, plan.p):
-        raise ValueError(f"obs_weight must have shape (n_obs, {plan.d}, n_bobs, {plan.p})")
-    plan.filter(key)
+    (d_obs, d_w, d_v, d_ind), ws = _smoother_inputs(plan, key, obs, D, Om, n_bobs, ind)
     dev = plan.dev
-    d_obs, d_w, d_v, d_ind = (dev.to_device(np.ascontiguousarray(a)) for a in (obs, D, Om, ind.astype(np.int32)))
-    nbytes = C.c_size_t(0)
-    _lib.check(dev.lib.rk_fenrir_workspace_bytes(C.byref(plan.cfg), C.byref(nbytes)))
-    ws = dev.empty((nbytes.value // 8,))
     _lib.check(dev.lib.rk_fenrir_solve_mv(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out), d_obs.ptr,
                                           d_w.ptr, d_v.ptr, d_ind.ptr, int(ind.shape[0]), n_bobs, ws.ptr))
     return plan.state_host()
 
 
+def _smoother_inputs(plan, key, obs, D, Om, n_bobs, ind):
+    """What both routes of ``solve_mv`` do first: ``_filter_and_stage`` (the observations share ``fenrir``'s cache on a cached
+    plan, so a loop of calls uploads them once) and the workspace of rk_fenrir_workspace_bytes, released on return."""
+    staged = _filter_and_stage(plan, key, obs, D, Om, n_bobs, ind)
+    nbytes = C.c_size_t(0)
+    _lib.check(plan.dev.lib.rk_fenrir_workspace_bytes(C.byref(plan.cfg), C.byref(nbytes)))
+    return staged, plan.dev.empty((nbytes.value // 8,))
+
+
 def _solve_mv_tiles(plan, key, obs, D, Om, ind, n_bobs):
     """``solve_mv`` on a plan whose forward pass runs on the blocked tiles (n_bstate 4 .. 8)."""
-    if D.shape[1:] != (plan.d, n_bobs, plan.p):
-        raise ValueError(f"obs_weight must have shape (n_obs, {plan.d}, n_bobs, {plan.p})")
-    plan.filter(key)
+    (d_obs, d_w, d_v, d_ind), ws = _smoother_inputs(plan, key, obs, D, Om, n_bobs, ind)
     dev = plan.dev
-    d_obs, d_w, d_v, d_ind = (dev.to_device(np.ascontiguousarray(a)) for a in (obs, D, Om, ind.astype(np.int32)))
-    nbytes = C.c_size_t(0)
-    _lib.check(dev.lib.rk_fenrir_workspace_bytes(C.byref(plan.cfg), C.byref(nbytes)))
-    ws = dev.empty((nbytes.value // 8,))
     N, d, p, B = plan.cfg.n_steps, plan.d, plan.p, plan.cfg.n_traj
     mean, var = dev.empty((N + 1, d, p, B)), dev.empty((N + 1, d, p, p, B))
     _lib.check(dev.lib.rk_fenrir_solve_mv_tiles(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out), d_obs.ptr,

@@ -61,74 +61,39 @@ def gauss_obs_logpost(plan, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10
     else:
         layout = plan.layout
         state = plan.var_state if layout in TILE_LAYOUTS else plan.mean_state
-    # observations / indices / output live on the plan and are re-uploaded only when they change (a pseudo-marginal
-    # chain calls this once per step with the same data): per call one upload (upars) and one kernel
-    cache = plan.__dict__.setdefault("_logpost_cache", {})
-    sig = (obs.shape, obs.tobytes(), ind.tobytes())
-    if cache.get("sig") != sig:
-        cache["sig"], cache["obs"], cache["ind"] = sig, dev.to_device(obs), dev.to_device(ind)
-    d_obs, d_ind = cache["obs"], cache["ind"]
-    d_up, k = None, 0
-    if upars is not None:
-        up = np.asarray(upars, dtype=np.float64)
-        k = up.shape[1] if n_prior is None else int(n_prior)
-        upt = np.ascontiguousarray(up[:, :k].T)
-        d_up = cache.get("up")
-        if d_up is None or tuple(d_up.shape) != upt.shape:
-            d_up = cache["up"] = dev.to_device(upt)
-        else:
-            d_up.upload(upt)
-    # The result is a fresh device array unless the caller opts into `reuse_out`: then it comes from a ring of four buffers on
-    # the plan (a device allocation per call cost more than the kernel: 0.08 of C4's 0.32 ms per evaluation) and is
-    # overwritten by the FOURTH reusing call after it -- for callers that read the result at once (FitzLogPosterior, basic).
-    if reuse_out:
-        ring = cache.setdefault("out_ring", [])
-        if ring and tuple(ring[0].shape) != (plan.B,):
-            ring.clear()
-            cache["out_calls"] = 0
-        n_call = cache.get("out_calls", 0)
-        cache["out_calls"] = n_call + 1
-        if len(ring) < 4:
-            ring.append(dev.empty((plan.B,)))
-        out = ring[n_call % 4]                  # call 5 reuses the buffer of call 1, call 6 that of call 2, ...
-    else:
-        out = dev.empty((plan.B,))
+    # per call one upload (upars) and one kernel
+    d_obs, d_ind, d_up, k = _staged(plan, obs, ind, upars, n_prior)
+    # The result is a fresh device array unless the caller opts into `reuse_out`: then it comes from the plan's ring of four
+    # (``SolvePlan.result_ring``) -- for callers that read the result at once (FitzLogPosterior, basic).
+    out = plan.result_ring() if reuse_out else dev.empty((plan.B,))
     _lib.check(dev.lib.rk_gauss_obs_logpost(dev.h, plan.B, plan.N, plan.d, plan.p, layout, state.ptr, d_obs.ptr,
                                             d_ind.ptr, ind.shape[0], float(noise_sd),
                                             d_up.ptr if d_up is not None else None, k, float(prior_sd), out.ptr))
     return out
 
 
-def _staged(plan, obs_data, obs_ind, upars, n_prior):
-    """Device copies of the observations / indices (cached on the plan while unchanged) and of the transposed parameters."""
-    dev = plan.dev
-    obs, ind = check_obs(obs_data, obs_ind, plan.d, plan.N)
-    cache = plan.__dict__.setdefault("_logpost_cache", {})
-    sig = (obs.shape, obs.tobytes(), ind.tobytes())
-    if cache.get("sig") != sig:
-        cache["sig"], cache["obs"], cache["ind"] = sig, dev.to_device(obs), dev.to_device(ind)
+def _staged(plan, obs, ind, upars, n_prior):
+    """Device copies of the checked observations / indices (``SolvePlan.staged``: a pseudo-marginal chain calls once per step
+    with the same data) and of the transposed parameters: ``(d_obs, d_ind, d_upars or None, n_prior)``."""
+    d_obs, d_ind = plan.staged("logpost", obs, ind)
     d_up, k = None, 0
-    if upars is not None and hasattr(upars, "ptr"):           # already staged: a DeviceArray (n_prior, B) from stage_upars()
-        d_up, k = upars, int(upars.shape[0])
-    elif upars is not None:
-        d_up = stage_upars(plan, upars, n_prior)
+    if upars is not None:           # (a DeviceArray (n_prior, B) from stage_upars() is already staged)
+        d_up = upars if hasattr(upars, "ptr") else stage_upars(plan, upars, n_prior)
         k = int(d_up.shape[0])
-    return cache, cache["obs"], cache["ind"], ind.shape[0], d_up, k
+    return d_obs, d_ind, d_up, k
 
 
 def stage_upars(plan, upars, n_prior=None):
     """The first ``n_prior`` unconstrained parameters of every trajectory as a device array (n_prior, B), batch-minor: what the
     reduction reads.  Upload it together with the plan's other inputs (``SolvePlan.update``), BEFORE the kernels are launched."""
-    cache = plan.__dict__.setdefault("_logpost_cache", {})
     up = np.asarray(upars, dtype=np.float64)
     k = up.shape[1] if n_prior is None else int(n_prior)
     upt = np.ascontiguousarray(up[:, :k].T)
-    d_up = cache.get("up")
-    if d_up is None or tuple(d_up.shape) != upt.shape:
-        d_up = cache["up"] = plan.dev.to_device(upt)
+    if plan.upars_dev is None or tuple(plan.upars_dev.shape) != upt.shape:
+        plan.upars_dev = plan.dev.to_device(upt)
     else:
-        d_up.upload(upt)
-    return d_up
+        plan.upars_dev.upload(upt)                    # (they change with every call: one buffer, overwritten in place)
+    return plan.upars_dev
 
 
 def sim_logpost(plan, key, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10.0, n_prior=None, keep_path=False):
@@ -146,35 +111,13 @@ def sim_logpost(plan, key, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10.
     left there is not this draw's, so ``plan.x_host()`` and ``gauss_obs_logpost(plan, ..., which="x" / "auto")`` raise
     ``RuntimeError`` until a ``plan.sim`` or a ``sim_logpost(..., keep_path=True)`` has written a path again.
     """
-    from ..solve import _seed
-    dev = plan.dev
-    cache, d_obs, d_ind, n_obs, d_up, k = _staged(plan, obs_data, obs_ind, upars, n_prior)
-    ring = cache.setdefault("out_ring", [])
-    if ring and tuple(ring[0].shape) != (plan.B,):
-        ring.clear()
-        cache["out_calls"] = 0
-    n_call = cache.get("out_calls", 0)
-    cache["out_calls"] = n_call + 1
-    if len(ring) < 4:
-        ring.append(dev.empty((plan.B,)))
-    out = ring[n_call % 4]
-    fused = _fused_supported(plan, n_obs)
-    plan._no_path = fused and not keep_path and plan.x_state is None
-    try:
-        plan.generation += 1
-        plan._prepare_out(_lib.MODE_SIM)
-    finally:
-        plan._no_path = False
-    plan.last_mode = _lib.MODE_SIM
-    plan.cfg.seed = _seed(key)
-    so = plan._out
-    if fused and not keep_path:
-        plan._x_generation = None          # this launch writes no path: what x_state holds (if anything) is an earlier draw's
-        so = _lib.SolveOut(workspace=so.workspace, workspace_bytes=so.workspace_bytes, mean_state=so.mean_state,
-                           var_state=so.var_state, mean_pred=so.mean_pred, var_pred=so.var_pred, x_state=None)
-    _lib.check(dev.lib.rk_solve_sim_logpost(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(so), d_obs.ptr, d_ind.ptr,
-                                            n_obs, float(noise_sd), d_up.ptr if d_up is not None else None, k,
-                                            float(prior_sd), out.ptr))
+    obs, ind = check_obs(obs_data, obs_ind, plan.d, plan.N)
+    d_obs, d_ind, d_up, k = _staged(plan, obs, ind, upars, n_prior)
+    n_obs, out = ind.shape[0], plan.result_ring()
+    # the fused sampler stores no path unless asked to: the launch then neither allocates nor writes x_state
+    plan.launch(plan.dev.lib.rk_solve_sim_logpost, key, _lib.MODE_SIM, d_obs.ptr, d_ind.ptr, n_obs, float(noise_sd),
+                d_up.ptr if d_up is not None else None, k, float(prior_sd), out.ptr,
+                path=keep_path or not _fused_supported(plan, n_obs))
     return out
 
 

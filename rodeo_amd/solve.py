@@ -78,7 +78,7 @@ def _device_ode(ode_fun, ode_weight, params):
 def _shape_rule(ode_fun, ode_weight, ode_init, prior_pars, params):
     """
     The shape and batch-size rule of a solver call, on the host and in one place (``SolvePlan``, ``solve_mv_at``,
-    ``inference.dalton.dalton_at``): ``ode_fun`` is a ``DeviceODE``; returns ``(W, x0, Q, R, theta, Bt, sizes)`` with the arrays
+    ``dalton_at`` / ``fenrir_at``): ``ode_fun`` is a ``DeviceODE``; returns ``(W, x0, Q, R, theta, Bt, sizes)`` with the arrays
     as float64, ``(theta, Bt)`` from ``pack_params(params)`` and ``sizes`` the leading batch sizes found (empty: unbatched).
     """
     W = np.asarray(ode_weight, dtype=np.float64)
@@ -156,6 +156,9 @@ class SolvePlan:
         self._out = _lib.SolveOut()
         self.generation = 0                # bumped by every launch and every update(): lazily read results check it
         self._x_generation = None          # generation of the launch that last wrote x_state; None: the last sampler stored no path
+        self._staged = {}                  # slot -> (signature, device arrays) of staged()
+        self._ring, self._ring_calls = [], 0     # result_ring()
+        self.upars_dev = None              # inference.stage_upars: the unconstrained parameters the log-posterior reads
 
     def update(self, ode_init=None, prior_pars=None, **params):
         """
@@ -176,8 +179,9 @@ class SolvePlan:
                 raise TypeError("this ODE has no parameters")
             self._theta.upload(_bm(theta, Bt is not None))
 
-    def _prepare_out(self, mode):
-        """Ask the library which layout this call uses and (once) allocate the outputs for it."""
+    def _prepare_out(self, mode, path=True):
+        """Ask the library which layout this call uses and (once) allocate the outputs for it.  ``path=False``: a sampler launch
+        that stores no path -- x_state is neither allocated nor handed to the library, and the plan holds no path afterwards."""
         lay = C.c_int32(0)
         _lib.check(self.dev.lib.rk_solve_layout(C.byref(self.cfg), mode, C.byref(lay)))
         lay = lay.value
@@ -204,10 +208,10 @@ class SolvePlan:
                 self.mean_pred, self.var_pred = dev.empty((B, N1, d, p)), dev.empty((B, N1, d, p, p))
             else:
                 self.mean_pred, self.var_pred = dev.empty((N1, d, p, B)), dev.empty((N1, d, p, p, B))
-        if mode == _lib.MODE_SIM and self.x_state is None and not getattr(self, "_no_path", False):
-            self.x_state = dev.empty((N1, d, p, B))
-        if mode == _lib.MODE_SIM:          # (inference.sim_logpost resets this to None where its sampler stores no path)
-            self._x_generation = self.generation if self.x_state is not None else None
+        if mode == _lib.MODE_SIM:
+            if path and self.x_state is None:
+                self.x_state = dev.empty((N1, d, p, B))
+            self._x_generation = self.generation if path else None     # (no path: what x_state holds is an earlier draw's)
         wsb = C.c_size_t(0)
         _lib.check(self.dev.lib.rk_solve_workspace_bytes(C.byref(self.cfg), mode, C.byref(wsb)))
         if wsb.value and (self._ws is None or self._ws.nbytes < wsb.value):
@@ -228,27 +232,60 @@ class SolvePlan:
             mean_state=self.mean_state.ptr if self.mean_state is not None else None, var_state=self.var_state.ptr,
             mean_pred=self.mean_pred.ptr if self.mean_pred is not None else None,
             var_pred=self.var_pred.ptr if self.var_pred is not None else None,
-            x_state=self.x_state.ptr if self.x_state is not None else None)
+            x_state=self.x_state.ptr if path and self.x_state is not None else None)
 
     # ---- launches (asynchronous) ----
-    def _call(self, fn, key, mode):
+    def launch(self, fn, key, mode, *extra, path=True):
+        """The one way a library entry writes this plan's outputs: ``fn(handle, cfg, in, out, *extra)`` after the bookkeeping
+        every such launch owes -- generation, outputs of ``mode``'s layout, last_mode, seed.  ``path=False``: see _prepare_out."""
         self.generation += 1               # whatever is in the output buffers now belongs to an earlier call
-        self._prepare_out(mode)
+        self._prepare_out(mode, path)
         self.last_mode = mode
+        self.set_seed(key)
+        _lib.check(fn(self.dev.h, C.byref(self.cfg), C.byref(self.inp), C.byref(self._out), *extra))
+
+    def set_seed(self, key):
+        """The seed of the next launch -- all that an entry which leaves the plan's outputs alone (dalton, daltonng) sets."""
         self.cfg.seed = _seed(key)
-        _lib.check(fn(self.dev.h, C.byref(self.cfg), C.byref(self.inp), C.byref(self._out)))
 
     def filter(self, key=None):
-        self._call(self.dev.lib.rk_solve_filter, key, _lib.MODE_FILTER)
+        self.launch(self.dev.lib.rk_solve_filter, key, _lib.MODE_FILTER)
 
     def mv(self, key=None):
-        self._call(self.dev.lib.rk_solve_mv, key, _lib.MODE_MV)
+        self.launch(self.dev.lib.rk_solve_mv, key, _lib.MODE_MV)
 
     def sim(self, key=None):
-        self._call(self.dev.lib.rk_solve_sim, key, _lib.MODE_SIM)
+        self.launch(self.dev.lib.rk_solve_sim, key, _lib.MODE_SIM)
 
     def sync(self):
         self.dev.sync()
+
+    # ---- staging for the inference callers (observations in, a few doubles per trajectory out) ----
+    def staged(self, slot, *arrays):
+        """Device copies of ``arrays`` (made C-contiguous), uploaded again only when a shape or a byte differs from the last call
+        with this ``slot``: a sampler calls with the same observations once per step.  One slot per caller, so callers that
+        alternate on one cached plan do not evict each other."""
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        sig = tuple((a.shape, a.tobytes()) for a in arrays)
+        if self._staged.get(slot, (None,))[0] != sig:
+            self._staged[slot] = (sig, tuple(self.dev.to_device(a) for a in arrays))
+        return self._staged[slot][1]
+
+    def result_ring(self):
+        """The next of four (B,) result buffers owned by the plan (a device allocation per call cost more than the reduction
+        kernel: 0.08 of C4's 0.32 ms per evaluation): overwritten by the FOURTH call after this one, so for callers that read
+        the result at once.  A change of B starts a new ring."""
+        if self._ring and tuple(self._ring[0].shape) != (self.B,):
+            self._ring, self._ring_calls = [], 0
+        if len(self._ring) < 4:
+            self._ring.append(self.dev.empty((self.B,)))
+        self._ring_calls += 1
+        return self._ring[(self._ring_calls - 1) % 4]     # call 5 reuses the buffer of call 1, call 6 that of call 2, ...
+
+    def per_traj(self, out):
+        """A device array (B,) of per-trajectory values on the host: the array for a batched plan, else a float."""
+        vals = out.to_host()
+        return vals if self.batched else float(vals[0])
 
     # ---- results in the reference's layouts ----
     def _host(self, arr):

@@ -138,8 +138,7 @@ def test_fenrir_at_refusals_are_raised_without_a_device(monkeypatch):
 
 
 def test_the_shared_table_builder_keeps_dalton_at_s_texts():
-    import rodeo_amd.inference.dalton  # noqa: F401
-    dmod = sys.modules["rodeo_amd.inference.dalton"]
+    from rodeo_amd.inference import _obs as dmod
     with pytest.raises(ValueError, match="dalton_at: obs_times must be strictly increasing"):
         dmod._at_layout(np.array([0.5, 0.2]), 0.0, 1.0, 10, None, None, 2, 3, 1)
     with pytest.raises(ValueError, match="fenrir_at: obs_times must be strictly increasing"):
