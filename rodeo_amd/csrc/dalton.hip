@@ -16,11 +16,6 @@
 
 namespace rk {
 
-// largest n_bstate of the built-in instances: three blocks at n_bstate = 6 hold more state than a lane's registers
-// (the store form spilled over 2 KiB per lane), so Lorenz63 stops at 5
-template <class RHS>
-constexpr int dalton_pmax() { return RHS::D >= 3 ? 5 : 6; }
-
 // Is this configuration served?  RK_OK, or RK_ERR_UNSUPPORTED with the reason.
 static int dalton_check(const rk_solve_cfg* c, int n_bobs) {
     RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED,
@@ -70,11 +65,11 @@ static int launch_dalton_tile_rhs(rk_handle h, const rk_solve_cfg* c, const Solv
         set_error("dalton: rhs %d has no tile form", c->rhs_id);
         return RK_ERR_UNSUPPORTED;
     } else {
-        const dim3 grid(div_up((STORE ? a.B : 2 * a.B) * RHS::D, Tpw<RHS::D>::value)), block(64);
+        const LaunchGeom g = dalton_tile_geom(a.B, RHS::D, !STORE);
         bool ok = false;
         dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
             LaunchTimer t(h, STORE ? "dalton_fwd_tile3_kernel<store>" : "dalton_fwd_tile3_kernel<loglik>");
-            hipLaunchKernelGGL((dalton_fwd_tile3_kernel<RHS, I, STORE>), grid, block, 0, h->stream, a, o, out);
+            hipLaunchKernelGGL((dalton_fwd_tile3_kernel<RHS, I, STORE>), g.grid, g.block, 0, h->stream, a, o, out);
             t.stop();
             ok = true;
         });
@@ -88,13 +83,13 @@ static int launch_dalton_tile_rhs(rk_handle h, const rk_solve_cfg* c, const Solv
 template <class RHS, bool STORE>
 static int launch_dalton_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, int n_bobs,
                              double* logdens) {
-    const dim3 grid(div_up(a.B, STORE ? 64 : 32)), block(64);
+    const LaunchGeom g = dalton_lane_geom(a.B, !STORE);
     bool ok = false;
     dispatch_int<2, dalton_pmax<RHS>()>(c->n_bstate, [&](auto P) {
         dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
             dispatch_int<1, 3>(n_bobs, [&](auto M) {
                 LaunchTimer t(h, STORE ? "dalton_fwd_kernel<store>" : "dalton_fwd_kernel<loglik>");
-                hipLaunchKernelGGL((dalton_fwd_kernel<RHS, P, I, M, STORE>), grid, block, 0, h->stream, a, o, logdens);
+                hipLaunchKernelGGL((dalton_fwd_kernel<RHS, P, I, M, STORE>), g.grid, g.block, 0, h->stream, a, o, logdens);
                 t.stop();
                 ok = true;
             });
@@ -115,10 +110,9 @@ static int dalton_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a
     if (is_user_rhs(c->rhs_id)) return user_dalton(h, c, a, o, n_bobs, STORE, tile, out);
     with_builtin_rhs(c->rhs_id, [&](auto rhs) {
         using RHS = decltype(rhs);
-        if (c->n_theta != 0 && c->n_theta < RHS::NTHETA && a.theta) {
-            set_error("rhs %d needs %d parameters, got n_theta=%d", c->rhs_id, RHS::NTHETA, c->n_theta);
-            rc = RK_ERR_INVALID;
-        } else if (tile) {
+        rc = check_n_theta<RHS>(c, a);
+        if (rc) return;
+        if (tile) {
             rc = launch_dalton_tile_rhs<RHS, STORE>(h, c, a, o, out);
         } else {
             rc = launch_dalton_rhs<RHS, STORE>(h, c, a, o, n_bobs, out);

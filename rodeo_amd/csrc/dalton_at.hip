@@ -14,10 +14,6 @@
 
 namespace rk {
 
-// (dalton.hip's dalton_pmax: three blocks at n_bstate = 6 hold more state than a lane's registers)
-template <class RHS>
-constexpr int dalton_at_pmax() { return RHS::D >= 3 ? 5 : 6; }
-
 template <class RHS>
 static int launch_dalton_at_tile_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o,
                                      const DaltonAt& s, double* out) {
@@ -25,11 +21,11 @@ static int launch_dalton_at_tile_rhs(rk_handle h, const rk_solve_cfg* c, const S
         set_error("dalton_at: rhs %d has no tile form", c->rhs_id);
         return RK_ERR_UNSUPPORTED;
     } else {
-        const dim3 grid(div_up(2 * a.B * RHS::D, Tpw<RHS::D>::value)), block(64);
+        const LaunchGeom g = dalton_tile_geom(a.B, RHS::D, true);
         bool ok = false;
         dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
             LaunchTimer t(h, "dalton_fwd_at_tile3_kernel");
-            hipLaunchKernelGGL((dalton_fwd_at_tile3_kernel<RHS, I>), grid, block, 0, h->stream, a, o, s, out);
+            hipLaunchKernelGGL((dalton_fwd_at_tile3_kernel<RHS, I>), g.grid, g.block, 0, h->stream, a, o, s, out);
             t.stop();
             ok = true;
         });
@@ -42,13 +38,13 @@ static int launch_dalton_at_tile_rhs(rk_handle h, const rk_solve_cfg* c, const S
 template <class RHS>
 static int launch_dalton_at_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const DaltonAt& s,
                                 int n_bobs, double* logdens) {
-    const dim3 grid(div_up(a.B, 32)), block(64);
+    const LaunchGeom g = dalton_lane_geom(a.B, true);
     bool ok = false;
-    dispatch_int<2, dalton_at_pmax<RHS>()>(c->n_bstate, [&](auto P) {
+    dispatch_int<2, dalton_pmax<RHS>()>(c->n_bstate, [&](auto P) {
         dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
             dispatch_int<1, 3>(n_bobs, [&](auto M) {
                 LaunchTimer t(h, "dalton_fwd_at_kernel");
-                hipLaunchKernelGGL((dalton_fwd_at_kernel<RHS, P, I, M>), grid, block, 0, h->stream, a, o, s, logdens);
+                hipLaunchKernelGGL((dalton_fwd_at_kernel<RHS, P, I, M>), g.grid, g.block, 0, h->stream, a, o, s, logdens);
                 t.stop();
                 ok = true;
             });
@@ -100,10 +96,9 @@ int rk_dalton_loglik_at(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* i
     rc = RK_ERR_UNSUPPORTED;
     with_builtin_rhs(c->rhs_id, [&](auto rhs) {
         using RHS = decltype(rhs);
-        if (c->n_theta != 0 && c->n_theta < RHS::NTHETA && a.theta) {
-            set_error("rhs %d needs %d parameters, got n_theta=%d", c->rhs_id, RHS::NTHETA, c->n_theta);
-            rc = RK_ERR_INVALID;
-        } else if (tile) {
+        rc = check_n_theta<RHS>(c, a);
+        if (rc) return;
+        if (tile) {
             rc = launch_dalton_at_tile_rhs<RHS>(h, c, a, o, s, logdens);
         } else {
             rc = launch_dalton_at_rhs<RHS>(h, c, a, o, s, n_bobs, logdens);

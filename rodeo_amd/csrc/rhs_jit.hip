@@ -3,8 +3,9 @@
 // rodeo's `ode_fun` is an arbitrary Python callable evaluated inside the scan (src/rodeo/solve.py:70-78) and
 // differentiated by jax.jacfwd (src/rodeo/interrogate.py:76).  Here the time loop lives in one GPU kernel, so a new ODE
 // arrives as HIP source for a small struct (the interface of csrc/rhs.hpp, or a scalar-generic `rhs` wrapped by
-// rk::AutoJac of csrc/dual.hpp for the Jacobian) and the kernel templates of solve_small_kernels.hpp are
-// instantiated for it at run time, once per (n_bstate, interrogation) actually used.
+// rk::AutoJac of csrc/dual.hpp for the Jacobian) and the kernel templates are instantiated for it at run time, once per
+// JitKey actually used.  The observation models of DALTON's non-Gaussian form (rodeo_amd.trace.trace_obs_source) arrive the
+// same way; their kernels are built around EITHER kind of right-hand side, a built-in one named through the embedded rhs.hpp.
 #include <hip/hiprtc.h>
 #include <dlfcn.h>
 #include <link.h>
@@ -12,8 +13,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -32,10 +35,79 @@ struct UserRhs {
     int n_block, n_theta, n_bmeas;
 };
 
+struct UserObs {
+    std::string type_name, source;
+    int n_block, n_bstate, n_ycols, n_theta, n_active;
+};
+
+// The registries and the two caches below share one mutex.  It is never held through a hiprtc build (jit_lookup).
 static std::mutex g_mu;
-static std::vector<UserRhs> g_rhs;                                   // id = RK_RHS_USER_BASE + index
-struct JitEntry { hipModule_t mod; hipFunction_t fn; };
-static std::map<std::tuple<int, int, int, int, int>, JitEntry> g_cache;   // (device, rhs, P, itg, kind)
+static std::deque<UserRhs> g_rhs;                                    // id = RK_RHS_USER_BASE + index; entries never move or change
+static std::deque<UserObs> g_obs;                                    // id = index; likewise
+
+// One row per JitKind.  expr: the kernel's name expression, with {P} = n_bstate, {I} = interrogate, {M} = n_bobs, {NB} = the
+// blocked tile kernel's instance, {A} = the observation model's n_active; rk::UserRhsT / rk::UserObsT alias the user's types
+// inside the translation unit (they may be template-ids).  header: included by this kind only, so that the program text of
+// every other build stays what it was.  label: the launch's name in the profile (none: not bracketed).
+struct JitKindRow { const char *expr, *header, *label; };
+static const JitKindRow kJitKinds[JIT_N_KINDS] = {
+    /* JIT_FWD                */ {"rk::fwd_kernel<rk::UserRhsT, {P}, {I}, false>", nullptr, "fwd_kernel<user>"},
+    /* JIT_FWD_STORE_PRED     */ {"rk::fwd_kernel<rk::UserRhsT, {P}, {I}, true>", nullptr, "fwd_kernel<user>"},
+    /* JIT_ITG                */ {"rk::interrogate_kernel<rk::UserRhsT, {P}, {I}>", nullptr, nullptr},
+    /* JIT_TILE3              */ {"rk::fwd_tile3_kernel<rk::UserRhsT, {I}>", nullptr, "fwd_tile3_kernel<user>"},
+    /* JIT_TILE4              */ {"rk::fwd_tile4_kernel<rk::UserRhsT, {I}>", nullptr, "fwd_tile4_kernel<user>"},
+    /* JIT_TILEN              */ {"rk::fwd_tilen_kernel<rk::UserRhsT, {I}, {NB}>", nullptr, "fwd_tilen_kernel<user>"},
+    /* JIT_SQRT               */ {"rk::fwd_sqrt_kernel<rk::UserRhsT, {P}, {I}>", nullptr, "fwd_sqrt_kernel<user>"},
+    /* JIT_FWD_M              */ {"rk::fwd_kernel_m<rk::UserRhsT, {P}, {I}, false>", nullptr, "fwd_kernel<user>"},
+    /* JIT_FWD_M_STORE_PRED   */ {"rk::fwd_kernel_m<rk::UserRhsT, {P}, {I}, true>", nullptr, "fwd_kernel<user>"},
+    /* JIT_DENSE_ITG          */ {"rk::dense_interrogate_kernel<rk::UserRhsT::Inner, {P}, {I}>", nullptr, nullptr},
+    /* JIT_ITG_M              */ {"rk::interrogate_kernel_m<rk::UserRhsT, {P}, {I}>", nullptr, nullptr},
+    /* JIT_DALTON             */ {"rk::dalton_fwd_kernel<rk::UserRhsT, {P}, {I}, {M}, false>", "dalton_kernels.hpp", "dalton_fwd_kernel<loglik, user>"},
+    /* JIT_DALTON_STORE       */ {"rk::dalton_fwd_kernel<rk::UserRhsT, {P}, {I}, {M}, true>", "dalton_kernels.hpp", "dalton_fwd_kernel<store, user>"},
+    /* JIT_DALTON_TILE3       */ {"rk::dalton_fwd_tile3_kernel<rk::UserRhsT, {I}, false>", "dalton_tile3_kernels.hpp", "dalton_fwd_tile3_kernel<loglik, user>"},
+    /* JIT_DALTON_TILE3_STORE */ {"rk::dalton_fwd_tile3_kernel<rk::UserRhsT, {I}, true>", "dalton_tile3_kernels.hpp", "dalton_fwd_tile3_kernel<store, user>"},
+    /* JIT_DALTONNG           */ {"rk::daltonng_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, false>", "daltonng_kernels.hpp", "daltonng_fwd_kernel<store>"},
+    /* JIT_DALTONNG_BOTH      */ {"rk::daltonng_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, true>", "daltonng_kernels.hpp", "daltonng_fwd_kernel<both>"},
+    /* JIT_DALTONNG_OBS       */ {"rk::daltonng_obs_kernel<rk::UserObsT>", "daltonng_kernels.hpp", "daltonng_obs_kernel"},
+    /* JIT_DALTON_AT          */ {"rk::dalton_fwd_at_kernel<rk::UserRhsT, {P}, {I}, {M}>", "dalton_at_kernels.hpp", "dalton_fwd_at_kernel<user>"},
+    /* JIT_DALTON_AT_TILE3    */ {"rk::dalton_fwd_at_tile3_kernel<rk::UserRhsT, {I}>", "dalton_at_tile3_kernels.hpp", "dalton_fwd_at_tile3_kernel<user>"},
+};
+
+// What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
+// model), so that configurations which share a kernel share its build.  device: -1 in the code map.
+struct JitKey {
+    int rhs, obs, n_bstate, n_bobs, nb, interrogate;
+    JitKind kind;
+    int device;
+    bool operator<(const JitKey& o) const {
+        return std::tie(rhs, obs, n_bstate, n_bobs, nb, interrogate, kind, device) <
+               std::tie(o.rhs, o.obs, o.n_bstate, o.n_bobs, o.nb, o.interrogate, o.kind, o.device);
+    }
+};
+
+// the key of `kind` for a configuration: which fields count is read off the kind's name expression
+static JitKey jit_key(JitKind kind, int rhs_id, const rk_solve_cfg* c, int n_bobs = 0, int obs_id = -1) {
+    const auto reads = [&](const char* tag) { return strstr(kJitKinds[kind].expr, tag) != nullptr; };
+    JitKey k;
+    k.rhs = reads("UserRhsT") ? rhs_id : 0;
+    k.obs = reads("UserObsT") ? obs_id : -1;
+    k.n_bstate = reads("{P}") ? c->n_bstate : 0;
+    k.n_bobs = reads("{M}") ? n_bobs : 0;
+    k.nb = reads("{NB}") ? (c->n_bstate <= 4 ? 1 : 2) : 0;             // solve_tilen_kernels.hpp: NB = 1 (p = 4) / 2 (p = 5 .. 8)
+    k.interrogate = reads("{I}") ? c->interrogate : 0;
+    k.kind = kind;
+    k.device = -1;
+    return k;
+}
+
+static std::string kernel_expr(const JitKey& k, int n_active) {
+    std::string s = kJitKinds[k.kind].expr;
+    const std::pair<const char*, int> fields[] = {{"{P}", k.n_bstate}, {"{I}", k.interrogate}, {"{M}", k.n_bobs},
+                                                  {"{NB}", k.nb}, {"{A}", n_active}};
+    for (const auto& f : fields)
+        for (size_t at; (at = s.find(f.first)) != std::string::npos;) s.replace(at, strlen(f.first), std::to_string(f.second));
+    return s;
+}
 
 // Are BOTH the libhiprtc behind hiprtcCompileProgram and the compiler library it drives (libamd_comgr) the ones under
 // /opt/rocm (the toolchain of this build)?  Evaluated at the first compilation, i.e. after whatever the process has loaded
@@ -72,49 +144,8 @@ static bool hiprtc_takes_backend_options() {
     return v != 0;
 }
 
-static std::string kernel_expr(const UserRhs& u, int P, int itg, JitKind kind) {
-    char buf[512];
-    (void)u;   // the user's type is aliased to rk::UserRhsT inside the translation unit (it may be a template-id)
-    if (kind == JIT_ITG) snprintf(buf, sizeof buf, "rk::interrogate_kernel<rk::UserRhsT, %d, %d>", P, itg);
-    else if (kind == JIT_ITG_M) snprintf(buf, sizeof buf, "rk::interrogate_kernel_m<rk::UserRhsT, %d, %d>", P, itg);   // standalone
-    else if (kind == JIT_TILE3) snprintf(buf, sizeof buf, "rk::fwd_tile3_kernel<rk::UserRhsT, %d>", itg);
-    else if (kind == JIT_TILE4) snprintf(buf, sizeof buf, "rk::fwd_tile4_kernel<rk::UserRhsT, %d>", itg);
-    else if (kind == JIT_FWD_M || kind == JIT_FWD_M_STORE_PRED)
-        snprintf(buf, sizeof buf, "rk::fwd_kernel_m<rk::UserRhsT, %d, %d, %s>", P, itg, kind == JIT_FWD_M_STORE_PRED ? "true" : "false");
-    else if (kind == JIT_SQRT) snprintf(buf, sizeof buf, "rk::fwd_sqrt_kernel<rk::UserRhsT, %d, %d>", P, itg);
-    else if (kind == JIT_DENSE_ITG) snprintf(buf, sizeof buf, "rk::dense_interrogate_kernel<rk::UserRhsT::Inner, %d, %d>", P, itg);
-    else if (kind == JIT_DALTON || kind == JIT_DALTON_STORE)      // P key = n_bstate + 16 n_bobs (user_dalton)
-        snprintf(buf, sizeof buf, "rk::dalton_fwd_kernel<rk::UserRhsT, %d, %d, %d, %s>", P % 16, itg, P / 16,
-                 kind == JIT_DALTON_STORE ? "true" : "false");
-    else if (kind == JIT_DALTON_TILE3 || kind == JIT_DALTON_TILE3_STORE)
-        snprintf(buf, sizeof buf, "rk::dalton_fwd_tile3_kernel<rk::UserRhsT, %d, %s>", itg, kind == JIT_DALTON_TILE3_STORE ? "true" : "false");
-    else if (kind == JIT_DALTON_AT)                               // P key = n_bstate + 16 n_bobs (user_dalton_at)
-        snprintf(buf, sizeof buf, "rk::dalton_fwd_at_kernel<rk::UserRhsT, %d, %d, %d>", P % 16, itg, P / 16);
-    else if (kind == JIT_DALTON_AT_TILE3) snprintf(buf, sizeof buf, "rk::dalton_fwd_at_tile3_kernel<rk::UserRhsT, %d>", itg);
-    else if (kind == JIT_TILEN) snprintf(buf, sizeof buf, "rk::fwd_tilen_kernel<rk::UserRhsT, %d, %d>", itg, P);  // P here = NB
-    else snprintf(buf, sizeof buf, "rk::fwd_kernel<rk::UserRhsT, %d, %d, %s>", P, itg, kind == JIT_FWD_STORE_PRED ? "true" : "false");
-    return buf;
-}
-
-static int jit_compile_src(const std::string& src, const std::string& expr, const std::string& what, std::vector<char>& code,
-                           std::string& lowered, const char* role = "user right-hand side");
-
-// compile one instantiation; returns code object in `code` and the mangled name in `lowered`
-static int jit_compile(const UserRhs& u, int P, int itg, JitKind kind, std::vector<char>& code, std::string& lowered) {
-    const std::string src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n"
-                                        "#include \"solve_tile3_kernels.hpp\"\n#include \"solve_tile4_kernels.hpp\"\n"
-                                        "#include \"solve_tilen_kernels.hpp\"\n#include \"solve_sqrt_kernels.hpp\"\n"
-                                        "#include \"solve_small_m_kernels.hpp\"\n#include \"solve_dense_itg_kernels.hpp\"\n") +
-                            // (only the DALTON kinds include its header: the source of every other build is unchanged)
-                            (kind == JIT_DALTON || kind == JIT_DALTON_STORE ? "#include \"dalton_kernels.hpp\"\n" : "") +
-                            (kind == JIT_DALTON_TILE3 || kind == JIT_DALTON_TILE3_STORE ? "#include \"dalton_tile3_kernels.hpp\"\n" : "") +
-                            (kind == JIT_DALTON_AT ? "#include \"dalton_at_kernels.hpp\"\n" : "") +
-                            (kind == JIT_DALTON_AT_TILE3 ? "#include \"dalton_at_tile3_kernels.hpp\"\n" : "") +
-                            "namespace rk {\n" + u.source + "\nusing UserRhsT = " + u.type_name + ";\n}  // namespace rk\n";
-    return jit_compile_src(src, kernel_expr(u, P, itg, kind), u.type_name, code, lowered);
-}
-
-// one hiprtc build of `src` for the kernel named by `expr`; `role` and `what` name the user's code in the error message
+// one hiprtc build of `src` for the kernel named by `expr`: the code object in `code`, the mangled name in `lowered`; `role` and
+// `what` name the user's code in the error message
 static int jit_compile_src(const std::string& src, const std::string& expr, const std::string& what, std::vector<char>& code,
                            std::string& lowered, const char* role) {
     hiprtcProgram prog;
@@ -157,233 +188,20 @@ static int jit_compile_src(const std::string& src, const std::string& expr, cons
     return RK_OK;
 }
 
-// compiled code objects, device independent: (rhs, P, itg, kind) -> (return code, code, lowered name).  A failed
-// compilation is remembered too (the tile kernels are tried first and simply do not exist for some right-hand sides).
-struct JitCode { int rc; std::vector<char> code; std::string lowered; std::string error; };
-static std::map<std::tuple<int, int, int, int>, JitCode> g_code;
-
-static const JitCode& jit_code_locked(int rhs_id, int P, int itg, JitKind kind) {
-    const auto key = std::make_tuple(rhs_id, P, itg, kind);
-    auto it = g_code.find(key);
-    if (it == g_code.end()) {
-        JitCode c;
-        c.rc = jit_compile(g_rhs[rhs_id - RK_RHS_USER_BASE], P, itg, kind, c.code, c.lowered);
-        if (c.rc) c.error = rk_last_error();
-        it = g_code.emplace(key, std::move(c)).first;
-    }
-    return it->second;
-}
-
-static int jit_get(rk_handle h, int rhs_id, int P, int itg, JitKind kind, hipFunction_t* fn) {
+// the registered right-hand side behind rhs_id, or the error (the entry is immutable: the pointer is good without the lock)
+static int user_rhs(int rhs_id, const UserRhs** u) {
     std::lock_guard<std::mutex> lk(g_mu);
     const int idx = rhs_id - RK_RHS_USER_BASE;
     RK_REQUIRE(idx >= 0 && idx < (int)g_rhs.size(), RK_ERR_INVALID, "unknown user rhs_id %d", rhs_id);
-    const auto key = std::make_tuple(h->device, rhs_id, P, itg, kind);
-    auto it = g_cache.find(key);
-    if (it == g_cache.end()) {
-        const JitCode& c = jit_code_locked(rhs_id, P, itg, kind);
-        if (c.rc) { set_error("%s", c.error.c_str()); return c.rc; }
-        JitEntry e;
-        RK_HIP(hipModuleLoadData(&e.mod, c.code.data()));
-        RK_HIP(hipModuleGetFunction(&e.fn, e.mod, c.lowered.c_str()));
-        if (getenv("RK_JIT_VERBOSE")) {                   // resources of the kernel hiprtc built (a spilled dual copy of a big system shows here)
-            int regs = 0, scratch = 0, lds = 0;
-            (void)hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, e.fn);
-            (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, e.fn);
-            (void)hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, e.fn);
-            fprintf(stderr, "[rk] jit kernel %s: %d registers, %d B scratch per lane, %d B LDS\n", c.lowered.c_str(), regs, scratch, lds);
-        }
-        it = g_cache.emplace(key, e).first;
-    }
-    *fn = it->second.fn;
+    *u = &g_rhs[idx];
     return RK_OK;
 }
-
-// The P key of a tile kernel's hiprtc build: the tile kind itself, or for the blocked tile kernel (solve_tilen_kernels.hpp)
-// its instance NB = 1 (p = 4) / 2 (p = 5 .. 8).
-static int tile_pkey(const rk_solve_cfg* c, JitKind tile) { return tile == JIT_TILEN ? (c->n_bstate <= 4 ? 1 : 2) : tile; }
-
-// Does the MFMA-tile forward kernel exist for this user right-hand side and configuration?  (It needs NDEP == 1 and a
-// block count the tile kernels support; decided by compiling it once -- cached -- so that rk_solve_layout and the
-// solve agree.)  tile = JIT_TILE3 / JIT_TILE4 for n_bstate = 3 / 4, JIT_TILEN for the blocked tiles.
-bool user_tile_available(const rk_solve_cfg* c, JitKind tile) {
+static int user_obs(int obs_id, const UserObs** u) {
     std::lock_guard<std::mutex> lk(g_mu);
-    const int idx = c->rhs_id - RK_RHS_USER_BASE;
-    if (idx < 0 || idx >= (int)g_rhs.size()) return false;
-    const int nb = g_rhs[idx].n_block;
-    if (c->n_block != nb || c->n_bmeas != 1 || g_rhs[idx].n_bmeas != 1 || c->kalman_type != RK_KALMAN_STANDARD) return false;
-    if (nb < 1 || nb > (tile == JIT_TILE4 ? 4 : 64)) return false;      // p = 3 and blocked tiles: up to 64 blocks (4 per wave, LDS exchange); p = 4: one wave
-    const JitCode& jc = jit_code_locked(c->rhs_id, tile_pkey(c, tile), c->interrogate, tile);
-    if (jc.rc && getenv("RK_JIT_VERBOSE")) fprintf(stderr, "[rk] tile kernel not available for user rhs %d (p = %d): %s\n", c->rhs_id, (int)tile, jc.error.c_str());
-    return jc.rc == RK_OK;
-}
-
-int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, JitKind tile) {
-    hipFunction_t fn;
-    int rc = jit_get(h, c->rhs_id, tile_pkey(c, tile), c->interrogate, tile, &fn);
-    if (rc) return rc;
-    SolveArgs args = a;
-    int P = c->n_bstate;
-    void* params[] = {&args, &tiles, &P};                           // (the p = 3 / p = 4 kernels take the first two)
-    const int tpw = c->n_block == 3 ? 3 : 4;
-    const int nw = c->n_block <= 4 ? 1 : (c->n_block + 3) / 4;     // waves per workgroup (TileWaves<D>)
-    const int grid = nw == 1 ? div_up(a.B * c->n_block, tpw) : a.B;
-    launch_placement_primer(h, dim3(grid), dim3(64 * nw));
-    LaunchTimer t(h, tile == JIT_TILE3 ? "fwd_tile3_kernel<user>" : (tile == JIT_TILE4 ? "fwd_tile4_kernel<user>" : "fwd_tilen_kernel<user>"));
-    RK_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, 64 * nw, 1, 1, 0, h->stream, params, nullptr));
-    t.stop();
+    RK_REQUIRE(obs_id >= 0 && obs_id < (int)g_obs.size(), RK_ERR_INVALID, "unknown obs_id %d", obs_id);
+    *u = &g_obs[obs_id];
     return RK_OK;
 }
-
-bool is_user_rhs(int rhs_id) { return rhs_id >= RK_RHS_USER_BASE; }
-
-int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        const int idx = c->rhs_id - RK_RHS_USER_BASE;
-        RK_REQUIRE(idx >= 0 && idx < (int)g_rhs.size(), RK_ERR_INVALID, "unknown user rhs_id %d", c->rhs_id);
-        RK_REQUIRE(c->n_block == g_rhs[idx].n_block && c->n_bmeas == 1 && g_rhs[idx].n_bmeas == 1, RK_ERR_UNSUPPORTED,
-                   "square-root solver: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, g_rhs[idx].n_block,
-                   c->n_block, c->n_bmeas);
-    }
-    hipFunction_t fn;
-    int rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, JIT_SQRT, &fn);
-    if (rc) return rc;
-    SolveArgs args = a;
-    void* params[] = {&args};
-    LaunchTimer t(h, "fwd_sqrt_kernel<user>");
-    RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, 64 / c->n_block), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));     // 64 / D trajectories per wave
-    t.stop();
-    return RK_OK;
-}
-
-int user_rhs_check(const rk_solve_cfg* c) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    const int idx = c->rhs_id - RK_RHS_USER_BASE;
-    RK_REQUIRE(idx >= 0 && idx < (int)g_rhs.size(), RK_ERR_INVALID, "unknown user rhs_id %d", c->rhs_id);
-    RK_REQUIRE(c->n_block == g_rhs[idx].n_block && c->n_bmeas == g_rhs[idx].n_bmeas, RK_ERR_UNSUPPORTED,
-               "user rhs %d needs n_block=%d, n_bmeas=%d (got %d, %d)", c->rhs_id, g_rhs[idx].n_block, g_rhs[idx].n_bmeas,
-               c->n_block, c->n_bmeas);
-    const int pmax = c->n_bmeas > 1 ? 9 : 6;                     // (the backward kernels exist up to n_bstate = 9)
-    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= pmax, RK_ERR_UNSUPPORTED, "lane-per-trajectory path supports n_bstate in [2, %d] "
-               "here, got %d", pmax, c->n_bstate);
-    RK_REQUIRE(c->n_bmeas <= c->n_bstate, RK_ERR_INVALID, "n_bmeas = %d exceeds n_bstate = %d", c->n_bmeas, c->n_bstate);
-    return RK_OK;
-}
-
-static int user_n_bmeas(int rhs_id) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    const int idx = rhs_id - RK_RHS_USER_BASE;
-    return idx >= 0 && idx < (int)g_rhs.size() ? g_rhs[idx].n_bmeas : 1;
-}
-
-// ---- dense ("non-block") path: the interrogation kernel around the user's right-hand side (solve_dense_itg_kernels.hpp)
-// Taken for one block with several measurements that the lane kernels do not serve (n_bstate > 9 or n_bmeas > 4).
-bool user_dense_wanted(const rk_solve_cfg* c) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    const int idx = c->rhs_id - RK_RHS_USER_BASE;
-    if (idx < 0 || idx >= (int)g_rhs.size()) return false;
-    const UserRhs& u = g_rhs[idx];
-    return u.n_block == 1 && c->n_block == 1 && u.n_bmeas > 1 && c->n_bmeas == u.n_bmeas && (c->n_bstate > 9 || c->n_bmeas > 4);
-}
-
-int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a) {
-    hipFunction_t fn;
-    int rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, JIT_DENSE_ITG, &fn);
-    if (rc) return rc;
-    DenseItgArgs args = a;
-    void* params[] = {&args};
-    RK_HIP(hipModuleLaunchKernel(fn, a.B, 1, 1, 256, 1, 1, 0, h->stream, params, nullptr));
-    return RK_OK;
-}
-
-int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
-    int rc = user_rhs_check(c);
-    if (rc) return rc;
-    hipFunction_t fn;
-    const bool sp = (c->flags & RK_FLAG_STORE_PRED) != 0;
-    rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, user_n_bmeas(c->rhs_id) > 1 ? (sp ? JIT_FWD_M_STORE_PRED : JIT_FWD_M) : (sp ? JIT_FWD_STORE_PRED : JIT_FWD), &fn);
-    if (rc) return rc;
-    SolveArgs args = a;
-    void* params[] = {&args};
-    LaunchTimer t(h, "fwd_kernel<user>");
-    RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, 64), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
-    t.stop();
-    return RK_OK;
-}
-
-// DALTON's forward filters around a user right-hand side.  Lanes (dalton_kernels.hpp): the log-likelihood form (32
-// trajectories per wave, joint and marginal filter in its two halves) or the joint filter's store form (64 per wave).
-// Tiles (dalton_tile3_kernels.hpp, n_bstate = 3, n_bobs = 1): 2 B or B filter instances of n_block tiles.
-int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, int n_bobs, bool store,
-                bool tile, double* out) {
-    int rc = user_rhs_check(c);
-    if (rc) return rc;
-    RK_REQUIRE(user_n_bmeas(c->rhs_id) == 1, RK_ERR_UNSUPPORTED, "dalton: n_bmeas = 1 only");
-    hipFunction_t fn;
-    if (tile) rc = jit_get(h, c->rhs_id, 3, c->interrogate, store ? JIT_DALTON_TILE3_STORE : JIT_DALTON_TILE3, &fn);
-    else rc = jit_get(h, c->rhs_id, c->n_bstate + 16 * n_bobs, c->interrogate, store ? JIT_DALTON_STORE : JIT_DALTON, &fn);
-    if (rc) return rc;
-    SolveArgs args = a;
-    const DaltonObs* op = &o;
-    void* params[] = {&args, (void*)op, &out};
-    const int grid = tile ? div_up((store ? a.B : 2 * a.B) * c->n_block, c->n_block == 3 ? 3 : 4) : div_up(a.B, store ? 64 : 32);
-    LaunchTimer t(h, tile ? (store ? "dalton_fwd_tile3_kernel<store, user>" : "dalton_fwd_tile3_kernel<loglik, user>")
-                          : (store ? "dalton_fwd_kernel<store, user>" : "dalton_fwd_kernel<loglik, user>"));
-    RK_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
-    t.stop();
-    return RK_OK;
-}
-
-// dalton_at's forward filters around a user right-hand side (dalton_at_kernels.hpp / dalton_at_tile3_kernels.hpp): the
-// log-likelihood form only, launched like user_dalton's.
-int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const DaltonAt& s, int n_bobs,
-                   bool tile, double* out) {
-    int rc = user_rhs_check(c);
-    if (rc) return rc;
-    RK_REQUIRE(user_n_bmeas(c->rhs_id) == 1, RK_ERR_UNSUPPORTED, "dalton_at: n_bmeas = 1 only");
-    hipFunction_t fn;
-    if (tile) rc = jit_get(h, c->rhs_id, 3, c->interrogate, JIT_DALTON_AT_TILE3, &fn);
-    else rc = jit_get(h, c->rhs_id, c->n_bstate + 16 * n_bobs, c->interrogate, JIT_DALTON_AT, &fn);
-    if (rc) return rc;
-    SolveArgs args = a;
-    const DaltonObs* op = &o;
-    const DaltonAt* sp = &s;
-    void* params[] = {&args, (void*)op, (void*)sp, &out};
-    const int grid = tile ? div_up(2 * a.B * c->n_block, c->n_block == 3 ? 3 : 4) : div_up(a.B, 32);
-    LaunchTimer t(h, tile ? "dalton_fwd_at_tile3_kernel<user>" : "dalton_fwd_at_kernel<user>");
-    RK_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
-    t.stop();
-    return RK_OK;
-}
-
-int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
-                     const double* vp, double* wm, double* mm_, double* vm) {
-    int rc = user_rhs_check(c);
-    if (rc) return rc;
-    const bool multi = c->n_bmeas > 1;                     // several measurements per block: interrogate_kernel_m
-    RK_REQUIRE(!multi || c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED,
-               "rk_interrogate_batched: n_bmeas > 1 with kalman_type = square-root is fused into the solvers only");
-    hipFunction_t fn;
-    rc = jit_get(h, c->rhs_id, c->n_bstate, c->interrogate, multi ? JIT_ITG_M : JIT_ITG, &fn);
-    if (rc) return rc;
-    SolveArgs args = a;
-    int sqrt_mode = c->kalman_type == RK_KALMAN_SQRT ? 1 : 0;
-    void* params[] = {&args, &t, &step, &mp, &vp, &wm, &mm_, &vm, &sqrt_mode};
-    RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, 64), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
-    return RK_OK;
-}
-
-// ---- DALTON for non-Gaussian observations (daltonng_kernels.hpp): the observation log-likelihood is always user code
-// (rodeo_amd.trace.trace_obs_source), so its forward filter is a hiprtc build around EITHER kind of right-hand side -- a
-// built-in one is named through the embedded rhs.hpp.
-struct UserObs {
-    std::string type_name, source;
-    int n_block, n_bstate, n_ycols, n_theta, n_active;
-};
-static std::vector<UserObs> g_obs;                                   // id = index
-static std::map<std::tuple<int, int, int, int, int>, JitCode> g_ng_code;        // (rhs, obs, P, itg, kind)
-static std::map<std::tuple<int, int, int, int, int, int>, JitEntry> g_ng_cache;  // (device, rhs, obs, P, itg, kind)
 
 static const char* builtin_rhs_type(int rhs_id) {
     switch (rhs_id) {
@@ -394,85 +212,233 @@ static const char* builtin_rhs_type(int rhs_id) {
     return nullptr;
 }
 
-int ng_obs_info(int obs_id, NgObsInfo* info) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    RK_REQUIRE(obs_id >= 0 && obs_id < (int)g_obs.size(), RK_ERR_INVALID, "unknown obs_id %d", obs_id);
-    const UserObs& u = g_obs[obs_id];
-    info->n_block = u.n_block; info->n_bstate = u.n_bstate; info->n_ycols = u.n_ycols; info->n_theta = u.n_theta;
-    info->n_active = u.n_active;
-    return RK_OK;
-}
+// Compiled code objects, device independent, and the modules loaded from them per device.  A failed compilation is
+// remembered with its message (the tile kernels are tried first and simply do not exist for some right-hand sides).
+struct JitCode { int rc; std::vector<char> code; std::string lowered; std::string error; };
+static std::map<JitKey, JitCode> g_code;                            // key.device = -1
+static std::map<JitKey, hipFunction_t> g_mod;                       // key.device = the handle's
 
-// the code object of one kernel around observation model obs_id (compiled once, failures remembered).  The source is put
-// together under the registry's lock and hiprtc runs outside it (as in rk_rhs_compile_check: a build takes seconds and must
-// not hold up registrations or other handles); two threads that miss at once both compile and the first result is kept.
-static int ng_code(int rhs_id, int obs_id, int P, int itg, JitKind kind, const JitCode** out) {
-    const auto ckey = std::make_tuple(rhs_id, obs_id, P, itg, (int)kind);
-    std::string src, name;
-    char expr[512];
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        RK_REQUIRE(obs_id >= 0 && obs_id < (int)g_obs.size(), RK_ERR_INVALID, "unknown obs_id %d", obs_id);
-        auto ci = g_ng_code.find(ckey);
-        if (ci != g_ng_code.end()) { *out = &ci->second; return RK_OK; }
-        const UserObs& ob = g_obs[obs_id];
-        src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n") +
-              (is_user_rhs(rhs_id) ? "" : "#include \"rhs.hpp\"\n") +        // (a user's names stay free)
-              "#include \"daltonng_kernels.hpp\"\nnamespace rk {\n";
-        if (kind == JIT_DALTONNG_OBS) {
-            snprintf(expr, sizeof expr, "rk::daltonng_obs_kernel<rk::UserObsT>");
-        } else {
-            if (is_user_rhs(rhs_id)) {
-                const int idx = rhs_id - RK_RHS_USER_BASE;
-                RK_REQUIRE(idx >= 0 && idx < (int)g_rhs.size(), RK_ERR_INVALID, "unknown user rhs_id %d", rhs_id);
-                src += g_rhs[idx].source + "\nusing UserRhsT = " + g_rhs[idx].type_name + ";\n";
-            } else {
-                const char* t = builtin_rhs_type(rhs_id);
-                RK_REQUIRE(t, RK_ERR_UNSUPPORTED, "daltonng: rhs %d has no lane-per-trajectory form", rhs_id);
-                src += std::string("using UserRhsT = ") + t + ";\n";
-            }
-            snprintf(expr, sizeof expr, "rk::daltonng_fwd_kernel<rk::UserRhsT, rk::UserObsT, %d, %d, %d, %s>", P, itg,
-                     ob.n_active, kind == JIT_DALTONNG_BOTH ? "true" : "false");
-        }
-        src += ob.source + "\nusing UserObsT = " + ob.type_name + ";\n}  // namespace rk\n";
-        name = ob.type_name;
-    }
-    JitCode c;
-    c.rc = jit_compile_src(src, expr, name, c.code, c.lowered, "observation log-likelihood");
-    if (c.rc) c.error = rk_last_error();
-    std::lock_guard<std::mutex> lk(g_mu);
-    *out = &g_ng_code.emplace(ckey, std::move(c)).first->second;      // (map nodes do not move: the pointer stays valid)
-    return RK_OK;
-}
-
-static int ng_jit_get(rk_handle h, int rhs_id, int obs_id, int P, int itg, JitKind kind, hipFunction_t* fn) {
-    if (kind == JIT_DALTONNG_OBS) rhs_id = 0;                         // (the observation kernel has no right-hand side)
-    const auto key = std::make_tuple(h->device, rhs_id, obs_id, P, itg, (int)kind);
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g_ng_cache.find(key);
-        if (it != g_ng_cache.end()) { *fn = it->second.fn; return RK_OK; }
-    }
-    const JitCode* cp = nullptr;
-    const int rc = ng_code(rhs_id, obs_id, P, itg, kind, &cp);
+// program text, name expression and the user's type name (for the error message) of the build behind `key`
+struct JitProgram { std::string src, expr, what; const char* role; };
+static int jit_program(const JitKey& key, JitProgram& p) {
+    const JitKindRow& row = kJitKinds[key.kind];
+    const UserRhs* u = nullptr;
+    const UserObs* ob = nullptr;
+    int rc = is_user_rhs(key.rhs) ? user_rhs(key.rhs, &u) : RK_OK;
+    if (rc == RK_OK && key.obs >= 0) rc = user_obs(key.obs, &ob);
     if (rc) return rc;
-    const JitCode& c = *cp;
-    if (c.rc) { set_error("%s", c.error.c_str()); return c.rc; }
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_ng_cache.find(key);
-    if (it == g_ng_cache.end()) {
-        JitEntry e;
-        RK_HIP(hipModuleLoadData(&e.mod, c.code.data()));
-        RK_HIP(hipModuleGetFunction(&e.fn, e.mod, c.lowered.c_str()));
-        if (getenv("RK_JIT_VERBOSE")) {
-            int regs = 0, scratch = 0;
-            (void)hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, e.fn);
-            (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, e.fn);
-            fprintf(stderr, "[rk] jit kernel %s: %d registers, %d B scratch per lane\n", c.lowered.c_str(), regs, scratch);
-        }
-        it = g_ng_cache.emplace(key, e).first;
+    RK_REQUIRE(u || ob, RK_ERR_INVALID, "unknown user rhs_id %d", key.rhs);
+    if (ob) p.src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n") +
+                    (u ? "" : "#include \"rhs.hpp\"\n");                // (a user's names stay free)
+    else p.src = "#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n"
+                 "#include \"solve_tile3_kernels.hpp\"\n#include \"solve_tile4_kernels.hpp\"\n"
+                 "#include \"solve_tilen_kernels.hpp\"\n#include \"solve_sqrt_kernels.hpp\"\n"
+                 "#include \"solve_small_m_kernels.hpp\"\n#include \"solve_dense_itg_kernels.hpp\"\n";
+    if (row.header) p.src += std::string("#include \"") + row.header + "\"\n";
+    p.src += "namespace rk {\n";
+    if (u) {
+        p.src += u->source + "\nusing UserRhsT = " + u->type_name + ";\n";
+    } else if (strstr(row.expr, "UserRhsT")) {
+        const char* t = builtin_rhs_type(key.rhs);
+        RK_REQUIRE(t, RK_ERR_UNSUPPORTED, "daltonng: rhs %d has no lane-per-trajectory form", key.rhs);
+        p.src += std::string("using UserRhsT = ") + t + ";\n";
     }
-    *fn = it->second.fn;
+    if (ob) p.src += ob->source + "\nusing UserObsT = " + ob->type_name + ";\n";
+    p.src += "}  // namespace rk\n";
+    p.expr = kernel_expr(key, ob ? ob->n_active : 0);
+    p.what = ob ? ob->type_name : u->type_name;
+    p.role = ob ? "observation log-likelihood" : "user right-hand side";
+    return RK_OK;
+}
+
+// The one lookup: the build behind `key` (compiled once; a failure is remembered and returned with its message) and, with
+// a handle, the kernel loaded on the handle's device.  g_mu is held for the map accesses and the module load only: the
+// program text is put together from registry entries that never change, and hiprtc runs outside the lock -- a build takes
+// seconds and must not hold up registrations or other handles.  Two threads that miss at once both compile; the first result
+// inserted is kept.
+static int jit_lookup(JitKey key, rk_handle h, hipFunction_t* fn) {
+    const JitKey ckey = key;
+    if (h) key.device = h->device;
+    const JitCode* c = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        const auto mi = h ? g_mod.find(key) : g_mod.end();
+        if (mi != g_mod.end()) { *fn = mi->second; return RK_OK; }
+        const auto ci = g_code.find(ckey);
+        if (ci != g_code.end()) c = &ci->second;
+    }
+    if (!c) {
+        JitProgram p;
+        const int rc = jit_program(ckey, p);
+        if (rc) return rc;
+        JitCode built;
+        built.rc = jit_compile_src(p.src, p.expr, p.what, built.code, built.lowered, p.role);
+        if (built.rc) built.error = rk_last_error();
+        std::lock_guard<std::mutex> lk(g_mu);
+        c = &g_code.emplace(ckey, std::move(built)).first->second;     // (map nodes do not move: the pointer stays valid)
+    }
+    if (c->rc) { set_error("%s", c->error.c_str()); return c->rc; }
+    if (!h) return RK_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto mi = g_mod.find(key);
+    if (mi == g_mod.end()) {
+        hipModule_t mod;
+        hipFunction_t f;
+        RK_HIP(hipModuleLoadData(&mod, c->code.data()));
+        RK_HIP(hipModuleGetFunction(&f, mod, c->lowered.c_str()));
+        if (getenv("RK_JIT_VERBOSE")) {                   // resources of the kernel hiprtc built (a spilled dual copy of a big system shows here)
+            int regs = 0, scratch = 0, lds = 0;
+            (void)hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, f);
+            (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f);
+            (void)hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, f);
+            fprintf(stderr, "[rk] jit kernel %s: %d registers, %d B scratch per lane, %d B LDS\n", c->lowered.c_str(), regs, scratch, lds);
+        }
+        mi = g_mod.emplace(key, f).first;
+    }
+    *fn = mi->second;
+    return RK_OK;
+}
+
+// the kernel behind `key` on the handle's device, launched on the handle's stream under the kind's profile label
+static int launch_jit(rk_handle h, const JitKey& key, LaunchGeom g, void** params) {
+    hipFunction_t fn;
+    const int rc = jit_lookup(key, h, &fn);
+    if (rc) return rc;
+    std::optional<LaunchTimer> t;
+    if (kJitKinds[key.kind].label) t.emplace(h, kJitKinds[key.kind].label);
+    RK_HIP(hipModuleLaunchKernel(fn, g.grid.x, 1, 1, g.block.x, 1, 1, 0, h->stream, params, nullptr));
+    if (t) t->stop();
+    return RK_OK;
+}
+
+bool is_user_rhs(int rhs_id) { return rhs_id >= RK_RHS_USER_BASE; }
+
+// Does the MFMA-tile forward kernel exist for this user right-hand side and configuration?  (It needs NDEP == 1 and a
+// block count the tile kernels support; decided by compiling it once -- cached -- so that rk_solve_layout and the
+// solve agree.)  tile = JIT_TILE3 / JIT_TILE4 for n_bstate = 3 / 4, JIT_TILEN for the blocked tiles.
+bool user_tile_available(const rk_solve_cfg* c, JitKind tile) {
+    const UserRhs* u;
+    if (user_rhs(c->rhs_id, &u)) return false;
+    const int nb = u->n_block;
+    if (c->n_block != nb || c->n_bmeas != 1 || u->n_bmeas != 1 || c->kalman_type != RK_KALMAN_STANDARD) return false;
+    if (nb < 1 || nb > (tile == JIT_TILE4 ? 4 : 64)) return false;      // p = 3 and blocked tiles: up to 64 blocks (4 per wave, LDS exchange); p = 4: one wave
+    const int rc = jit_lookup(jit_key(tile, c->rhs_id, c), nullptr, nullptr);
+    if (rc && getenv("RK_JIT_VERBOSE")) fprintf(stderr, "[rk] tile kernel not available for user rhs %d (p = %d): %s\n", c->rhs_id, (int)tile, rk_last_error());
+    return rc == RK_OK;
+}
+
+int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, JitKind tile) {
+    SolveArgs args = a;
+    int P = c->n_bstate;
+    void* params[] = {&args, &tiles, &P};                           // (the p = 3 / p = 4 kernels take the first two)
+    const LaunchGeom g = fwd_tile_geom(a.B, c->n_block);
+    launch_placement_primer(h, g.grid, g.block);
+    return launch_jit(h, jit_key(tile, c->rhs_id, c), g, params);
+}
+
+int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
+    const UserRhs* u;
+    const int rc = user_rhs(c->rhs_id, &u);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
+               "square-root solver: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block,
+               c->n_bmeas);
+    SolveArgs args = a;
+    void* params[] = {&args};
+    return launch_jit(h, jit_key(JIT_SQRT, c->rhs_id, c), fwd_sqrt_geom(a.B, c->n_block), params);
+}
+
+// Is the configuration the one rhs_id was registered for (n_block, n_bmeas), at an n_bstate the lane kernels serve?
+int user_rhs_check(const rk_solve_cfg* c) {
+    const UserRhs* u;
+    const int rc = user_rhs(c->rhs_id, &u);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == u->n_bmeas, RK_ERR_UNSUPPORTED,
+               "user rhs %d needs n_block=%d, n_bmeas=%d (got %d, %d)", c->rhs_id, u->n_block, u->n_bmeas, c->n_block, c->n_bmeas);
+    const int pmax = c->n_bmeas > 1 ? 9 : 6;                     // (the backward kernels exist up to n_bstate = 9)
+    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= pmax, RK_ERR_UNSUPPORTED, "lane-per-trajectory path supports n_bstate in [2, %d] "
+               "here, got %d", pmax, c->n_bstate);
+    RK_REQUIRE(c->n_bmeas <= c->n_bstate, RK_ERR_INVALID, "n_bmeas = %d exceeds n_bstate = %d", c->n_bmeas, c->n_bstate);
+    return RK_OK;
+}
+
+// ---- dense ("non-block") path: the interrogation kernel around the user's right-hand side (solve_dense_itg_kernels.hpp)
+// Taken for one block with several measurements that the lane kernels do not serve (n_bstate > 9 or n_bmeas > 4).
+static bool dense_wanted(const UserRhs& u, int n_bstate) { return u.n_block == 1 && u.n_bmeas > 1 && (n_bstate > 9 || u.n_bmeas > 4); }
+
+bool user_dense_wanted(const rk_solve_cfg* c) {
+    const UserRhs* u;
+    return user_rhs(c->rhs_id, &u) == RK_OK && c->n_block == 1 && c->n_bmeas == u->n_bmeas && dense_wanted(*u, c->n_bstate);
+}
+
+int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a) {
+    DenseItgArgs args = a;
+    void* params[] = {&args};
+    return launch_jit(h, jit_key(JIT_DENSE_ITG, c->rhs_id, c), LaunchGeom{dim3(a.B), dim3(256)}, params);
+}
+
+int user_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
+    const int rc = user_rhs_check(c);
+    if (rc) return rc;
+    const bool sp = (c->flags & RK_FLAG_STORE_PRED) != 0;
+    const JitKind kind = c->n_bmeas > 1 ? (sp ? JIT_FWD_M_STORE_PRED : JIT_FWD_M) : (sp ? JIT_FWD_STORE_PRED : JIT_FWD);
+    SolveArgs args = a;
+    void* params[] = {&args};
+    return launch_jit(h, jit_key(kind, c->rhs_id, c), fwd_lane_geom(a.B), params);
+}
+
+// DALTON's forward filters around a user right-hand side.  Lanes (dalton_kernels.hpp): the log-likelihood form (joint and
+// marginal filter in the two halves of a wave) or the joint filter's store form.  Tiles (dalton_tile3_kernels.hpp,
+// n_bstate = 3, n_bobs = 1): 2 B or B filter instances of n_block tiles.
+int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, int n_bobs, bool store,
+                bool tile, double* out) {
+    const int rc = user_rhs_check(c);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "dalton: n_bmeas = 1 only");
+    SolveArgs args = a;
+    const DaltonObs* op = &o;
+    void* params[] = {&args, (void*)op, &out};
+    const JitKind kind = tile ? (store ? JIT_DALTON_TILE3_STORE : JIT_DALTON_TILE3) : (store ? JIT_DALTON_STORE : JIT_DALTON);
+    return launch_jit(h, jit_key(kind, c->rhs_id, c, n_bobs), tile ? dalton_tile_geom(a.B, c->n_block, !store) : dalton_lane_geom(a.B, !store),
+                      params);
+}
+
+// dalton_at's forward filters around a user right-hand side (dalton_at_kernels.hpp / dalton_at_tile3_kernels.hpp): the
+// log-likelihood form only, launched like user_dalton's.
+int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const DaltonAt& s, int n_bobs,
+                   bool tile, double* out) {
+    const int rc = user_rhs_check(c);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "dalton_at: n_bmeas = 1 only");
+    SolveArgs args = a;
+    const DaltonObs* op = &o;
+    const DaltonAt* sp = &s;
+    void* params[] = {&args, (void*)op, (void*)sp, &out};
+    return launch_jit(h, jit_key(tile ? JIT_DALTON_AT_TILE3 : JIT_DALTON_AT, c->rhs_id, c, n_bobs),
+                      tile ? dalton_tile_geom(a.B, c->n_block, true) : dalton_lane_geom(a.B, true), params);
+}
+
+int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
+                     const double* vp, double* wm, double* mm_, double* vm) {
+    const int rc = user_rhs_check(c);
+    if (rc) return rc;
+    const bool multi = c->n_bmeas > 1;                     // several measurements per block: interrogate_kernel_m
+    RK_REQUIRE(!multi || c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED,
+               "rk_interrogate_batched: n_bmeas > 1 with kalman_type = square-root is fused into the solvers only");
+    SolveArgs args = a;
+    int sqrt_mode = c->kalman_type == RK_KALMAN_SQRT ? 1 : 0;
+    void* params[] = {&args, &t, &step, &mp, &vp, &wm, &mm_, &vm, &sqrt_mode};
+    return launch_jit(h, jit_key(multi ? JIT_ITG_M : JIT_ITG, c->rhs_id, c), fwd_lane_geom(a.B), params);
+}
+
+// ---- DALTON for non-Gaussian observations (daltonng_kernels.hpp): the observation log-likelihood is always user code, so
+// its forward filter is a hiprtc build around either kind of right-hand side
+int ng_obs_info(int obs_id, NgObsInfo* info) {
+    const UserObs* u;
+    const int rc = user_obs(obs_id, &u);
+    if (rc) return rc;
+    info->n_block = u->n_block; info->n_bstate = u->n_bstate; info->n_ycols = u->n_ycols; info->n_theta = u->n_theta;
+    info->n_active = u->n_active;
     return RK_OK;
 }
 
@@ -483,31 +449,19 @@ int ng_forward(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& 
         const int rc = user_rhs_check(c);
         if (rc) return rc;
     }
-    hipFunction_t fn;
-    const int rc = ng_jit_get(h, c->rhs_id, obs_id, c->n_bstate, c->interrogate, both ? JIT_DALTONNG_BOTH : JIT_DALTONNG, &fn);
-    if (rc) return rc;
     SolveArgs args = a;
     NgObs obs = o;
     void* params[] = {&args, &obs, &zm, &zv};
-    LaunchTimer t(h, both ? "daltonng_fwd_kernel<both>" : "daltonng_fwd_kernel<store>");
-    RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, both ? 32 : 64), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
-    t.stop();
-    return RK_OK;
+    return launch_jit(h, jit_key(both ? JIT_DALTONNG_BOTH : JIT_DALTONNG, c->rhs_id, c, 0, obs_id), dalton_lane_geom(a.B, both), params);
 }
 
 // logy_x on the smoothed means and the final sum into out (B)
 int ng_obs_eval(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, const double* sm,
                 const double* part, double* out) {
-    hipFunction_t fn;
-    const int rc = ng_jit_get(h, 0, obs_id, c->n_bstate, 0, JIT_DALTONNG_OBS, &fn);
-    if (rc) return rc;
     int B = a.B, n_obs = o.n_obs, theta_b = a.theta_b;
     const double *y = o.y, *theta = a.theta;
     void* params[] = {&B, &n_obs, &y, &sm, &theta, &theta_b, &part, &out};
-    LaunchTimer t(h, "daltonng_obs_kernel");
-    RK_HIP(hipModuleLaunchKernel(fn, div_up(a.B, 64), 1, 1, 64, 1, 1, 0, h->stream, params, nullptr));
-    t.stop();
-    return RK_OK;
+    return launch_jit(h, jit_key(JIT_DALTONNG_OBS, c->rhs_id, c, 0, obs_id), fwd_lane_geom(a.B), params);
 }
 
 }  // namespace rk
@@ -546,33 +500,29 @@ int rk_register_obs_source(const char* type_name, const char* source, int32_t n_
 
 int rk_obs_compile_check(int32_t obs_id, int32_t rhs_id, int32_t interrogate) {
     NgObsInfo info;
-    int rc0 = ng_obs_info(obs_id, &info);
-    if (rc0) return rc0;
-    const int P = info.n_bstate;
+    int rc = ng_obs_info(obs_id, &info);
+    if (rc) return rc;
+    rk_solve_cfg c{};
+    c.n_bstate = info.n_bstate;
+    c.interrogate = interrogate;
     const JitKind kinds[] = {JIT_DALTONNG_BOTH, JIT_DALTONNG, JIT_DALTONNG_OBS};
     for (JitKind k : kinds) {
-        const JitCode* c = nullptr;
-        const bool tail = k == JIT_DALTONNG_OBS;
-        const int rc = ng_code(tail ? 0 : rhs_id, obs_id, P, tail ? 0 : interrogate, k, &c);
+        rc = jit_lookup(jit_key(k, rhs_id, &c, 0, obs_id), nullptr, nullptr);
         if (rc) return rc;
-        if (c->rc) { set_error("%s", c->error.c_str()); return c->rc; }
     }
     return RK_OK;
 }
 
 int rk_rhs_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
-    UserRhs u;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        const int idx = rhs_id - RK_RHS_USER_BASE;
-        RK_REQUIRE(idx >= 0 && idx < (int)g_rhs.size(), RK_ERR_INVALID, "unknown user rhs_id %d", rhs_id);
-        u = g_rhs[idx];
-    }
-    std::vector<char> code;
-    std::string lowered;
-    const bool dense = u.n_block == 1 && u.n_bmeas > 1 && (n_bstate > 9 || u.n_bmeas > 4);      // (user_dense_wanted)
-    int rc = jit_compile(u, n_bstate, interrogate, dense ? JIT_DENSE_ITG : (u.n_bmeas > 1 ? JIT_FWD_M : JIT_FWD), code, lowered);
-    if (rc == RK_OK && !dense && u.n_bmeas > 1) rc = jit_compile(u, n_bstate, interrogate, JIT_ITG_M, code, lowered);     // + the standalone interrogation
+    const UserRhs* u;
+    int rc = user_rhs(rhs_id, &u);
+    if (rc) return rc;
+    rk_solve_cfg c{};
+    c.n_bstate = n_bstate;
+    c.interrogate = interrogate;
+    const bool dense = dense_wanted(*u, n_bstate);
+    rc = jit_lookup(jit_key(dense ? JIT_DENSE_ITG : (u->n_bmeas > 1 ? JIT_FWD_M : JIT_FWD), rhs_id, &c), nullptr, nullptr);
+    if (rc == RK_OK && !dense && u->n_bmeas > 1) rc = jit_lookup(jit_key(JIT_ITG_M, rhs_id, &c), nullptr, nullptr);     // + the standalone interrogation
     return rc;
 }
 

@@ -31,28 +31,29 @@ int dense_solve(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const
 size_t dense_ws_bytes(const rk_solve_cfg* c, int mode);
 
 // ---- user-supplied right-hand sides (rhs_jit.hip) ------------------------------------------------------------------
-// Kernel kinds of the hiprtc builds.  The values are keys of the JIT caches: do not renumber.
+// Kernel kinds of the hiprtc builds: the row index of rhs_jit.hip's table and a field of its cache key.  Do not renumber.
 enum JitKind : int {
     JIT_FWD = 0,              // fwd_kernel<.., false>
     JIT_FWD_STORE_PRED = 1,   // fwd_kernel<.., true>
     JIT_ITG = 2,              // interrogate_kernel
     JIT_TILE3 = 3,            // fwd_tile3_kernel
     JIT_TILE4 = 4,            // fwd_tile4_kernel
-    JIT_TILEN = 5,            // fwd_tilen_kernel (P = NB)
+    JIT_TILEN = 5,            // fwd_tilen_kernel
     JIT_SQRT = 6,             // fwd_sqrt_kernel
     JIT_FWD_M = 7,            // fwd_kernel_m<.., false>   (n_bmeas > 1)
     JIT_FWD_M_STORE_PRED = 8, // fwd_kernel_m<.., true>
     JIT_DENSE_ITG = 9,        // dense_interrogate_kernel
     JIT_ITG_M = 10,           // interrogate_kernel_m     (n_bmeas > 1)
-    JIT_DALTON = 11,          // dalton_fwd_kernel<.., false> (log-likelihood; P key = n_bstate + 16 n_bobs)
-    JIT_DALTON_STORE = 12,    // dalton_fwd_kernel<.., true>  (joint filter's moments; same P key)
+    JIT_DALTON = 11,          // dalton_fwd_kernel<.., false> (log-likelihood)
+    JIT_DALTON_STORE = 12,    // dalton_fwd_kernel<.., true>  (joint filter's moments)
     JIT_DALTON_TILE3 = 13,    // dalton_fwd_tile3_kernel<.., false> (log-likelihood on the p = 3 tiles)
     JIT_DALTON_TILE3_STORE = 14,  // dalton_fwd_tile3_kernel<.., true> (RK_LAYOUT_TILE3 records)
-    JIT_DALTONNG = 15,        // daltonng_fwd_kernel<.., false> (joint filter's moments; cached per (rhs, obs model))
+    JIT_DALTONNG = 15,        // daltonng_fwd_kernel<.., false> (joint filter's moments)
     JIT_DALTONNG_BOTH = 16,   // daltonng_fwd_kernel<.., true>  (joint filter and the filter on Z alone)
     JIT_DALTONNG_OBS = 17,    // daltonng_obs_kernel (logy_x and the final sum; no right-hand side)
-    JIT_DALTON_AT = 18,       // dalton_fwd_at_kernel (dalton_at's log-likelihood; P key = n_bstate + 16 n_bobs)
+    JIT_DALTON_AT = 18,       // dalton_fwd_at_kernel (dalton_at's log-likelihood)
     JIT_DALTON_AT_TILE3 = 19, // dalton_fwd_at_tile3_kernel (dalton_at's log-likelihood on the p = 3 tiles)
+    JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
 bool user_tile_available(const rk_solve_cfg* c, JitKind tile);
@@ -135,6 +136,48 @@ inline int path_layout(SolvePath p, const rk_solve_cfg* c) {
     }
 }
 
+// ---- launch geometry --------------------------------------------------------------------------------------------------
+// One function per kernel family, called by the launcher of its ahead-of-time instances and by the launcher of its
+// hiprtc builds (rhs_jit.hip), so that the two cannot size a grid differently.
+struct LaunchGeom { dim3 grid, block; };
+
+// forward tile kernels: tiles per wave and waves per workgroup at n_block = D (Tpw<D> of mfma_tile.hpp and TileWaves<D> of
+// solve_tile3_kernels.hpp; solve_tile3.hip asserts the equality for every D)
+constexpr int tiles_per_wave(int D) { return D == 3 ? 3 : 4; }
+constexpr int tile_waves(int D) { return D <= 4 ? 1 : (D + 3) / 4; }
+
+// lane kernels with one trajectory per lane: fwd_kernel, fwd_kernel_m, interrogate_kernel(_m), daltonng_obs_kernel
+inline LaunchGeom fwd_lane_geom(int B) { return {dim3(div_up(B, 64)), dim3(64)}; }
+// fwd_sqrt_kernel: 64 / D trajectories per wave (solve_sqrt_kernels.hpp)
+inline LaunchGeom fwd_sqrt_geom(int B, int D) { return {dim3(div_up(B, 64 / D)), dim3(64)}; }
+// fwd_tile3_kernel, fwd_tile4_kernel, fwd_tilen_kernel: whole trajectories in one wave up to four blocks, beyond that one
+// workgroup of tile_waves(D) waves per trajectory
+inline LaunchGeom fwd_tile_geom(int B, int D) {
+    const int nw = tile_waves(D);
+    return {dim3(nw == 1 ? div_up(B * D, tiles_per_wave(D)) : B), dim3(64 * nw)};
+}
+// dalton_fwd_kernel, dalton_fwd_at_kernel, daltonng_fwd_kernel: the log-likelihood forms run two filters per trajectory
+// in the two halves of a wave (pair: 32 trajectories per wave), the store forms one (64)
+inline LaunchGeom dalton_lane_geom(int B, bool pair) { return {dim3(div_up(B, pair ? 32 : 64)), dim3(64)}; }
+// dalton_fwd_tile3_kernel, dalton_fwd_at_tile3_kernel (n_block <= 4): 2 B (pair) or B filter instances of D tiles
+inline LaunchGeom dalton_tile_geom(int B, int D, bool pair) {
+    return {dim3(div_up((pair ? 2 * B : B) * D, tiles_per_wave(D))), dim3(64)};
+}
+
+// ---- what the built-in instances of several families share ---------------------------------------------------------------
+// largest n_bstate of DALTON's built-in lane instances (dalton, dalton_at): three blocks at n_bstate = 6 hold more state than
+// a lane's registers (the store form spilled over 2 KiB per lane), so Lorenz63 stops at 5
+template <class RHS>
+constexpr int dalton_pmax() { return RHS::D >= 3 ? 5 : 6; }
+
+// a built-in right-hand side reads RHS::NTHETA parameters: fewer given (with a parameter array at all) is refused
+template <class RHS>
+int check_n_theta(const rk_solve_cfg* c, const SolveArgs& a) {
+    RK_REQUIRE(c->n_theta == 0 || c->n_theta >= RHS::NTHETA || !a.theta, RK_ERR_INVALID,
+               "rhs %d needs %d parameters, got n_theta=%d", c->rhs_id, RHS::NTHETA, c->n_theta);
+    return RK_OK;
+}
+
 // ---- compile-time dispatch ------------------------------------------------------------------------------------------
 // f(std::integral_constant<int, v>{}) for v in [Lo, Hi]; false (f not called) outside.  Instantiates f for every value.
 template <int Lo, int Hi, class F>
@@ -159,6 +202,13 @@ bool with_builtin_rhs(int rhs_id, F&& f) {
         case RK_RHS_HIGHER_ORDER: f(HigherOrder{}); return true;
     }
     return false;
+}
+
+// is rhs_id a built-in right-hand side with n_block blocks (RHS::D)?
+inline bool builtin_has_n_block(int rhs_id, int n_block) {
+    bool fits = false;
+    with_builtin_rhs(rhs_id, [&](auto rhs) { fits = decltype(rhs)::D == n_block; });
+    return fits;
 }
 
 }  // namespace rk

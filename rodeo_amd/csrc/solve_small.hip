@@ -457,16 +457,16 @@ template <class RHS>
 static int launch_fwd_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     RK_REQUIRE(c->n_block == RHS::D && c->n_bmeas == 1, RK_ERR_UNSUPPORTED,
                "rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, RHS::D, c->n_block, c->n_bmeas);
-    RK_REQUIRE(c->n_theta == 0 || c->n_theta >= RHS::NTHETA || !a.theta, RK_ERR_INVALID,
-               "rhs %d needs %d parameters, got n_theta=%d", c->rhs_id, RHS::NTHETA, c->n_theta);
+    const int rc = check_n_theta<RHS>(c, a);
+    if (rc) return rc;
     const bool sp = (c->flags & RK_FLAG_STORE_PRED) != 0;
-    const dim3 grid(div_up(a.B, 64)), block(64);
+    const LaunchGeom g = fwd_lane_geom(a.B);
     bool itg_ok = false;
     const bool p_ok = dispatch_int<2, 6>(c->n_bstate, [&](auto P) {
         itg_ok = dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
             LaunchTimer t(h, "fwd_kernel");
-            if (sp) hipLaunchKernelGGL((fwd_kernel<RHS, P, I, true>), grid, block, 0, h->stream, a);
-            else hipLaunchKernelGGL((fwd_kernel<RHS, P, I, false>), grid, block, 0, h->stream, a);
+            if (sp) hipLaunchKernelGGL((fwd_kernel<RHS, P, I, true>), g.grid, g.block, 0, h->stream, a);
+            else hipLaunchKernelGGL((fwd_kernel<RHS, P, I, false>), g.grid, g.block, 0, h->stream, a);
             t.stop();
         });
     });
@@ -509,11 +509,11 @@ static int launch_itg_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a
                           const double* mp, const double* vp, double* wm, double* mm_, double* vm) {
     RK_REQUIRE(c->n_block == RHS::D && c->n_bmeas == 1, RK_ERR_UNSUPPORTED,
                "rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, RHS::D, c->n_block, c->n_bmeas);
-    const dim3 grid(div_up(a.B, 64)), block(64);
+    const LaunchGeom g = fwd_lane_geom(a.B);
     const int sqrt_mode = c->kalman_type == RK_KALMAN_SQRT ? 1 : 0;      // only interrogate_chkrebtii reads it
     const bool ok = dispatch_int<2, 6>(c->n_bstate, [&](auto P) {
         dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
-            hipLaunchKernelGGL((interrogate_kernel<RHS, P, I>), grid, block, 0, h->stream, a, t, step, mp, vp, wm, mm_, vm, sqrt_mode);
+            hipLaunchKernelGGL((interrogate_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, t, step, mp, vp, wm, mm_, vm, sqrt_mode);
         });
     });
     RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "rk_interrogate_batched supports n_bstate in [2, 6], got %d", c->n_bstate);

@@ -369,12 +369,12 @@ template <class RHS>
 static int launch_fwd_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
     RK_REQUIRE(c->n_block == RHS::D && c->n_bmeas == 1, RK_ERR_UNSUPPORTED,
                "rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, RHS::D, c->n_block, c->n_bmeas);
-    const dim3 grid(div_up(a.B, 64 / RHS::D)), block(64);      // 64 / D trajectories per wave (solve_sqrt_kernels.hpp)
+    const LaunchGeom g = fwd_sqrt_geom(a.B, RHS::D);
     bool itg_ok = false;
     const bool p_ok = dispatch_int<2, 8>(c->n_bstate, [&](auto P) {
         LaunchTimer t(h, "fwd_sqrt_kernel");
         itg_ok = dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
-            hipLaunchKernelGGL((fwd_sqrt_kernel<RHS, P, I>), grid, block, 0, h->stream, a);
+            hipLaunchKernelGGL((fwd_sqrt_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a);
         });
         if (itg_ok) t.stop();
     });

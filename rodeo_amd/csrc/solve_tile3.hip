@@ -868,36 +868,32 @@ __global__ void __launch_bounds__(256, 2) bwd_sim_tile3_kernel(SolveArgs a, doub
 // per wave or more waves per workgroup change nothing (measured, round 1) -- only more trajectories raise throughput.
 template <class RHS>
 static int launch_fwd_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles) {
-    const dim3 grid(div_up(a.B * RHS::D, Tpw<RHS::D>::value)), block(64);
-    launch_placement_primer(h, grid, block);           // (common.hpp: exact one-wave-per-SIMD placement behind any kernel)
+    const LaunchGeom g = fwd_tile_geom(a.B, RHS::D);
+    launch_placement_primer(h, g.grid, g.block);           // (common.hpp: exact one-wave-per-SIMD placement behind any kernel)
     LaunchTimer t(h, "fwd_tile3_kernel");
-    switch (c->interrogate) {
-        case RK_INTERROGATE_KRAMER:
-            hipLaunchKernelGGL((fwd_tile3_kernel<RHS, RK_INTERROGATE_KRAMER>), grid, block, 0, h->stream, a, tiles); break;
-        case RK_INTERROGATE_SCHOBER:
-            hipLaunchKernelGGL((fwd_tile3_kernel<RHS, RK_INTERROGATE_SCHOBER>), grid, block, 0, h->stream, a, tiles); break;
-        case RK_INTERROGATE_RODEO:
-            hipLaunchKernelGGL((fwd_tile3_kernel<RHS, RK_INTERROGATE_RODEO>), grid, block, 0, h->stream, a, tiles); break;
-        case RK_INTERROGATE_CHKREBTII:
-            hipLaunchKernelGGL((fwd_tile3_kernel<RHS, RK_INTERROGATE_CHKREBTII>), grid, block, 0, h->stream, a, tiles); break;
-        default:
-            set_error("tile path: interrogate id %d not supported", c->interrogate);
-            return RK_ERR_UNSUPPORTED;
-    }
+    const bool ok = dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
+        hipLaunchKernelGGL((fwd_tile3_kernel<RHS, I>), g.grid, g.block, 0, h->stream, a, tiles);
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "tile path: interrogate id %d not supported", c->interrogate);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;
 }
 
+// the run-time geometry of the forward tile kernels (solve_paths.hpp) is the kernels' compile-time one, at every n_block
+template <int D>
+constexpr bool tile_geom_matches() {
+    if constexpr (D == 0) return true;
+    else return tiles_per_wave(D) == Tpw<D>::value && tile_waves(D) == TileWaves<D>::value && tile_geom_matches<D - 1>();
+}
+static_assert(tile_geom_matches<TILE_MAX_BLOCKS>(), "tiles_per_wave / tile_waves differ from Tpw<D> / TileWaves<D>");
+
 bool tile3_supported(const rk_solve_cfg* c, int mode) {
     if (c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) return false;
     if (c->kalman_type != RK_KALMAN_STANDARD || c->n_bstate != 3 || c->n_bmeas != 1) return false;
     if (c->interrogate < RK_INTERROGATE_RODEO || c->interrogate > RK_INTERROGATE_CHKREBTII) return false;
-    if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) return c->n_block == 2;
-    if (c->rhs_id == RK_RHS_LORENZ63) return c->n_block == 3;
-    if (c->rhs_id == RK_RHS_HIGHER_ORDER) return c->n_block == 1;
     if (is_user_rhs(c->rhs_id)) return user_tile_available(c, JIT_TILE3);       // hiprtc build of fwd_tile3_kernel (rhs_jit.hip)
-    return false;
+    return builtin_has_n_block(c->rhs_id, c->n_block);
 }
 
 bool tile3_sim_logpost_supported(const rk_solve_cfg* c, int n_obs) {

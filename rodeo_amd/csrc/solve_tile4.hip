@@ -467,20 +467,13 @@ __global__ void __launch_bounds__(256 * SETS, SETS == 1 ? 2 : 1) bwd_mv_tile4_ke
 // ---- dispatch ---------------------------------------------------------------------------------------------------
 template <class RHS>
 static int launch_fwd_tile4(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles) {
-    const dim3 grid(div_up(a.B * RHS::D, Tpw<RHS::D>::value)), block(64);
-    launch_placement_primer(h, grid, block);           // (common.hpp: exact one-wave-per-SIMD placement behind any kernel)
+    const LaunchGeom g = fwd_tile_geom(a.B, RHS::D);
+    launch_placement_primer(h, g.grid, g.block);           // (common.hpp: exact one-wave-per-SIMD placement behind any kernel)
     LaunchTimer t(h, "fwd_tile4_kernel");
-    switch (c->interrogate) {
-        case RK_INTERROGATE_KRAMER:
-            hipLaunchKernelGGL((fwd_tile4_kernel<RHS, RK_INTERROGATE_KRAMER>), grid, block, 0, h->stream, a, tiles); break;
-        case RK_INTERROGATE_SCHOBER:
-            hipLaunchKernelGGL((fwd_tile4_kernel<RHS, RK_INTERROGATE_SCHOBER>), grid, block, 0, h->stream, a, tiles); break;
-        case RK_INTERROGATE_RODEO:
-            hipLaunchKernelGGL((fwd_tile4_kernel<RHS, RK_INTERROGATE_RODEO>), grid, block, 0, h->stream, a, tiles); break;
-        default:
-            set_error("tile path: interrogate id %d not supported", c->interrogate);
-            return RK_ERR_UNSUPPORTED;
-    }
+    const bool ok = dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {        // (no chkrebtii instance at p = 4)
+        hipLaunchKernelGGL((fwd_tile4_kernel<RHS, I>), g.grid, g.block, 0, h->stream, a, tiles);
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "tile path: interrogate id %d not supported", c->interrogate);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;
@@ -493,16 +486,13 @@ bool tile4_supported(const rk_solve_cfg* c, int mode) {
     if (c->interrogate != RK_INTERROGATE_KRAMER && c->interrogate != RK_INTERROGATE_SCHOBER &&
         c->interrogate != RK_INTERROGATE_RODEO)
         return false;
-    if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) return c->n_block == 2;
-    if (c->rhs_id == RK_RHS_LORENZ63) return c->n_block == 3;
-    if (c->rhs_id == RK_RHS_HIGHER_ORDER) return c->n_block == 1;
     if (is_user_rhs(c->rhs_id)) return user_tile_available(c, JIT_TILE4);       // hiprtc build of fwd_tile4_kernel (rhs_jit.hip)
-    return false;
+    return builtin_has_n_block(c->rhs_id, c->n_block);
 }
 
 size_t tile4_doubles(const rk_solve_cfg* c) {
     const size_t n_tiles = (size_t)c->n_block * (size_t)c->n_traj;
-    const size_t tpw = c->n_block == 3 ? 3 : 4;
+    const size_t tpw = tiles_per_wave(c->n_block);
     const size_t waves = (n_tiles + tpw - 1) / tpw;
     return (size_t)(c->n_steps + 1) * n_tiles * T4_DOUBLES + ((waves + 1) / 2) * 2 * 128;
 }
@@ -512,7 +502,7 @@ int tile4_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
     if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, JIT_TILE4);
     else with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_tile4<decltype(rhs)>(h, c, a, tiles); });     // (tile4_supported: a built-in id)
     if (rc || mode == RK_MODE_FILTER || a.N < 2) return rc;
-    const int tpw = a.D == 3 ? 3 : 4;
+    const int tpw = tiles_per_wave(a.D);
     // Two shapes of workgroup (RK_T4_BWD=quad|ds forces one).  quad: 4 waves, two workgroups per CU.  ds: 8 waves carrying two sets, each
     // consumer alone on its SIMD -- built in round 4 to see whether the chain wave suffers from its SIMD partner: it does not (HW_ID stamps
     // confirm the placement, and the consumer's tick stayed at 3925 cycles against 3945, 245 per step, even with ONE set per CU,

@@ -933,24 +933,14 @@ static inline int tilen_nb(int p) { return p <= 4 ? 1 : 2; }
 
 template <class RHS, int NB>
 static int launch_fwd_tilen_nb(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles) {
-    constexpr int NW = TileWaves<RHS::D>::value;
-    const dim3 grid(NW == 1 ? div_up(a.B * RHS::D, Tpw<RHS::D>::value) : a.B), block(64 * NW);
+    const LaunchGeom g = fwd_tile_geom(a.B, RHS::D);
     const int P = c->n_bstate;
-    launch_placement_primer(h, grid, block);           // (common.hpp: exact one-wave-per-SIMD placement behind any kernel)
+    launch_placement_primer(h, g.grid, g.block);           // (common.hpp: exact one-wave-per-SIMD placement behind any kernel)
     LaunchTimer t(h, "fwd_tilen_kernel");
-    switch (c->interrogate) {
-        case RK_INTERROGATE_KRAMER:
-            hipLaunchKernelGGL((fwd_tilen_kernel<RHS, RK_INTERROGATE_KRAMER, NB>), grid, block, 0, h->stream, a, tiles, P); break;
-        case RK_INTERROGATE_SCHOBER:
-            hipLaunchKernelGGL((fwd_tilen_kernel<RHS, RK_INTERROGATE_SCHOBER, NB>), grid, block, 0, h->stream, a, tiles, P); break;
-        case RK_INTERROGATE_RODEO:
-            hipLaunchKernelGGL((fwd_tilen_kernel<RHS, RK_INTERROGATE_RODEO, NB>), grid, block, 0, h->stream, a, tiles, P); break;
-        case RK_INTERROGATE_CHKREBTII:
-            hipLaunchKernelGGL((fwd_tilen_kernel<RHS, RK_INTERROGATE_CHKREBTII, NB>), grid, block, 0, h->stream, a, tiles, P); break;
-        default:
-            set_error("tile path: interrogate id %d not supported", c->interrogate);
-            return RK_ERR_UNSUPPORTED;
-    }
+    const bool ok = dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
+        hipLaunchKernelGGL((fwd_tilen_kernel<RHS, I, NB>), g.grid, g.block, 0, h->stream, a, tiles, P);
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "tile path: interrogate id %d not supported", c->interrogate);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;
@@ -965,11 +955,8 @@ bool tilen_supported(const rk_solve_cfg* c, int mode) {
     if (c->kalman_type != RK_KALMAN_STANDARD || c->n_bmeas != 1) return false;
     if (c->n_bstate < 4 || c->n_bstate > 8) return false;
     if (c->interrogate < RK_INTERROGATE_RODEO || c->interrogate > RK_INTERROGATE_CHKREBTII) return false;
-    if (c->rhs_id == RK_RHS_FITZHUGH_NAGUMO) return c->n_block == 2;
-    if (c->rhs_id == RK_RHS_LORENZ63) return c->n_block == 3;
-    if (c->rhs_id == RK_RHS_HIGHER_ORDER) return c->n_block == 1;
     if (is_user_rhs(c->rhs_id)) return user_tile_available(c, JIT_TILEN);       // hiprtc build of fwd_tilen_kernel (rhs_jit.hip)
-    return false;
+    return builtin_has_n_block(c->rhs_id, c->n_block);
 }
 
 size_t tilen_tile_doubles(const rk_solve_cfg* c) {

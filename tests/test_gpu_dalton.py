@@ -113,6 +113,34 @@ def test_dalton_traced_python_rhs(p):
     _check_ll(_device(_module().dalton, c, "kramer", ode_fun=_fitz), _oracle(dal.dalton, c, "kramer", THETA))
 
 
+def test_dalton_traced_rhs_keys_stay_apart_in_one_process():
+    """One traced right-hand side at every (p, n_bobs) of the list, then the list in reverse: the run-time builds are keyed
+    by n_bstate AND n_bobs, so no shape may be served by another shape's kernel; the second pass runs on cache hits."""
+    shapes = [(3, 1), (3, 2), (3, 3), (4, 1), (4, 2)]
+    cases = {}
+    for p, n_bobs in shapes:
+        c = _fhn(p, n_bobs=n_bobs, **LANE[p])
+        c["W"], _ = ra.utils.first_order_pad(_fitz, 2, p)
+        cases[p, n_bobs] = (c, _oracle(dal.dalton, c, "kramer", THETA))
+    for shape in shapes + shapes[::-1]:
+        c, ref = cases[shape]
+        _check_ll(_device(_module().dalton, c, "kramer", ode_fun=_fitz), ref)
+
+
+@pytest.mark.parametrize("p,n_bobs,lanes", [(3, 1, "0"), (3, 1, "1"), (4, 2, "0")])
+def test_dalton_traced_rhs_solve_mv(p, n_bobs, lanes, monkeypatch):
+    """test_dalton_solve_mv_parity around a traced right-hand side: the run-time builds of the tile and lane store kernels."""
+    monkeypatch.setenv("RK_DALTON_LANES", lanes)
+    c = _fhn(p, B=3, n_bobs=n_bobs, **LANE[p])
+    c["W"], _ = ra.utils.first_order_pad(_fitz, 2, p)
+    m, v = _device(_module().solve_mv, c, "kramer", ode_fun=_fitz)
+    assert m.shape == (3, c["N"] + 1, 2, p) and v.shape == (3, c["N"] + 1, 2, p, p)
+    for b in range(3):
+        mo, vo = _oracle(dal.solve_mv, c, "kramer", c["thetas"][b])
+        assert np.max(np.abs(m[b] - mo)) <= 1e-8 * max(1.0, np.max(np.abs(mo)))
+        assert np.max(np.abs(v[b] - vo)) <= 1e-8 * max(1.0, np.max(np.abs(vo)))
+
+
 # (grids and prior scales that keep every forecast variance far above utils.py:60-78's 1e-8 threshold)
 LANE = {2: {}, 3: {}, 4: dict(N=20, sigma=10.0), 5: dict(N=20, sigma=10.0), 6: dict(N=10, t_max=2.0, sigma=1000.0)}
 

@@ -71,6 +71,23 @@ def test_user_sources_compile_for_gfx950_without_gpu():
         fn(np.zeros((2, 3)), 0.0, theta=np.ones(3))          # registered without a host twin
 
 
+def test_compile_failure_is_remembered_per_source_not_globally():
+    """A build that fails is remembered under its own key: after another source has built, the broken one still fails with
+    its type name in the message, and the good one still passes."""
+    import rodeo_amd as ra
+    from rodeo_amd import _lib
+    bad = ra.ode.from_source("BrokenTwo", "struct BrokenTwo { static constexpr int D = 1; this is not C++ };", 1)
+    with pytest.raises(_lib.RodeoKalmanError) as e:
+        ra.ode.compile_check(bad, 3)
+    assert "BrokenTwo" in str(e.value)
+    good = ra.ode.from_source("MyFitz", FN_SRC, 2, (("theta", 3),), name="myfitz_after_broken")
+    ra.ode.compile_check(good, 3, _lib.INTERROGATE_RODEO)
+    with pytest.raises(_lib.RodeoKalmanError) as e:
+        ra.ode.compile_check(bad, 3)                         # the remembered failure, not the last build's outcome
+    assert "BrokenTwo" in str(e.value)
+    ra.ode.compile_check(good, 3, _lib.INTERROGATE_RODEO)
+
+
 def test_trace_python_rhs_to_source_and_compile():
     """ode.from_python: the generated struct, NDEP detection, powers / elementary functions, host twin, hiprtc build."""
     import rodeo_amd as ra
