@@ -3,6 +3,8 @@
 // interval that holds an observation, time-parallel) and the chain kernel of the route the filter took:
 //   tiles  -- fenrir_bwd_at_tile3_kernel (solve_tile3.hip): n_bstate = 3, n_bobs = 1, no flags, RK_LAYOUT_TILE3 records;
 //   lanes  -- fenrir_bwd_at_kernel (fenrir_at_kernels.hpp): n_bstate 2..6, n_bobs 1..3, RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR.
+// Both are fenrir's own chain kernels with the off-grid parts added: the tile one is an instance of the same body
+// (fenrir_tile3_body), the lane one shares the Markov step and the conditioning (fenrir_kernels.hpp, dalton_observe).
 #include "common.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"

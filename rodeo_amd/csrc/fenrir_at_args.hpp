@@ -1,5 +1,6 @@
 // fenrir_at: the arguments its three kernels share -- fenrir_at_hops_kernel and fenrir_bwd_at_kernel
-// (fenrir_at_kernels.hpp) and fenrir_bwd_at_tile3_kernel (solve_tile3.hip, next to its sibling's file-local helpers).
+// (fenrir_at_kernels.hpp) and fenrir_bwd_at_tile3_kernel (solve_tile3.hip: fenrir_tile3_body<true>, the body it shares with
+// fenrir_bwd_tile3_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -9,7 +9,7 @@
 // the chain kernels (fenrir_bwd_at_kernel here, fenrir_bwd_at_tile3_kernel in solve_tile3.hip) read them and add no LU.
 #pragma once
 #include "../../include/rodeo_kalman.h"
-#include "dalton_kernels.hpp"
+#include "fenrir_kernels.hpp"
 #include "eval_at_kernels.hpp"
 #include "fenrir_at_args.hpp"
 
@@ -120,10 +120,10 @@ __global__ void __launch_bounds__(64) fenrir_at_hops_kernel(SolveArgs a, FenrirA
     }
 }
 
-// The sibling of fenrir_bwd_kernel<P, false, MO, false> (solve_small.hip, left untouched): one lane per (block, trajectory)
-// over the batch-minor filtered and predicted moments.  At an interval with off-grid observations it runs the hops from the
-// batch-minor hop records -- G is read, not solved for -- with the conditioning (dalton_observe: fenrir_bwd_kernel's observe()
-// as a function) between them; the table index i is wave-uniform.
+// fenrir_bwd_kernel<P, false, MO, false> (solve_small.hip) for observations anywhere: one lane per (block, trajectory) over the
+// batch-minor filtered and predicted moments, with that kernel's Markov step (fenrir_markov_step, fenrir_kernels.hpp).  At an
+// interval with off-grid observations it runs the hops from the batch-minor hop records -- G is read, not solved for -- with
+// the conditioning (dalton_observe, at MO = 1 too) between them; the table index i is wave-uniform.
 template <int P, int MO>
 __global__ void __launch_bounds__(64) fenrir_bwd_at_kernel(SolveArgs a, FenrirAt f) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
@@ -173,26 +173,10 @@ __global__ void __launch_bounds__(64) fenrir_bwd_at_kernel(SolveArgs a, FenrirAt
                 hop(pre);
             } while (i >= 0 && f.tab[4 * i + 1] != 0 && f.tab[4 * i] == n);
         } else {
-            double mf[P], Sf[P][P], mp[P], Sp[P][P], T[P][P], G[P][P];
+            double mf[P], Sf[P][P], mp[P], Sp[P][P], G[P][P];
             eval_at_load<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, a.B, a.D, n, blk, b, mf, Sf);
             eval_at_load<P, RK_LAYOUT_BATCH_MINOR>(a.mean_pred, a.var_pred, a.B, a.D, n + 1, blk, b, mp, Sp);   // solve.py:93-96
-            smooth_gain<P>(Q, Sf, Sp, T, G);                                    // A = G            (standard.py:175-176)
-            double bb[P], Cc[P][P], GT[P][P];
-            mm_nt<P, P, P>(G, T, GT);
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                bb[r] = mf[r] - dot<P>(G[r], mp);                               // b = mu_f - G mu-   (standard.py:368)
-#pragma unroll
-                for (int c = 0; c < P; ++c) Cc[r][c] = Sf[r][c] - GT[r][c];     // C = Sigma_f - G T^T (standard.py:369-370)
-            }
-            double nm[P], nS[P][P];
-            predict_block<P>(G, Cc, bm, bS, nm, nS);                            // A m + 0, A S A^T + C (standard.py:57-59)
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                bm[r] = nm[r] + bb[r];
-#pragma unroll
-                for (int c = 0; c < P; ++c) bS[r][c] = nS[r][c];
-            }
+            fenrir_markov_step<P>(Q, mf, Sf, mp, Sp, bm, bS, G);
         }
         if (i >= 0 && f.tab[4 * i + 1] == 0 && f.tab[4 * i] == n) observe();   // fenrir.py:155-170
     }

@@ -13,6 +13,7 @@
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
 #include "solve_small_kernels.hpp"
+#include "fenrir_kernels.hpp"
 
 namespace rk {
 
@@ -190,7 +191,6 @@ __global__ void __launch_bounds__(64) fenrir_bwd_kernel(SolveArgs a, const doubl
     if (l >= a.B * a.D) return;
     const int blk = l / a.B, b = l - blk * a.B;
     const size_t B = (size_t)a.B;
-    const double LOG_2PI = 1.83787706640934548356;
     double Q[P][P], R[P][P];
     load_block_consts<P>(a, blk, b, Q, R);
     double bm[P], bS[P][P];
@@ -198,102 +198,11 @@ __global__ void __launch_bounds__(64) fenrir_bwd_kernel(SolveArgs a, const doubl
     else load_filt<P>(a, a.N, blk, b, bm, bS);                               // terminal point (fenrir.py:186-188)
     double acc = 0.0;
     int i = n_obs - 1;
-    // forecast (standard.py:333-335) + log-density + update (standard.py:93-102) with observation i
+    // conditioning on observation i: forecast (standard.py:333-335) + log-density + update (standard.py:93-102)
+    const DaltonObs o{obs, obs_w, obs_v, obs_ind, n_obs};
     auto observe = [&](double (&m)[P], double (&S)[P][P]) {
-        if constexpr (MO == 1) {
-            double D[P], SD[P];
-#pragma unroll
-            for (int k = 0; k < P; ++k) D[k] = obs_w[((size_t)i * a.D + blk) * P + k];
-            const double y = obs[(size_t)i * a.D + blk], Om = obs_v[(size_t)i * a.D + blk];
-            const double mean_fore = dot<P>(D, m);
-#pragma unroll
-            for (int r = 0; r < P; ++r) SD[r] = dot<P>(S[r], D);                // Sigma D^T
-            double DS[P];
-#pragma unroll
-            for (int c = 0; c < P; ++c) {
-                double t = D[0] * S[0][c];
-#pragma unroll
-                for (int k = 1; k < P; ++k) t = fma(D[k], S[k][c], t);
-                DS[c] = t;                                                      // D Sigma
-            }
-            const double w = dot<P>(DS, D) + Om;                                // var_fore
-            const double z = y - mean_fore;
-            if (fabs(w) > 1e-8) acc += -0.5 * (z * z / w + log(w)) - 0.5 * LOG_2PI;
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                const double K = SD[r] / w;                                     // solve_var with a 1 x 1 system
-                m[r] = fma(K, z, m[r]);
-#pragma unroll
-                for (int c = 0; c < P; ++c) S[r][c] = fma(-K, DS[c], S[r][c]);
-            }
-        } else {
-            // vector observation of this block: y (MO), D (MO x P), Omega (MO x MO)
-            double D[MO][P], y[MO], Wf[MO][MO], DS[MO][P], X[MO][P], z[MO];
-            const size_t ib = (size_t)i * a.D + blk;
-#pragma unroll
-            for (int j = 0; j < MO; ++j) {
-                y[j] = obs[ib * MO + j];
-#pragma unroll
-                for (int k = 0; k < P; ++k) D[j][k] = obs_w[(ib * MO + j) * P + k];
-            }
-#pragma unroll
-            for (int j = 0; j < MO; ++j) {
-                z[j] = y[j] - dot<P>(D[j], m);                                   // x_meas - (D mu + 0)
-#pragma unroll
-                for (int c = 0; c < P; ++c) {
-                    double t = D[j][0] * S[0][c];
-#pragma unroll
-                    for (int k = 1; k < P; ++k) t = fma(D[j][k], S[k][c], t);
-                    DS[j][c] = t;                                               // D Sigma  (var_meas_state_pred)
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < MO; ++j)
-#pragma unroll
-                for (int l2 = 0; l2 < MO; ++l2) Wf[j][l2] = dot<P>(DS[j], D[l2]) + obs_v[(ib * MO + j) * MO + l2];   // var_fore
-            {   // log N(y; D mu, var_fore) by eigendecomposition (utils.py:60-78)
-                double Aw[MO][MO], w[MO], V[MO][MO];
-#pragma unroll
-                for (int j = 0; j < MO; ++j)
-#pragma unroll
-                    for (int l2 = 0; l2 < MO; ++l2) Aw[j][l2] = 0.5 * (Wf[j][l2] + Wf[l2][j]);
-                sym_eig_jacobi<MO>(Aw, w, V);
-#pragma unroll
-                for (int k = 0; k < MO; ++k) {
-                    double zk = 0.0;
-#pragma unroll
-                    for (int j = 0; j < MO; ++j) zk = fma(V[j][k], z[j], zk);
-                    if (fabs(w[k]) > 1e-8) acc += -0.5 * (zk * zk / w[k] + log(w[k])) - 0.5 * LOG_2PI;
-                }
-            }
-            // K^T = solve(var_fore, (Sigma D^T)^T) by LU with partial pivoting (utils.py:119)
-#pragma unroll
-            for (int j = 0; j < MO; ++j)
-#pragma unroll
-                for (int r = 0; r < P; ++r) X[j][r] = dot<P>(S[r], D[j]);        // (Sigma D^T)^T, row j
-            lu_solve<MO, P>(Wf, X);
-            double dm[P], dS[P][P];
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                double t = X[0][r] * z[0];
-#pragma unroll
-                for (int j = 1; j < MO; ++j) t = fma(X[j][r], z[j], t);
-                dm[r] = t;
-#pragma unroll
-                for (int c = 0; c < P; ++c) {
-                    double u = X[0][r] * DS[0][c];
-#pragma unroll
-                    for (int j = 1; j < MO; ++j) u = fma(X[j][r], DS[j][c], u);
-                    dS[r][c] = u;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                m[r] = m[r] + dm[r];                                            // mu + K (y - D mu)
-#pragma unroll
-                for (int c = 0; c < P; ++c) S[r][c] = S[r][c] - dS[r][c];       // Sigma - K (D Sigma)
-            }
-        }
+        if constexpr (MO == 1) fenrir_observe_scalar<P>(o, (size_t)i * a.D + blk, m, S, acc);
+        else dalton_observe<P, MO>(o, (size_t)i * a.D + blk, m, S, acc);
         --i;
     };
     constexpr int ITEM = 3 * P * P + 2 * P;
@@ -310,7 +219,7 @@ __global__ void __launch_bounds__(64) fenrir_bwd_kernel(SolveArgs a, const doubl
     if (i >= 0 && obs_ind[i] >= a.N) observe(bm, bS);                      // fenrir.py:189-209
     if constexpr (STORE) keep(a.N, P + P * P, bm, bS);
     for (int n = a.N - 1; n >= 0; --n) {
-        double mf[P], Sf[P][P], mp[P], Sp[P][P], T[P][P], G[P][P];
+        double mf[P], Sf[P][P], mp[P], Sp[P][P], G[P][P];
         if constexpr (TILES) {
             load_filt_tiles<P>(a, tiles, n, blk, b, mf, Sf);
             predict_block<P>(Q, R, mf, Sf, mp, Sp);                         // pred[n + 1] from filt[n]
@@ -326,23 +235,7 @@ __global__ void __launch_bounds__(64) fenrir_bwd_kernel(SolveArgs a, const doubl
                 for (int c = 0; c < P; ++c) Sp[r][c] = vi[((size_t)r * P + c) * B];
             }
         }
-        smooth_gain<P>(Q, Sf, Sp, T, G);                                    // A = G            (standard.py:175-176)
-        double bb[P], Cc[P][P], GT[P][P];
-        mm_nt<P, P, P>(G, T, GT);
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            bb[r] = mf[r] - dot<P>(G[r], mp);                               // b = mu_f - G mu-   (standard.py:368)
-#pragma unroll
-            for (int c = 0; c < P; ++c) Cc[r][c] = Sf[r][c] - GT[r][c];     // C = Sigma_f - G T^T (standard.py:369-370)
-        }
-        double nm[P], nS[P][P];
-        predict_block<P>(G, Cc, bm, bS, nm, nS);                            // A m + 0, A S A^T + C (standard.py:57-59)
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            bm[r] = nm[r] + bb[r];
-#pragma unroll
-            for (int c = 0; c < P; ++c) bS[r][c] = nS[r][c];
-        }
+        fenrir_markov_step<P>(Q, mf, Sf, mp, Sp, bm, bS, G);
         if constexpr (STORE) {
             keep(n, 0, bm, bS);
             double* o = states + (((size_t)n * a.D + blk) * ITEM + 2 * (P + P * P)) * B + b;

@@ -272,6 +272,14 @@ __global__ void __launch_bounds__(256) bwd_mv_tile3_kernel(SolveArgs a, double* 
 // with the same producers, a consumer that stores nothing, conditions on the observations (rare: a slow per-step path
 // for the chunks that contain one) and accumulates their log-densities.  Predicted moments are re-evaluated from the
 // filtered ones like everywhere on the tile path, so the forward pass is the MFMA-tile forward kernel.
+//
+// fenrir_at is the same kernel for observations between grid nodes: fenrir_tile3_body<AT> is the one
+// body of both, and everything off-grid in it sits under `if constexpr (AT)`.  What differs is the per-step path of the chunks
+// that hold an event.  At the step for node n of an interval (t_n, t_n+1) with off-grid observations the consumer does not use
+// the LDS item: it reads the interval's hop tiles [M- | G~^T | M_f] = [e_j | diag(G_j, 1)^T | s_j] from the workspace
+// (fenrir_at_hops_kernel, fenrir_at_kernels.hpp) and runs, per hop j = k .. 0, the same two MFMAs, with observe() after each of
+// the hops k .. 1; hop 0 lands on node n, where an on-node observation is handled as on the grid.  Interval 0 is not a loop
+// step: its hops k .. 1 go after the loop, and the state at t_min is filt[0] whatever came before.
 struct FenrirObs {
     const double *obs, *obs_w, *obs_v;      // (n_obs, D), (n_obs, D, 3), (n_obs, D)
     const int32_t* obs_ind;                 // (n_obs,) ascending grid indices
@@ -279,7 +287,9 @@ struct FenrirObs {
     double* logdens;                        // (B,), zeroed by the caller
 };
 
-__global__ void __launch_bounds__(256) fenrir_bwd_tile3_kernel(SolveArgs a, const double* __restrict__ tiles, int D, FenrirObs ob) {
+// OB = FenrirObs (AT = false: observations on nodes, obs_ind) or FenrirAt (AT = true: table rows, hop records)
+template <bool AT, class OB>
+__device__ __forceinline__ void fenrir_tile3_body(const SolveArgs& a, const double* __restrict__ tiles, int D, const OB& ob) {
     __shared__ __attribute__((aligned(16))) char lds_all[2 * BUF_BYTES];
     __shared__ __attribute__((aligned(16))) char zones[3 * ZONE_BYTES];      // the producers' prefetch landing zones
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;    // 0 = consumer; producers q = wave - 1 own ch = q (mod 3)
@@ -317,7 +327,19 @@ __global__ void __launch_bounds__(256) fenrir_bwd_tile3_kernel(SolveArgs a, cons
         double Ms = in_tile ? my[(size_t)a.N * tstride] : e3;       // terminal point filt[N]   (fenrir.py:186-188)
         double acc = 0.0;
         int i = ob.n_obs - 1;
-        int next = i >= 0 ? ob.obs_ind[i] : -1;                     // grid index of the next observation (backwards in time)
+        // node of the next observation (backwards in time) and, off the grid, whether it lies inside the interval (t_next,
+        // t_next+1) and not on the node; wave-uniform
+        int next = -1;
+        [[maybe_unused]] int off = 0;
+        auto look = [&]() {
+            if constexpr (AT) {
+                next = i >= 0 ? ob.tab[4 * i] : -1;
+                off = i >= 0 ? ob.tab[4 * i + 1] : 0;
+            } else {
+                next = i >= 0 ? ob.obs_ind[i] : -1;
+            }
+        };
+        look();
         // Conditioning on observation i (forecast standard.py:333-335, log-density, update standard.py:93-102) is the
         // forward update in tile form with the measurement row X_w = [D_0, D_1, D_2 | -y] and var_meas = Omega:
         //     WS = MF(X_w, M) = [D Sigma | D mu - y] ; Z = MF(M^T with row 3 zeroed, X_w) = Sigma D^T ; w = MF(Z, X_w) + Omega
@@ -335,144 +357,31 @@ __global__ void __launch_bounds__(256) fenrir_bwd_tile3_kernel(SolveArgs a, cons
             const double K = Z / w;                                             // solve_var with a 1 x 1 system
             Ms = fma(-K, WS, Ms);
             --i;
-            next = i >= 0 ? ob.obs_ind[i] : -1;
+            look();
         };
-        if (next >= a.N) observe();                                 // fenrir.py:189-209
-        __syncthreads();                                            // tick -3
-        __syncthreads();                                            // tick -2
-        __syncthreads();                                            // tick -1: chunk 0 is in LDS
-        for (int t = 0; t < n_chunks; ++t) {
-            const char* in = lds_raw + (t & 1) * BUF_BYTES;
-            const int n_hi = a.N - 1 - t * CHUNK;
-            const int cnt = __builtin_amdgcn_readfirstlane(n_hi >= CHUNK ? CHUNK : n_hi);   // steps n_hi .. n_hi-cnt+1
-            const bool has_obs = next > n_hi - cnt;
-            if (cnt == CHUNK && !has_obs) {
-                // the 16-step dependent chain of bwd_mv_tile3_kernel, nothing stored:
-                //     D = M - M- ; V = MF(D, G~^T) ; M = MF(V, G~^T, M_f)   = G M G^T + (M_f - G M- G^T)  (standard.py:366-370)
-                constexpr int LOOKAHEAD = 4;
-                double Mp[CHUNK], Gt[CHUNK], Mf[CHUNK];
-                auto load = [&](int s) {
-                    const char* q = in + roff[s & 3] + s * 4 * ITEM_BYTES;
-                    Mp[s] = *(const double*)(q);
-                    Gt[s] = *(const double*)(q + 128);
-                    Mf[s] = *(const double*)(q + 256);
-                };
-#pragma unroll
-                for (int s = 0; s < LOOKAHEAD; ++s) load(s);
-                double Dm = Ms - Mp[0];
-#pragma unroll
-                for (int s = 0; s < CHUNK; ++s) {
-                    if (s + LOOKAHEAD < CHUNK) load(s + LOOKAHEAD);
-                    __builtin_amdgcn_sched_barrier(0);
-                    const double V1 = MF(Dm, Gt[s], 0.0);
-                    Ms = MF(V1, Gt[s], Mf[s]);
-                    if (s + 1 < CHUNK) Dm = Ms - Mp[s + 1];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-                for (int s = 0; s < cnt; ++s) {
-                    const char* q = in + lds_byte(s, g, 0, idx);
-                    const double Mp = *(const double*)(q), Gt = *(const double*)(q + 128), Mf = *(const double*)(q + 256);
-                    const double V1 = MF(Ms - Mp, Gt, 0.0);
-                    Ms = MF(V1, Gt, Mf);
-                    if (next == n_hi - s) observe();                            // fenrir.py:155-170
-                }
-            }
-            __syncthreads();
-        }
-        // n = 0: filt[0] = (ode_init, 0) has G = 0, so the state there is filt[0] itself whatever came before
-        if (next == 0) {
-            Ms = in_tile ? my[0] : e3;
-            observe();
-        }
-        if (valid && r == 0 && c == 0) atomicAdd(&ob.logdens[b], acc);
-    }
-}
-
-// ---- fenrir_at on the tile path ------------------------------------------------------------------
-// The sibling of fenrir_bwd_tile3_kernel for observations between grid nodes: the same producers, LDS hand-off and 16-step
-// branch-free chain; what differs is the per-step path of the chunks that hold an event.  At the step for node n of an interval
-// (t_n, t_n+1) with off-grid observations the consumer does not use the LDS item: it reads the interval's hop tiles
-// [M- | G~^T | M_f] = [e_j | diag(G_j, 1)^T | s_j] from the workspace (fenrir_at_hops_kernel, fenrir_at_kernels.hpp) and runs, per
-// hop j = k .. 0, the same two MFMAs, with observe() after each of the hops k .. 1; hop 0 lands on node n, where an on-node
-// observation is handled as in the sibling.  Interval 0 is not a loop step: its hops k .. 1 go after the loop, and the state at
-// t_min is filt[0] whatever came before.
-__global__ void __launch_bounds__(256) fenrir_bwd_at_tile3_kernel(SolveArgs a, const double* __restrict__ tiles, int D, FenrirAt ob) {
-    __shared__ __attribute__((aligned(16))) char lds_all[2 * BUF_BYTES];
-    __shared__ __attribute__((aligned(16))) char zones[3 * ZONE_BYTES];      // the producers' prefetch landing zones
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;    // 0 = consumer; producers q = wave - 1 own ch = q (mod 3)
-    const int n_tiles = a.B * D;
-    const size_t tstride = (size_t)n_tiles * TILE_DOUBLES;
-    const int n_chunks = (a.N - 1 + CHUNK - 1) / CHUNK;            // steps n = N-1 .. 1
-
-    // constant entries of the hand-off tiles (row 3 = e_3; column 3 of G~^T = e_3) are written once
-    for (int i = threadIdx.x; i < 2 * 64 * 3 * 16; i += 256) {
-        const int idx = i & 15, which = (i >> 4) % 3, item = ((i >> 4) / 3) & 63, buf = i / (64 * 3 * 16);
-        const double v = (idx == 15) ? 1.0 : 0.0;
-        *(double*)(lds_all + buf * BUF_BYTES + lds_byte(item >> 2, item & 3, which, idx)) = v;
-    }
-    __syncthreads();
-
-    const int tw = blockIdx.x;                                     // tile-wave index: tiles 4 tw .. 4 tw + 3
-    char* const lds_raw = lds_all;
-
-    if (wave >= 1) {
-        tile3_gain_producers(a, tiles, D, tw, wave, lane, n_tiles, tstride, n_chunks, lds_raw, zones);
-    } else {
-        // ---------------- consumer: the backward filter on MFMA tiles ----------------
-        __builtin_amdgcn_s_setprio(3);
-        const int r = lane >> 4, g = (lane >> 2) & 3, c = lane & 3, idx = r * 4 + c;
-        const int tau_raw = tw * 4 + g;
-        const bool valid = tau_raw < n_tiles;
-        const int tau = valid ? tau_raw : n_tiles - 1;
-        const int b = tau / D, blk = tau - b * D;
-        const bool in_tile = valid && r < 3;
-        const double e3 = (r == 3 && c == 3) ? 1.0 : 0.0, I4 = r == c ? 1.0 : 0.0;
-        const double* const my = tiles + (size_t)tau * TILE_DOUBLES + idx;
-        const double* const my_hops = ob.hops + (size_t)tau * FENRIR_AT_TILE_REC + idx;
-        const int n_rec = ob.n_pre + ob.n_post;
-        int roff[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) roff[k] = lds_byte(k, g, 0, idx) - k * 4 * ITEM_BYTES;
-        double Ms = in_tile ? my[(size_t)a.N * tstride] : e3;       // terminal point filt[N]   (fenrir.py:186-188)
-        double acc = 0.0;
-        int i = ob.n_obs - 1;
-        // node and off-grid flag of the next observation (backwards in time); wave-uniform
-        int next = i >= 0 ? ob.tab[4 * i] : -1;
-        int off = i >= 0 ? ob.tab[4 * i + 1] : 0;
-        // fenrir_bwd_tile3_kernel's observe(): forecast, log-density and update in tile form with X_w = [D_0, D_1, D_2 | -y]
-        auto observe = [&]() {
-            const double xw = valid ? (r < 3 ? ob.obs_w[((size_t)i * D + blk) * 3 + r] : -ob.obs[(size_t)i * D + blk]) : 0.0;
-            const double Om = valid ? ob.obs_v[(size_t)i * D + blk] : 1.0;
-            double MsT = MF(Ms, I4, 0.0);
-            MsT = r == 3 ? 0.0 : MsT;
-            const double WS = MF(xw, Ms, 0.0);
-            const double Z = MF(MsT, xw, 0.0);
-            const double w = MF(Z, xw, 0.0) + Om;                               // var_fore
-            const double z = -quad_bcast3(WS);                                  // y - D mu
-            if (fabs(w) > 1e-8) acc += -0.5 * (z * z / w + log(w)) - 0.5 * 1.83787706640934548356;   // utils.py:60-78
-            const double K = Z / w;                                             // solve_var with a 1 x 1 system
-            Ms = fma(-K, WS, Ms);
-            --i;
-            next = i >= 0 ? ob.tab[4 * i] : -1;
-            off = i >= 0 ? ob.tab[4 * i + 1] : 0;
-        };
-        // the carry through the hop of record `rec` (clamped): the chain's step with the item read from the workspace
-        auto hop = [&](int rec) {
-            const double* q = my_hops + (size_t)fenrir_at_clamp(rec, n_rec) * n_tiles * FENRIR_AT_TILE_REC;
-            const double Mp = q[0], Gt = q[16], Mf = q[32];
+        // one step of the chain: the carry through the item [M- | G~^T | M_f]
+        auto step = [&](double Mp, double Gt, double Mf) {
             const double V1 = MF(Ms - Mp, Gt, 0.0);
             Ms = MF(V1, Gt, Mf);
         };
-        // interval n holds the observations i, i - 1, ..: hop k behind the last one, then condition and hop in turn; the
-        // last hop (onto node n) is left out for interval 0
-        auto interval = [&](int n, bool to_node) {
-            hop(ob.n_pre + fenrir_at_clamp(ob.tab[4 * i + 3], ob.n_post));
-            do {
-                const int pre = fenrir_at_clamp(ob.tab[4 * i + 2], ob.n_pre);
-                observe();
-                if (to_node || (off && next == n)) hop(pre);
-            } while (off && next == n);
+        // interval n holds the off-grid observations i, i - 1, ..: hop k behind the last one, then condition and hop in turn,
+        // each hop a step with the item of record `rec` (clamped) read from the workspace; the last hop (onto node n) is left
+        // out for interval 0
+        [[maybe_unused]] auto interval = [&](int n, bool to_node) {
+            if constexpr (AT) {
+                const double* const my_hops = ob.hops + (size_t)tau * FENRIR_AT_TILE_REC + idx;
+                const int n_rec = ob.n_pre + ob.n_post;
+                auto hop = [&](int rec) {
+                    const double* q = my_hops + (size_t)fenrir_at_clamp(rec, n_rec) * n_tiles * FENRIR_AT_TILE_REC;
+                    step(q[0], q[16], q[32]);
+                };
+                hop(ob.n_pre + fenrir_at_clamp(ob.tab[4 * i + 3], ob.n_post));
+                do {
+                    const int pre = fenrir_at_clamp(ob.tab[4 * i + 2], ob.n_pre);
+                    observe();
+                    if (to_node || (off && next == n)) hop(pre);
+                } while (off && next == n);
+            }
         };
         if (next >= a.N && !off) observe();                         // fenrir.py:189-209
         __syncthreads();                                            // tick -3
@@ -509,20 +418,21 @@ __global__ void __launch_bounds__(256) fenrir_bwd_at_tile3_kernel(SolveArgs a, c
             } else {
                 for (int s = 0; s < cnt; ++s) {
                     const int n = n_hi - s;
-                    if (off && next == n) {
+                    bool hops = false;                                          // the step's interval holds observations
+                    if constexpr (AT) hops = off && next == n;
+                    if (hops) {
                         interval(n, true);
                     } else {
                         const char* q = in + lds_byte(s, g, 0, idx);
-                        const double Mp = *(const double*)(q), Gt = *(const double*)(q + 128), Mf = *(const double*)(q + 256);
-                        const double V1 = MF(Ms - Mp, Gt, 0.0);
-                        Ms = MF(V1, Gt, Mf);
+                        step(*(const double*)(q), *(const double*)(q + 128), *(const double*)(q + 256));
                     }
                     if (!off && next == n) observe();                           // fenrir.py:155-170
                 }
             }
             __syncthreads();
         }
-        if (off && next == 0) interval(0, false);                   // interval 0: hops k .. 1
+        if constexpr (AT)
+            if (off && next == 0) interval(0, false);               // interval 0: hops k .. 1
         // n = 0: filt[0] = (ode_init, 0) has G = 0, so the state there is filt[0] itself whatever came before
         if (!off && next == 0) {
             Ms = in_tile ? my[0] : e3;
@@ -530,6 +440,14 @@ __global__ void __launch_bounds__(256) fenrir_bwd_at_tile3_kernel(SolveArgs a, c
         }
         if (valid && r == 0 && c == 0) atomicAdd(&ob.logdens[b], acc);
     }
+}
+
+__global__ void __launch_bounds__(256) fenrir_bwd_tile3_kernel(SolveArgs a, const double* __restrict__ tiles, int D, FenrirObs ob) {
+    fenrir_tile3_body<false>(a, tiles, D, ob);
+}
+
+__global__ void __launch_bounds__(256) fenrir_bwd_at_tile3_kernel(SolveArgs a, const double* __restrict__ tiles, int D, FenrirAt ob) {
+    fenrir_tile3_body<true>(a, tiles, D, ob);
 }
 
 // ---- backward sampler (solve.py:162-204): x_n = mu_f + G (x_{n+1} - mu-) + L~ z_n --------------------------------

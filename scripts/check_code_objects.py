@@ -90,7 +90,7 @@ def demangled(name):
 # other): a few registers too many make the two workgroups of a CU run one after the other without any other symptom
 # (found with per-workgroup time stamps on bwd_mv_tile4_kernel, which had crept to 260 registers: DESIGN.md).
 MIN_WORKGROUPS_PER_CU = {"19bwd_mv_tile3_kernel": 2, "19bwd_mv_tile4_kernel": 2, "20bwd_sim_tile3_kernel": 2,
-                         "23fenrir_bwd_tile3_kernel": 2}
+                         "23fenrir_bwd_tile3_kernel": 2, "26fenrir_bwd_at_tile3_kernel": 2}
 
 
 def workgroups_per_cu(k):
