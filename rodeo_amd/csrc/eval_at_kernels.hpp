@@ -9,6 +9,7 @@
 #pragma once
 #include "../../include/rodeo_kalman.h"
 #include "kalman_small.hpp"
+#include "records.hpp"
 #include "solve_args.hpp"
 
 namespace rk {
@@ -22,55 +23,6 @@ struct EvalAtArgs {
     int trans_b, noise_b;
     double *mean_out, *var_out;     // (B, T, D, P) and (B, T, D, P, P): the reference's layout, batch first
 };
-
-// Lanes run fastest over what is contiguous in the records: (trajectory, block) for the tile records (time, B, D, record),
-// the trajectory for the batch-minor columns.
-template <int LAYOUT>
-__device__ __forceinline__ void eval_at_lane(int l, int B, int D, int& blk, int& b) {
-    if constexpr (LAYOUT == RK_LAYOUT_BATCH_MINOR) {
-        blk = l / B;
-        b = l - blk * B;
-    } else {
-        b = l / D;
-        blk = l - b * D;
-    }
-}
-
-// (mean, var) of time n from the records of one solver call, in the four layouts of rk_solve_layout: RK_LAYOUT_TILE3 rows
-// [Sigma[i][0..2] | mu[i]], RK_LAYOUT_TILE4 / RK_LAYOUT_TILEP [Sigma row-major | mu], batch-minor (N+1, D, P[, P], B).
-template <int P, int LAYOUT>
-__device__ __forceinline__ void eval_at_load(const double* mean, const double* var, int B, int D, int n, int blk, int b,
-                                             double (&m)[P], double (&S)[P][P]) {
-    if constexpr (LAYOUT == RK_LAYOUT_BATCH_MINOR) {
-        const size_t Bs = (size_t)B;
-        const double* mi = mean + ((size_t)n * D + blk) * P * Bs + b;
-        const double* vi = var + ((size_t)n * D + blk) * P * P * Bs + b;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            m[i] = mi[(size_t)i * Bs];
-#pragma unroll
-            for (int j = 0; j < P; ++j) S[i][j] = vi[((size_t)i * P + j) * Bs];
-        }
-    } else if constexpr (LAYOUT == RK_LAYOUT_TILE3) {
-        static_assert(P == 3, "RK_LAYOUT_TILE3 is the n_bstate = 3 record");
-        const double* rec = (const double*)__builtin_assume_aligned(var + ((size_t)n * B * D + (size_t)b * D + blk) * 12, 32);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) S[i][j] = rec[4 * i + j];
-            m[i] = rec[4 * i + 3];
-        }
-    } else {
-        const double* rec =
-            (const double*)__builtin_assume_aligned(var + ((size_t)n * B * D + (size_t)b * D + blk) * (P * P + P), 16);
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            m[i] = rec[P * P + i];
-#pragma unroll
-            for (int j = 0; j < P; ++j) S[i][j] = rec[i * P + j];
-        }
-    }
-}
 
 // matrix `which` (0: over h1, 1: over h2) of quadruple `slot`
 template <int P>
@@ -95,14 +47,14 @@ __global__ void __launch_bounds__(64) eval_at_kernel(EvalAtArgs a) {
     const int l = (blockIdx.x - q * nbx) * 64 + threadIdx.x;
     if (l >= a.B * a.D) return;
     int blk, b;
-    eval_at_lane<LAYOUT>(l, a.B, a.D, blk, b);
+    record_lane<LAYOUT>(l, a.B, a.D, blk, b);
     const bool on = a.query[3 * q + 1] != 0;
     const int n = min(max(a.query[3 * q], 0), on ? a.N : a.N - 1);
     const int slot = min(max(a.query[3 * q + 2], 0), a.n_quad - 1);
 
     double mu[P], S[P][P];
     if (on) {
-        eval_at_load<P, LAYOUT>(a.smean, a.svar, a.B, a.D, n, blk, b, mu, S);
+        load_moments<P, LAYOUT>(a.smean, a.svar, a.B, a.D, n, blk, b, mu, S);
     } else {
         // Three stages, each with its own loads.  The scheduler would issue every load up front and hold 4 P^2 + 2 P (prior) +
         // 2 (P^2 + P) (records) doubles under the whole computation (P = 6 spilled): the barriers keep Q1, R1 and the filtered
@@ -111,7 +63,7 @@ __global__ void __launch_bounds__(64) eval_at_kernel(EvalAtArgs a) {
         {
             double Q1[P][P], R1[P][P], mf[P], Sf[P][P];
             eval_at_prior<P>(a, slot, 0, blk, b, Q1, R1);
-            eval_at_load<P, LAYOUT>(a.fmean, a.fvar, a.B, a.D, n, blk, b, mf, Sf);
+            load_moments<P, LAYOUT>(a.fmean, a.fvar, a.B, a.D, n, blk, b, mf, Sf);
             predict_block<P>(Q1, R1, mf, Sf, mt, St);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -123,7 +75,7 @@ __global__ void __launch_bounds__(64) eval_at_kernel(EvalAtArgs a) {
             smooth_gain<P>(Q2, St, Sp, Tm, G);
         }
         __builtin_amdgcn_sched_barrier(0);
-        eval_at_load<P, LAYOUT>(a.smean, a.svar, a.B, a.D, n + 1, blk, b, mu, S);
+        load_moments<P, LAYOUT>(a.smean, a.svar, a.B, a.D, n + 1, blk, b, mu, S);
         smooth_mv_block<P>(G, mt, St, mp, Sp, mu, S);
     }
     double* mo = a.mean_out + ((((size_t)b * a.T + q) * a.D + blk) * P);

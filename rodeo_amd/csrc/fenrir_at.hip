@@ -38,7 +38,7 @@ static int fenrir_at_route(const rk_solve_cfg* c, int n_bobs, bool* tile) {
 }
 
 static size_t fenrir_at_ws_doubles(const rk_solve_cfg* c, bool tile, int n_rec) {
-    const size_t per = tile ? (size_t)FENRIR_AT_TILE_REC : (size_t)fenrir_at_lane_rec(c->n_bstate);
+    const size_t per = tile ? (size_t)FENRIR_AT_TILE_REC : (size_t)FenrirAtLaneRec(c->n_bstate).width;
     return (size_t)n_rec * c->n_block * per * (size_t)c->n_traj;
 }
 

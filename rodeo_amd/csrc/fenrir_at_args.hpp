@@ -25,7 +25,12 @@ struct FenrirAt {
 };
 
 constexpr int FENRIR_AT_TILE_REC = 48;      // doubles per (record, tile) on the tile route
-constexpr int fenrir_at_lane_rec(int p) { return 3 * p * p + 2 * p; }   // doubles per (record, block, trajectory) on the lanes
+// the lane record [mu(s), Sigma(s) | mu(e), Sigma(e) | G] of n_bstate = p: element offsets of its fields and its doubles per
+// (record, block, trajectory)
+struct FenrirAtLaneRec {
+    int s, e, G, width;
+    constexpr explicit FenrirAtLaneRec(int p) : s(0), e(p + p * p), G(2 * (p + p * p)), width(3 * p * p + 2 * p) {}
+};
 
 __device__ __forceinline__ int fenrir_at_clamp(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 

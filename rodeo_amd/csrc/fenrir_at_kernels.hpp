@@ -10,7 +10,7 @@
 #pragma once
 #include "../../include/rodeo_kalman.h"
 #include "fenrir_kernels.hpp"
-#include "eval_at_kernels.hpp"
+#include "records.hpp"
 #include "fenrir_at_args.hpp"
 
 namespace rk {
@@ -34,7 +34,7 @@ __device__ __forceinline__ void fenrir_at_pair(const double* q, const double* r,
 // or, for an interval's last observation, the hop behind it (which = 1, record n_pre + post slot) -- so the table row, the
 // trip count of the chain and every branch are the same in all lanes of a wave.  Hop ids of on-node observations and of
 // observations without a post slot have no record and leave at once.  The lane walks the interval's chain from filt[n]
-// (read through the record accessor of the plan's layout) up to its hop, serially: an interval with k observations costs its
+// (read through load_moments in the plan's layout) up to its hop, serially: an interval with k observations costs its
 // last hop k + 1 predicts, and nothing here or in the workspace (one record per pair) bounds k.  Indices are clamped to the
 // buffers.
 // LAYOUT = RK_LAYOUT_TILE3 (P = 3): a.var holds the filter's tile records, the record written is the tile form;
@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(64) fenrir_at_hops_kernel(SolveArgs a, FenrirA
     const int l = (blockIdx.x - q * nbx) * 64 + threadIdx.x;
     if (l >= a.B * a.D) return;
     int blk, b;
-    eval_at_lane<LAYOUT>(l, a.B, a.D, blk, b);
+    record_lane<LAYOUT>(l, a.B, a.D, blk, b);
     const int i = fenrir_at_clamp(q >> 1, f.n_obs), which = q & 1;
     const int32_t* row = f.tab + 4 * i;
     if (row[1] == 0 || (which && row[3] < 0)) return;                       // (wave-uniform)
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(64) fenrir_at_hops_kernel(SolveArgs a, FenrirA
     while (i0 > 0 && f.tab[4 * (i0 - 1) + 1] != 0 && f.tab[4 * (i0 - 1)] == row[0]) --i0;
 
     double ms[P], Ss[P][P];
-    eval_at_load<P, LAYOUT>(a.mean, a.var, a.B, a.D, n, blk, b, ms, Ss);      // s_0 = filt[n]
+    load_moments<P, LAYOUT>(a.mean, a.var, a.B, a.D, n, blk, b, ms, Ss);      // s_0 = filt[n]
     for (int m = i0; m < i + which; ++m) {                                    // s_j+1 = predict(s_j; Q_j, R_j)
         double Qm[P][P], Rm[P][P], mt[P], St[P][P];
         fenrir_at_pair<P>(f.pre_q, f.pre_r, fenrir_at_clamp(f.tab[4 * m + 2], f.n_pre), a.D, blk, f.prior_b, a.B, b, Qm, Rm);
@@ -104,23 +104,24 @@ __global__ void __launch_bounds__(64) fenrir_at_hops_kernel(SolveArgs a, FenrirA
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[16 * w + 12 + c] = c == 3 ? 1.0 : 0.0;
     } else {
+        constexpr FenrirAtLaneRec REC(P);
         const size_t B = (size_t)a.B;
-        double* o = f.hops + ((size_t)rec * a.D + blk) * fenrir_at_lane_rec(P) * B + b;
+        double* o = f.hops + ((size_t)rec * a.D + blk) * REC.width * B + b;
 #pragma unroll
         for (int r = 0; r < P; ++r) {
-            o[(size_t)r * B] = ms[r];
-            o[(size_t)(P + P * P + r) * B] = me[r];
+            o[(size_t)(REC.s + r) * B] = ms[r];
+            o[(size_t)(REC.e + r) * B] = me[r];
 #pragma unroll
             for (int c = 0; c < P; ++c) {
-                o[(size_t)(P + r * P + c) * B] = Ss[r][c];
-                o[(size_t)(2 * P + P * P + r * P + c) * B] = Se[r][c];
-                o[(size_t)(2 * P + 2 * P * P + r * P + c) * B] = G[r][c];
+                o[(size_t)(REC.s + P + r * P + c) * B] = Ss[r][c];
+                o[(size_t)(REC.e + P + r * P + c) * B] = Se[r][c];
+                o[(size_t)(REC.G + r * P + c) * B] = G[r][c];
             }
         }
     }
 }
 
-// fenrir_bwd_kernel<P, false, MO, false> (solve_small.hip) for observations anywhere: one lane per (block, trajectory) over the
+// fenrir_bwd_kernel<P, false, MO, false> (fenrir.hip) for observations anywhere: one lane per (block, trajectory) over the
 // batch-minor filtered and predicted moments, with that kernel's Markov step (fenrir_markov_step, fenrir_kernels.hpp).  At an
 // interval with off-grid observations it runs the hops from the batch-minor hop records -- G is read, not solved for -- with
 // the conditioning (dalton_observe, at MO = 1 too) between them; the table index i is wave-uniform.
@@ -130,6 +131,7 @@ __global__ void __launch_bounds__(64) fenrir_bwd_at_kernel(SolveArgs a, FenrirAt
     if (l >= a.B * a.D) return;
     const int blk = l / a.B, b = l - blk * a.B;
     const size_t B = (size_t)a.B;
+    constexpr FenrirAtLaneRec REC(P);
     double Q[P][P];
     {
         double R[P][P];
@@ -138,7 +140,7 @@ __global__ void __launch_bounds__(64) fenrir_bwd_at_kernel(SolveArgs a, FenrirAt
     DaltonObs o;
     o.obs = f.obs; o.obs_w = f.obs_w; o.obs_v = f.obs_v; o.obs_ind = nullptr; o.n_obs = f.n_obs;
     double bm[P], bS[P][P];
-    eval_at_load<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, a.B, a.D, a.N, blk, b, bm, bS);   // terminal point (fenrir.py:186-188)
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, a.B, a.D, a.N, blk, b, bm, bS);   // terminal point (fenrir.py:186-188)
     double acc = 0.0;
     int i = f.n_obs - 1;
     auto observe = [&]() {
@@ -147,17 +149,17 @@ __global__ void __launch_bounds__(64) fenrir_bwd_at_kernel(SolveArgs a, FenrirAt
     };
     // the carry through the hop of record `rec`: smooth_mv_block is the smooth_cond map applied to (m, M)
     auto hop = [&](int rec) {
-        const double* h = f.hops + ((size_t)rec * a.D + blk) * fenrir_at_lane_rec(P) * B + b;
+        const double* h = f.hops + ((size_t)rec * a.D + blk) * REC.width * B + b;
         double msj[P], Ssj[P][P], mej[P], Sej[P][P], G[P][P];
 #pragma unroll
         for (int r = 0; r < P; ++r) {
-            msj[r] = h[(size_t)r * B];
-            mej[r] = h[(size_t)(P + P * P + r) * B];
+            msj[r] = h[(size_t)(REC.s + r) * B];
+            mej[r] = h[(size_t)(REC.e + r) * B];
 #pragma unroll
             for (int c = 0; c < P; ++c) {
-                Ssj[r][c] = h[(size_t)(P + r * P + c) * B];
-                Sej[r][c] = h[(size_t)(2 * P + P * P + r * P + c) * B];
-                G[r][c] = h[(size_t)(2 * P + 2 * P * P + r * P + c) * B];
+                Ssj[r][c] = h[(size_t)(REC.s + P + r * P + c) * B];
+                Sej[r][c] = h[(size_t)(REC.e + P + r * P + c) * B];
+                G[r][c] = h[(size_t)(REC.G + r * P + c) * B];
             }
         }
         smooth_mv_block<P>(G, msj, Ssj, mej, Sej, bm, bS);
@@ -174,8 +176,8 @@ __global__ void __launch_bounds__(64) fenrir_bwd_at_kernel(SolveArgs a, FenrirAt
             } while (i >= 0 && f.tab[4 * i + 1] != 0 && f.tab[4 * i] == n);
         } else {
             double mf[P], Sf[P][P], mp[P], Sp[P][P], G[P][P];
-            eval_at_load<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, a.B, a.D, n, blk, b, mf, Sf);
-            eval_at_load<P, RK_LAYOUT_BATCH_MINOR>(a.mean_pred, a.var_pred, a.B, a.D, n + 1, blk, b, mp, Sp);   // solve.py:93-96
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, a.B, a.D, n, blk, b, mf, Sf);
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean_pred, a.var_pred, a.B, a.D, n + 1, blk, b, mp, Sp);   // solve.py:93-96
             fenrir_markov_step<P>(Q, mf, Sf, mp, Sp, bm, bS, G);
         }
         if (i >= 0 && f.tab[4 * i + 1] == 0 && f.tab[4 * i] == n) observe();   // fenrir.py:155-170

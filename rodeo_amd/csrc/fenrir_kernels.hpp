@@ -1,10 +1,17 @@
-// Fenrir's backward filter on the lanes: the pieces that fenrir_bwd_kernel (solve_small.hip, observations on grid nodes) and
+// Fenrir's backward filter on the lanes: the pieces that fenrir_bwd_kernel (fenrir.hip, observations on grid nodes) and
 // fenrir_bwd_at_kernel (fenrir_at_kernels.hpp, observations anywhere) share.  The vector-observation update of both is
 // dalton_observe (dalton_kernels.hpp).  Not part of the hiprtc program text (embed_sources.py).
 #pragma once
 #include "dalton_kernels.hpp"
 
 namespace rk {
+
+// The stored backward filter of fenrir's solve_mv (fenrir_bwd_kernel with STORE -> fenrir_smooth_kernel): per (time n, block) a
+// batch-minor item [m_pred, S_pred | m_filt, S_filt | A] of n_bstate = p; element offsets of its fields and its doubles
+struct FenrirItem {
+    int pred, filt, A, width;
+    constexpr explicit FenrirItem(int p) : pred(0), filt(p + p * p), A(2 * (p + p * p)), width(3 * p * p + 2 * p) {}
+};
 
 // One step of the backward Markov chain (smooth_cond, standard.py:366-370) as a Kalman prediction of the carry (bm, bS) from
 // time n + 1 to n, given filt[n] = (mf, Sf) and pred[n + 1] = (mp, Sp); G is the step's weight A

@@ -1,6 +1,6 @@
 // Fenrir's backward pass and data-adaptive smoother with kalman_type = "square-root"
 // (src/rodeo/inference/fenrir.py:292-296 and 421-426 select src/rodeo/kalmantv/square_root.py for every step map of
-// fenrir.py:86-259 and 333-402).  One lane per (block, trajectory), like the covariance-form kernels in solve_small.hip;
+// fenrir.py:86-259 and 333-402).  One lane per (block, trajectory), like the covariance-form kernels in fenrir.hip;
 // every `var` is a lower square-root factor: prior_pars[1] = chol(R), obs_var = chol(Omega), and the filtered factors of
 // the square-root forward pass (solve_sqrt.hip), from which the predicted ones are re-evaluated (square_root.py:56-57).
 // square_root.forecast returns the full forecast VARIANCE (square_root.py:343-344: var_fore.dot(var_fore.T)), so the value
@@ -11,21 +11,9 @@
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
 #include "sqrt_small.hpp"
+#include "records.hpp"
 
 namespace rk {
-
-template <int P>
-__device__ __forceinline__ void fs_load_state(const SolveArgs& a, int n, int blk, int b, double (&mf)[P], double (&Lf)[P][P]) {
-    const size_t B = (size_t)a.B;
-    const double* mi = a.mean + ((size_t)n * a.D + blk) * P * B + b;
-    const double* vi = a.var + ((size_t)n * a.D + blk) * P * P * B + b;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        mf[i] = mi[(size_t)i * B];
-#pragma unroll
-        for (int j = 0; j < P; ++j) Lf[i][j] = vi[((size_t)i * P + j) * B];
-    }
-}
 
 // forecast + log-density + update with one observation of M components (square_root.py:342-345, utils.py:60-78,
 // square_root.py:88-99 with x_meas = y, mean_meas = 0, wgt_meas = D, var_meas = the factor Vh of Omega)
@@ -93,8 +81,15 @@ __device__ __forceinline__ void fs_observe(const double (&D)[M][P], const double
     add_sqrt<P, P, M>(A1, B1, L);                                       // square_root.py:98-99
 }
 
-// STORE: per (time n, block) an item of 4 P^2 + 2 P doubles [m_pred, L_pred, m_filt, L_filt, A, C^{1/2}], batch-minor
-// (fenrir.py:236-258; the square-root smoother needs the Markov chain's factor too, square_root.py:217-218).
+// STORE: per (time n, block) a batch-minor item [m_pred, L_pred | m_filt, L_filt | A | C^{1/2}] (fenrir.py:236-258; the
+// square-root smoother needs the Markov chain's factor too, square_root.py:217-218); element offsets of its fields and its
+// doubles, n_bstate = p
+struct FenrirSqrtItem {
+    int pred, filt, A, C, width;
+    constexpr explicit FenrirSqrtItem(int p)
+        : pred(0), filt(p + p * p), A(2 * (p + p * p)), C(2 * (p + p * p) + p * p), width(4 * p * p + 2 * p) {}
+};
+
 template <int P, bool STORE, int MO>
 __global__ void __launch_bounds__(64) fenrir_bwd_sqrt_kernel(SolveArgs a, const double* __restrict__ obs,
                                                              const double* __restrict__ obs_w, const double* __restrict__ obs_v,
@@ -107,7 +102,7 @@ __global__ void __launch_bounds__(64) fenrir_bwd_sqrt_kernel(SolveArgs a, const 
     double Q[P][P], LR[P][P];
     load_block_consts<P>(a, blk, b, Q, LR);
     double bm[P], bL[P][P];
-    fs_load_state<P>(a, a.N, blk, b, bm, bL);                               // terminal point (fenrir.py:186-188)
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, a.B, a.D, a.N, blk, b, bm, bL);   // terminal point (fenrir.py:186-188)
     double acc = 0.0;
     int i = n_obs - 1;
     auto observe = [&](double (&m)[P], double (&L)[P][P]) {
@@ -124,9 +119,9 @@ __global__ void __launch_bounds__(64) fenrir_bwd_sqrt_kernel(SolveArgs a, const 
         fs_observe<P, MO>(D, y, Vh, m, L, acc);
         --i;
     };
-    constexpr int ITEM = 4 * P * P + 2 * P;
+    constexpr FenrirSqrtItem IT(P);
     auto keep = [&](int n, int off, const double (&m)[P], const double (&S)[P][P]) {
-        double* o = states + (((size_t)n * a.D + blk) * ITEM + off) * B + b;
+        double* o = states + (((size_t)n * a.D + blk) * IT.width + off) * B + b;
 #pragma unroll
         for (int r = 0; r < P; ++r) {
             o[(size_t)r * B] = m[r];
@@ -134,12 +129,12 @@ __global__ void __launch_bounds__(64) fenrir_bwd_sqrt_kernel(SolveArgs a, const 
             for (int c = 0; c < P; ++c) o[(size_t)(P + r * P + c) * B] = S[r][c];
         }
     };
-    if constexpr (STORE) keep(a.N, 0, bm, bL);
+    if constexpr (STORE) keep(a.N, IT.pred, bm, bL);
     if (i >= 0 && obs_ind[i] >= a.N) observe(bm, bL);                      // fenrir.py:189-209
-    if constexpr (STORE) keep(a.N, P + P * P, bm, bL);
+    if constexpr (STORE) keep(a.N, IT.filt, bm, bL);
     for (int n = a.N - 1; n >= 0; --n) {
         double mf[P], Lf[P][P], mp[P], Lp[P][P], G[P][P], JL[P][P];
-        fs_load_state<P>(a, n, blk, b, mf, Lf);
+        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, a.B, a.D, n, blk, b, mf, Lf);
         sqrt_predict<P>(Q, LR, mf, Lf, mp, Lp);                             // pred[n+1] from filt[n] (square_root.py:56-57)
         sqrt_gain<P>(Q, Lf, Lp, G, JL);                                     // A = G (square_root.py:376-377), J L_f
         double bb[P], GR[P][P], Cc[P][P], AL[P][P], nm[P], nL[P][P];
@@ -156,18 +151,18 @@ __global__ void __launch_bounds__(64) fenrir_bwd_sqrt_kernel(SolveArgs a, const 
             for (int c = 0; c < P; ++c) bL[r][c] = nL[r][c];
         }
         if constexpr (STORE) {
-            keep(n, 0, bm, bL);
-            double* o = states + (((size_t)n * a.D + blk) * ITEM + 2 * (P + P * P)) * B + b;
+            keep(n, IT.pred, bm, bL);
+            double* o = states + (((size_t)n * a.D + blk) * IT.width + IT.A) * B + b;
 #pragma unroll
             for (int r = 0; r < P; ++r)
 #pragma unroll
                 for (int c = 0; c < P; ++c) {
                     o[(size_t)(r * P + c) * B] = G[r][c];
-                    o[(size_t)(P * P + r * P + c) * B] = Cc[r][c];
+                    o[(size_t)(IT.C - IT.A + r * P + c) * B] = Cc[r][c];
                 }
         }
         if (i >= 0 && obs_ind[i] == n) observe(bm, bL);                     // fenrir.py:155-170
-        if constexpr (STORE) keep(n, P + P * P, bm, bL);
+        if constexpr (STORE) keep(n, IT.filt, bm, bL);
     }
     if (logdens) atomicAdd(&logdens[b], acc);
 }
@@ -180,9 +175,9 @@ __global__ void __launch_bounds__(64) fenrir_smooth_sqrt_kernel(SolveArgs a, con
     if (l >= a.B * a.D) return;
     const int blk = l / a.B, b = l - blk * a.B;
     const size_t B = (size_t)a.B;
-    constexpr int ITEM = 4 * P * P + 2 * P;
+    constexpr FenrirSqrtItem IT(P);
     auto item = [&](int n, int off, double (&m)[P], double (&S)[P][P]) {
-        const double* o = states + (((size_t)n * a.D + blk) * ITEM + off) * B + b;
+        const double* o = states + (((size_t)n * a.D + blk) * IT.width + off) * B + b;
 #pragma unroll
         for (int r = 0; r < P; ++r) {
             m[r] = o[(size_t)r * B];
@@ -191,7 +186,7 @@ __global__ void __launch_bounds__(64) fenrir_smooth_sqrt_kernel(SolveArgs a, con
         }
     };
     auto mat = [&](int n, int off, double (&S)[P][P]) {
-        const double* o = states + (((size_t)n * a.D + blk) * ITEM + off) * B + b;
+        const double* o = states + (((size_t)n * a.D + blk) * IT.width + off) * B + b;
 #pragma unroll
         for (int r = 0; r < P; ++r)
 #pragma unroll
@@ -208,17 +203,17 @@ __global__ void __launch_bounds__(64) fenrir_smooth_sqrt_kernel(SolveArgs a, con
         }
     };
     double cm[P], cL[P][P];
-    item(0, P + P * P, cm, cL);
+    item(0, IT.filt, cm, cL);
     put(0, cm, cL);
     if (a.N < 1) return;
-    item(1, P + P * P, cm, cL);
+    item(1, IT.filt, cm, cL);
     put(1, cm, cL);
     for (int k = 0; k + 2 <= a.N; ++k) {
         double fm[P], fL[P][P], pm[P], pL[P][P], A[P][P], Ch[P][P], G[P][P], JL[P][P];
-        item(k + 2, P + P * P, fm, fL);
-        item(k + 1, 0, pm, pL);
-        mat(k + 1, 2 * (P + P * P), A);
-        mat(k + 1, 2 * (P + P * P) + P * P, Ch);
+        item(k + 2, IT.filt, fm, fL);
+        item(k + 1, IT.pred, pm, pL);
+        mat(k + 1, IT.A, A);
+        mat(k + 1, IT.C, Ch);
         sqrt_gain<P>(A, fL, pL, G, JL);                                     // square_root.py:170-175 with wgt_state = A
         double dm[P], gm[P], both[P][2 * P], GA[P][2 * P];
 #pragma unroll
@@ -236,7 +231,7 @@ __global__ void __launch_bounds__(64) fenrir_smooth_sqrt_kernel(SolveArgs a, con
     }
 }
 
-size_t fenrir_sqrt_item_doubles(int p) { return 4 * (size_t)p * p + 2 * (size_t)p; }
+size_t fenrir_sqrt_item_doubles(int p) { return (size_t)FenrirSqrtItem(p).width; }
 
 // states == nullptr: the log-density only (rk_fenrir_backward); else the stored backward filter + the smoothing sweep
 int fenrir_sqrt_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* obs, const double* obs_w,

@@ -18,7 +18,7 @@ struct DaltonObs;
 struct DaltonAt;
 struct FenrirAt;
 
-// ---- lane-per-trajectory solver (solve_small.hip): helpers that DALTON (dalton.hip) shares ------------------------------
+// ---- lane-per-trajectory solver (solve_small.hip): helpers that DALTON (dalton.hip) and Fenrir (fenrir.hip) share ------
 int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in);
 int make_args(const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, SolveArgs& a);
 int begin_solve(rk_handle h);
@@ -78,7 +78,7 @@ int ng_obs_eval(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs&
 bool user_dense_wanted(const rk_solve_cfg* c);
 int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a);
 
-// ---- fused square-root solver (solve_sqrt.hip) and fenrir in the square-root form (fenrir_sqrt.hip) ------------------
+// ---- fused square-root solver (solve_sqrt.hip) and fenrir in the square-root form (fenrir_sqrt.hip, entered from fenrir.hip)
 int sqrt_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, double* ws, size_t ws_bytes);
 size_t sqrt_ws_doubles(const rk_solve_cfg* c, int mode);
 size_t fenrir_sqrt_item_doubles(int p);

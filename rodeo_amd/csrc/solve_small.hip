@@ -1,7 +1,12 @@
-// Small-block solver kernels (n_bmeas = 1, n_bstate <= 6): the fused time loops of
-//   src/rodeo/solve.py:31-122   _solve_filter   -> fwd_kernel
+// The lane-per-trajectory solver in the covariance form and the solver's C entries.  Kernels (n_bmeas = 1; forward n_bstate <= 6,
+// backward <= 9): the fused time loops of
+//   src/rodeo/solve.py:31-122   _solve_filter   -> fwd_kernel      (solve_small_kernels.hpp, also built at run time)
 //   src/rodeo/solve.py:257-301  solve_mv        -> bwd_mv_kernel   (in place over the filtered moments)
 //   src/rodeo/solve.py:162-204  solve_sim       -> bwd_sim_kernel
+// and gauss_logpost_kernel, the Gaussian observation log-posterior of a sampled path.  Host side: the argument block and
+// checks every path shares (make_args, check_cfg, begin_solve), and rk_solve_filter / _mv / _sim, rk_solve_layout / _sizes /
+// _workspace_bytes, rk_solve_sim_logpost, rk_interrogate_batched, rk_gauss_obs_logpost, which route a configuration to its
+// path (solve_paths.hpp).  Fenrir is in fenrir.hip.
 // The whole N-step recursion of a trajectory runs inside ONE kernel launch; the state lives in VGPRs and only the
 // filtered / smoothed moments touch HBM, in the batch-minor layout of include/rodeo_kalman.h (512 B per wave per
 // element row).  Predicted moments are re-evaluated from the filtered ones in the backward pass instead of being
@@ -13,39 +18,11 @@
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
 #include "solve_small_kernels.hpp"
-#include "fenrir_kernels.hpp"
+#include "records.hpp"
 
 namespace rk {
 
 // ---- backward passes: one lane per (block, trajectory) -----------------------------------------------------------
-template <int P>
-__device__ __forceinline__ void load_filt(const SolveArgs& a, int n, int blk, int b, double (&mf)[P],
-                                          double (&Sf)[P][P]) {
-    const size_t B = (size_t)a.B;
-    const double* mi = a.mean + ((size_t)n * a.D + blk) * P * B + b;
-    const double* vi = a.var + ((size_t)n * a.D + blk) * P * P * B + b;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        mf[i] = mi[(size_t)i * B];
-#pragma unroll
-        for (int j = 0; j < P; ++j) Sf[i][j] = vi[((size_t)i * P + j) * B];
-    }
-}
-
-// the same from the blocked tile path's records [Sigma row-major (p^2) | mu (p)] per (time, trajectory, block)
-// (RK_LAYOUT_TILE4 / RK_LAYOUT_TILEP, solve_tilen_kernels.hpp)
-template <int P>
-__device__ __forceinline__ void load_filt_tiles(const SolveArgs& a, const double* tiles, int n, int blk, int b, double (&mf)[P],
-                                                double (&Sf)[P][P]) {
-    const double* rec = tiles + ((size_t)n * a.B * a.D + (size_t)b * a.D + blk) * (P * P + P);
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        mf[i] = rec[P * P + i];
-#pragma unroll
-        for (int j = 0; j < P; ++j) Sf[i][j] = rec[i * P + j];
-    }
-}
-
 template <int P>
 __global__ void __launch_bounds__(64) bwd_mv_kernel(SolveArgs a) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
@@ -56,25 +33,18 @@ __global__ void __launch_bounds__(64) bwd_mv_kernel(SolveArgs a) {
     load_block_consts<P>(a, blk, b, Q, R);
 
     double ms[P], Ss[P][P];                    // carry: smoothed moments at n+1 (solve.py:279-282)
-    load_filt<P>(a, a.N, blk, b, ms, Ss);
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, ms, Ss);
     double mf[P], Sf[P][P];
-    if (a.N >= 2) load_filt<P>(a, a.N - 1, blk, b, mf, Sf);
+    if (a.N >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
     for (int n = a.N - 1; n >= 1; --n) {
         // software prefetch of the next (earlier) filtered state while this step computes
         double mfn[P], Sfn[P][P];
-        if (n >= 2) load_filt<P>(a, n - 1, blk, b, mfn, Sfn);
+        if (n >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
         double mp[P], Sp[P][P], T[P][P], G[P][P];
         predict_block<P>(Q, R, mf, Sf, mp, Sp);          // pred[n+1] re-evaluated from filt[n]
         smooth_gain<P>(Q, Sf, Sp, T, G);
         smooth_mv_block<P>(G, mf, Sf, mp, Sp, ms, Ss);
-        double* mo = a.mean + ((size_t)n * a.D + blk) * P * B + b;
-        double* vo = a.var + ((size_t)n * a.D + blk) * P * P * B + b;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            mo[(size_t)i * B] = ms[i];
-#pragma unroll
-            for (int j = 0; j < P; ++j) vo[((size_t)i * P + j) * B] = Ss[i][j];
-        }
+        store_moments<P>(a.mean, a.var, B, a.D, n, blk, b, ms, Ss);
         if (n >= 2) {
 #pragma unroll
             for (int i = 0; i < P; ++i) {
@@ -105,14 +75,14 @@ __global__ void __launch_bounds__(64) bwd_sim_kernel(SolveArgs a) {
 
     double mf[P], Sf[P][P], xn[P], z[P];
     // terminal draw x_N ~ N(filt[N]) (solve.py:182-186)
-    load_filt<P>(a, a.N, blk, b, mf, Sf);
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, mf, Sf);
     normals<P>(a.seed, traj, (uint32_t)a.N, (uint32_t)blk, PURPOSE_SMOOTH, z);
     mvn_draw<P>(mf, Sf, z, xn);
     store_x(a.N, xn);
-    if (a.N >= 2) load_filt<P>(a, a.N - 1, blk, b, mf, Sf);
+    if (a.N >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
     for (int n = a.N - 1; n >= 1; --n) {
         double mfn[P], Sfn[P][P];
-        if (n >= 2) load_filt<P>(a, n - 1, blk, b, mfn, Sfn);
+        if (n >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
         double mp[P], Sp[P][P], T[P][P], G[P][P], msim[P], Ssim[P][P];
         predict_block<P>(Q, R, mf, Sf, mp, Sp);
         smooth_gain<P>(Q, Sf, Sp, T, G);
@@ -167,154 +137,6 @@ __global__ void __launch_bounds__(64) gauss_logpost_kernel(int B, int n_steps, i
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
     if (lane == 0) out[b] = acc;
-}
-
-// ---- Fenrir backward pass (src/rodeo/inference/fenrir.py:86-259), scalar observations per block --------------------
-// One lane per (block, trajectory): the backward Markov chain X_n = A_n X_{n+1} + b_n + C_n^{1/2} eps
-// (smooth_cond, standard.py:366-370) is run as a Kalman filter backwards in time over the stored forward moments
-// (batch-minor filt and pred), conditioning on the observations y_i = D_i X_{n(i)} + N(0, Omega_i) at their grid
-// indices; every observation contributes log N(y_i; D m, D S D^T + Omega) with utils.py:60-78's rule that a variance
-// with |w| <= 1e-8 contributes nothing (jnp.isclose(w, 0, rtol=1e-300)).  Block values are summed per trajectory.
-// With STORE (fenrir.py:236-258, for fenrir's solve_mv) the backward filter's predicted and updated moments of every
-// time and the Markov weights A_n are kept in `states`: per (time n, block) an item of 3 P^2 + 2 P doubles
-// [m_pred (P), S_pred (P^2), m_filt (P), S_filt (P^2), A (P^2)], batch-minor.
-// MO = n_bobs (observations per block, fenrir.py:106-122): obs (n_obs, d, MO), obs_w (n_obs, d, MO, P), obs_v (n_obs, d, MO, MO)
-// TILES: the forward pass ran on the blocked MFMA tiles (n_bstate 4 .. 8): `tiles` holds its records and the predicted
-// moments are re-evaluated from the filtered ones (standard.py:57-59, what the forward pass computed) instead of read.
-template <int P, bool STORE, int MO, bool TILES = false>
-__global__ void __launch_bounds__(64) fenrir_bwd_kernel(SolveArgs a, const double* __restrict__ obs,
-                                                        const double* __restrict__ obs_w, const double* __restrict__ obs_v,
-                                                        const int32_t* __restrict__ obs_ind, int n_obs,
-                                                        double* __restrict__ logdens, double* __restrict__ states,
-                                                        const double* __restrict__ tiles = nullptr) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= a.B * a.D) return;
-    const int blk = l / a.B, b = l - blk * a.B;
-    const size_t B = (size_t)a.B;
-    double Q[P][P], R[P][P];
-    load_block_consts<P>(a, blk, b, Q, R);
-    double bm[P], bS[P][P];
-    if constexpr (TILES) load_filt_tiles<P>(a, tiles, a.N, blk, b, bm, bS);
-    else load_filt<P>(a, a.N, blk, b, bm, bS);                               // terminal point (fenrir.py:186-188)
-    double acc = 0.0;
-    int i = n_obs - 1;
-    // conditioning on observation i: forecast (standard.py:333-335) + log-density + update (standard.py:93-102)
-    const DaltonObs o{obs, obs_w, obs_v, obs_ind, n_obs};
-    auto observe = [&](double (&m)[P], double (&S)[P][P]) {
-        if constexpr (MO == 1) fenrir_observe_scalar<P>(o, (size_t)i * a.D + blk, m, S, acc);
-        else dalton_observe<P, MO>(o, (size_t)i * a.D + blk, m, S, acc);
-        --i;
-    };
-    constexpr int ITEM = 3 * P * P + 2 * P;
-    auto keep = [&](int n, int off, const double (&m)[P], const double (&S)[P][P]) {
-        double* o = states + (((size_t)n * a.D + blk) * ITEM + off) * B + b;
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            o[(size_t)r * B] = m[r];
-#pragma unroll
-            for (int c = 0; c < P; ++c) o[(size_t)(P + r * P + c) * B] = S[r][c];
-        }
-    };
-    if constexpr (STORE) keep(a.N, 0, bm, bS);                              // "prediction" at N = the terminal point
-    if (i >= 0 && obs_ind[i] >= a.N) observe(bm, bS);                      // fenrir.py:189-209
-    if constexpr (STORE) keep(a.N, P + P * P, bm, bS);
-    for (int n = a.N - 1; n >= 0; --n) {
-        double mf[P], Sf[P][P], mp[P], Sp[P][P], G[P][P];
-        if constexpr (TILES) {
-            load_filt_tiles<P>(a, tiles, n, blk, b, mf, Sf);
-            predict_block<P>(Q, R, mf, Sf, mp, Sp);                         // pred[n + 1] from filt[n]
-        } else {
-            load_filt<P>(a, n, blk, b, mf, Sf);
-            // stored predicted moments of time n + 1 (solve.py:93-96)
-            const double* mi = a.mean_pred + ((size_t)(n + 1) * a.D + blk) * P * B + b;
-            const double* vi = a.var_pred + ((size_t)(n + 1) * a.D + blk) * P * P * B + b;
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                mp[r] = mi[(size_t)r * B];
-#pragma unroll
-                for (int c = 0; c < P; ++c) Sp[r][c] = vi[((size_t)r * P + c) * B];
-            }
-        }
-        fenrir_markov_step<P>(Q, mf, Sf, mp, Sp, bm, bS, G);
-        if constexpr (STORE) {
-            keep(n, 0, bm, bS);
-            double* o = states + (((size_t)n * a.D + blk) * ITEM + 2 * (P + P * P)) * B + b;
-#pragma unroll
-            for (int r = 0; r < P; ++r)
-#pragma unroll
-                for (int c = 0; c < P; ++c) o[(size_t)(r * P + c) * B] = G[r][c];
-        }
-        if (i >= 0 && obs_ind[i] == n) observe(bm, bS);                     // fenrir.py:155-170
-        if constexpr (STORE) keep(n, P + P * P, bm, bS);
-    }
-    if (logdens) atomicAdd(&logdens[b], acc);
-}
-
-// fenrir.py:333-402: the smoothing pass over the backward filter's stored moments, a forward sweep in time -- times 0 and
-// 1 keep the backward filter's own estimates; for k = 0 .. N-2
-//     (m, S)_{k+2} = smooth_mv(next = (m, S)_{k+1}, wgt_state = A_{k+1}, filt = bfilt_{k+2}, pred = bpred_{k+1}).
-// Results go to a.mean / a.var (batch-minor), which the backward filter no longer needs.
-template <int P>
-__global__ void __launch_bounds__(64) fenrir_smooth_kernel(SolveArgs a, const double* __restrict__ states) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= a.B * a.D) return;
-    const int blk = l / a.B, b = l - blk * a.B;
-    const size_t B = (size_t)a.B;
-    constexpr int ITEM = 3 * P * P + 2 * P;
-    auto item = [&](int n, int off, double (&m)[P], double (&S)[P][P]) {
-        const double* o = states + (((size_t)n * a.D + blk) * ITEM + off) * B + b;
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            m[r] = o[(size_t)r * B];
-#pragma unroll
-            for (int c = 0; c < P; ++c) S[r][c] = o[(size_t)(P + r * P + c) * B];
-        }
-    };
-    auto put = [&](int n, const double (&m)[P], const double (&S)[P][P]) {
-        double* mo = a.mean + ((size_t)n * a.D + blk) * P * B + b;
-        double* vo = a.var + ((size_t)n * a.D + blk) * P * P * B + b;
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            mo[(size_t)r * B] = m[r];
-#pragma unroll
-            for (int c = 0; c < P; ++c) vo[((size_t)r * P + c) * B] = S[r][c];
-        }
-    };
-    double cm[P], cS[P][P];
-    item(0, P + P * P, cm, cS);
-    put(0, cm, cS);
-    if (a.N < 1) return;
-    item(1, P + P * P, cm, cS);
-    put(1, cm, cS);
-    for (int k = 0; k + 2 <= a.N; ++k) {
-        double fm[P], fS[P][P], pm[P], pS[P][P], A[P][P], T[P][P], G[P][P];
-        item(k + 2, P + P * P, fm, fS);
-        item(k + 1, 0, pm, pS);
-        {
-            const double* o = states + (((size_t)(k + 1) * a.D + blk) * ITEM + 2 * (P + P * P)) * B + b;
-#pragma unroll
-            for (int r = 0; r < P; ++r)
-#pragma unroll
-                for (int c = 0; c < P; ++c) A[r][c] = o[(size_t)(r * P + c) * B];
-        }
-        smooth_gain<P>(A, fS, pS, T, G);                                    // standard.py:175-176 with wgt_state = A
-        double dm[P], dS[P][P], GD[P][P], nS[P][P];
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            dm[r] = cm[r] - pm[r];
-#pragma unroll
-            for (int c = 0; c < P; ++c) dS[r][c] = cS[r][c] - pS[r][c];
-        }
-        mm<P, P, P>(G, dS, GD);
-        mm_nt<P, P, P>(GD, G, nS);
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            cm[r] = fm[r] + dot<P>(G[r], dm);                               // standard.py:213-214
-#pragma unroll
-            for (int c = 0; c < P; ++c) cS[r][c] = fS[r][c] + nS[r][c];     // standard.py:215-216
-        }
-        put(k + 2, cm, cS);
-    }
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------
@@ -412,30 +234,6 @@ static int launch_itg_rhs(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a
     RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "rk_interrogate_batched supports n_bstate in [2, 6], got %d", c->n_bstate);
     RK_HIP(hipGetLastError());
     return RK_OK;
-}
-
-// fenrir's backward filter, one lane per (block, trajectory): fenrir_bwd_kernel<P, STORE, n_bobs, TILES> for P in [PLO, PHI]
-// (tiles: the records of the blocked-tile forward pass, TILES only)
-template <int PLO, int PHI, bool STORE, bool TILES>
-static void launch_fenrir_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int n_bobs, const double* obs,
-                              const double* obs_w, const double* obs_v, const int32_t* obs_ind, int n_obs, double* logdens,
-                              double* states, const double* tiles) {
-    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
-    dispatch_int<PLO, PHI>(c->n_bstate, [&](auto P) {
-        dispatch_int<1, 3>(n_bobs, [&](auto M) {
-            hipLaunchKernelGGL((fenrir_bwd_kernel<P, STORE, M, TILES>), grid, block, 0, h->stream, a, obs, obs_w, obs_v, obs_ind, n_obs,
-                               logdens, states, tiles);
-        });
-    });
-}
-
-// fenrir's smoothing sweep over the stored backward filter (fenrir_smooth_kernel<P>), P in [PLO, PHI]
-template <int PLO, int PHI>
-static void launch_fenrir_smooth(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* states) {
-    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
-    dispatch_int<PLO, PHI>(c->n_bstate, [&](auto P) {
-        hipLaunchKernelGGL(fenrir_smooth_kernel<P>, grid, block, 0, h->stream, a, states);
-    });
 }
 
 int begin_solve(rk_handle h) {
@@ -617,151 +415,6 @@ int rk_gauss_obs_logpost(rk_handle h, int32_t n_traj, int32_t n_steps, int32_t n
     hipLaunchKernelGGL(gauss_logpost_kernel, dim3(n_traj), dim3(64), 0, h->stream, n_traj, n_steps, n_block,
                        n_bstate, layout == RK_LAYOUT_TILE3 ? 12 : (layout == RK_LAYOUT_BATCH_MINOR ? 0 : n_bstate * (n_bstate + 1)),
                        layout == RK_LAYOUT_TILE3 ? 3 : n_bstate * n_bstate, x_state, obs, obs_ind, n_obs, noise_sd, upars, n_prior, prior_sd, logpost);
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
-int rk_fenrir_backward(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out,
-                       const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
-                       int32_t n_obs, int32_t n_bobs, double* logdens) {
-    RK_REQUIRE(h && c && in && out && obs && obs_weight && obs_var && obs_ind && logdens, RK_ERR_INVALID,
-               "rk_fenrir_backward: null argument");
-    RK_REQUIRE(n_bobs >= 1 && n_bobs <= 3, RK_ERR_UNSUPPORTED, "rk_fenrir_backward: n_bobs in 1..3, got %d", n_bobs);
-    if (c->kalman_type == RK_KALMAN_SQRT) {
-        // fenrir.py:292-296: every step map from square_root.py; the filtered FACTORS of the square-root forward pass
-        // (batch-minor, solve_sqrt.hip) are all it needs -- the predicted ones are re-evaluated (fenrir_sqrt.hip)
-        RK_REQUIRE(out->mean_state && out->var_state && n_obs >= 0, RK_ERR_INVALID,
-                   "rk_fenrir_backward (square-root): out->mean_state / var_state of rk_solve_filter are null");
-        SolveArgs as;
-        int rcs = make_args(c, in, out, as);
-        if (rcs) return rcs;
-        RK_HIP(hipSetDevice(h->device));
-        RK_HIP(hipMemsetAsync(logdens, 0, sizeof(double) * (size_t)c->n_traj, h->stream));
-        return fenrir_sqrt_launch(h, c, as, obs, obs_weight, obs_var, obs_ind, n_obs, n_bobs, logdens, nullptr);
-    }
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "rk_fenrir_backward: unknown kalman_type %d", c->kalman_type);
-    const bool own_layout = !(c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR));
-    const SolvePath fpath = own_layout ? solve_path(c, RK_MODE_FILTER) : SolvePath::Small;      // the route rk_solve_filter took
-    if (n_bobs == 1 && fpath == SolvePath::Tile3) {
-        // the filter ran on the MFMA-tile path: out->var_state holds the RK_LAYOUT_TILE3 tiles, predicted moments are
-        // re-evaluated from the filtered ones (solve_tile3.hip, fenrir_bwd_tile3_kernel)
-        RK_REQUIRE(out->var_state && n_obs >= 0, RK_ERR_INVALID, "rk_fenrir_backward: out->var_state (tiles) is null");
-        SolveArgs at;
-        int rct = make_args(c, in, out, at);
-        if (rct) return rct;
-        RK_HIP(hipSetDevice(h->device));
-        RK_HIP(hipMemsetAsync(logdens, 0, sizeof(double) * (size_t)c->n_traj, h->stream));
-        return tile3_fenrir_backward(h, at, out->var_state, obs, obs_weight, obs_var, obs_ind, n_obs, logdens);
-    }
-    if (fpath == SolvePath::Tile4 || fpath == SolvePath::TileN) {
-        // the filter ran on the blocked MFMA tiles (n_bstate 4 .. 8): out->var_state holds its records [Sigma | mu]; the
-        // backward filter runs one lane per (block, trajectory) on them and re-evaluates the predicted moments
-        RK_REQUIRE(out->var_state && n_obs >= 0, RK_ERR_INVALID, "rk_fenrir_backward: out->var_state (tiles) is null");
-        SolveArgs at;
-        int rct = make_args(c, in, out, at);
-        if (rct) return rct;
-        RK_HIP(hipSetDevice(h->device));
-        RK_HIP(hipMemsetAsync(logdens, 0, sizeof(double) * (size_t)c->n_traj, h->stream));
-        LaunchTimer t(h, "fenrir_bwd_kernel<tiles>");
-        launch_fenrir_bwd<4, 8, false, true>(h, c, at, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, nullptr, out->var_state);
-        t.stop();
-        RK_HIP(hipGetLastError());
-        return RK_OK;
-    }
-    RK_REQUIRE(out->mean_state && out->var_state && out->mean_pred && out->var_pred, RK_ERR_INVALID,
-               "rk_fenrir_backward needs the batch-minor filtered AND predicted moments of rk_solve_filter "
-               "(RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR), or a configuration of the tile paths (n_bstate = 3 .. 8) without them");
-    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 6 && n_obs >= 0, RK_ERR_UNSUPPORTED,
-               "rk_fenrir_backward: n_bstate in 2..6");
-    SolveArgs a;
-    int rc = make_args(c, in, out, a);
-    if (rc) return rc;
-    RK_HIP(hipSetDevice(h->device));
-    RK_HIP(hipMemsetAsync(logdens, 0, sizeof(double) * (size_t)c->n_traj, h->stream));
-    LaunchTimer t(h, "fenrir_bwd_kernel");
-    launch_fenrir_bwd<2, 6, false, false>(h, c, a, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, logdens, nullptr, nullptr);
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
-int rk_fenrir_workspace_bytes(const rk_solve_cfg* c, size_t* bytes) {
-    RK_REQUIRE(c && bytes, RK_ERR_INVALID, "rk_fenrir_workspace_bytes: null argument");
-    const size_t p = (size_t)c->n_bstate;
-    const size_t item = c->kalman_type == RK_KALMAN_SQRT ? fenrir_sqrt_item_doubles(c->n_bstate) : 3 * p * p + 2 * p;
-    *bytes = sizeof(double) * (size_t)(c->n_steps + 1) * c->n_block * item * c->n_traj;
-    return RK_OK;
-}
-
-// fenrir's solve_mv on the records of the blocked-tile forward pass (n_bstate 4 .. 8, rk_solve_filter without RK_FLAG_STORE_PRED |
-// RK_FLAG_BATCH_MINOR): out->var_state holds the records [Sigma | mu] per (time, trajectory, block); the backward filter re-evaluates
-// the predicted moments from them (fenrir_bwd_kernel<.., STORE, .., TILES>), the smoothing pass writes mean_out (N+1, d, p, B) and
-// var_out (N+1, d, p, p, B), batch-minor.
-int rk_fenrir_solve_mv_tiles(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out,
-                             const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
-                             int32_t n_obs, int32_t n_bobs, void* workspace, double* mean_out, double* var_out) {
-    RK_REQUIRE(h && c && in && out && obs && obs_weight && obs_var && obs_ind && workspace && mean_out && var_out, RK_ERR_INVALID,
-               "rk_fenrir_solve_mv_tiles: null argument");
-    const SolvePath fpath = !(c->flags & (RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)) ? solve_path(c, RK_MODE_FILTER) : SolvePath::Small;
-    RK_REQUIRE(fpath == SolvePath::Tile4 || fpath == SolvePath::TileN, RK_ERR_UNSUPPORTED,
-               "rk_fenrir_solve_mv_tiles: a configuration of the blocked-tile forward pass (kalman_type standard, n_bstate 4..8, no "
-               "RK_FLAG_STORE_PRED / RK_FLAG_BATCH_MINOR)");
-    RK_REQUIRE(out->var_state && n_obs >= 0 && n_bobs >= 1 && n_bobs <= 3, RK_ERR_INVALID,
-               "rk_fenrir_solve_mv_tiles: out->var_state (tile records) is null, or n_bobs outside 1..3");
-    SolveArgs a;
-    int rc = make_args(c, in, out, a);
-    if (rc) return rc;
-    a.mean = mean_out; a.var = var_out;                             // (the smoothing pass's output; the backward filter reads the records)
-    RK_HIP(hipSetDevice(h->device));
-    double* st = (double*)workspace;
-    {
-        LaunchTimer t(h, "fenrir_bwd_kernel<tiles>");
-        launch_fenrir_bwd<4, 8, true, true>(h, c, a, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, nullptr, st, out->var_state);
-        t.stop();
-    }
-    RK_HIP(hipGetLastError());
-    LaunchTimer t(h, "fenrir_smooth_kernel");
-    launch_fenrir_smooth<4, 8>(h, c, a, st);
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
-int rk_fenrir_solve_mv(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out,
-                       const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
-                       int32_t n_obs, int32_t n_bobs, void* workspace) {
-    RK_REQUIRE(h && c && in && out && obs && obs_weight && obs_var && obs_ind && workspace, RK_ERR_INVALID,
-               "rk_fenrir_solve_mv: null argument");
-    if (c->kalman_type == RK_KALMAN_SQRT) {                          // fenrir.py:421-426 (fenrir_sqrt.hip)
-        RK_REQUIRE(out->mean_state && out->var_state && n_obs >= 0, RK_ERR_INVALID,
-                   "rk_fenrir_solve_mv (square-root): out->mean_state / var_state of rk_solve_filter are null");
-        SolveArgs as;
-        int rcs = make_args(c, in, out, as);
-        if (rcs) return rcs;
-        RK_HIP(hipSetDevice(h->device));
-        return fenrir_sqrt_launch(h, c, as, obs, obs_weight, obs_var, obs_ind, n_obs, n_bobs, nullptr, (double*)workspace);
-    }
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "rk_fenrir_solve_mv: unknown kalman_type %d", c->kalman_type);
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) && (c->flags & RK_FLAG_BATCH_MINOR) && out->mean_state && out->var_state &&
-               out->mean_pred && out->var_pred, RK_ERR_INVALID,
-               "rk_fenrir_solve_mv needs the batch-minor filtered AND predicted moments of rk_solve_filter "
-               "(RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR)");
-    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 6 && n_obs >= 0 && n_bobs >= 1 && n_bobs <= 3, RK_ERR_UNSUPPORTED,
-               "rk_fenrir_solve_mv: n_bstate in 2..6, n_bobs in 1..3");
-    SolveArgs a;
-    int rc = make_args(c, in, out, a);
-    if (rc) return rc;
-    RK_HIP(hipSetDevice(h->device));
-    double* st = (double*)workspace;
-    {
-        LaunchTimer t(h, "fenrir_bwd_kernel");
-        launch_fenrir_bwd<2, 6, true, false>(h, c, a, n_bobs, obs, obs_weight, obs_var, obs_ind, n_obs, nullptr, st, nullptr);
-        t.stop();
-    }
-    RK_HIP(hipGetLastError());
-    LaunchTimer t(h, "fenrir_smooth_kernel");
-    launch_fenrir_smooth<2, 6>(h, c, a, st);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;

@@ -22,24 +22,13 @@
 #include "solve_paths.hpp"
 #include "sqrt_small.hpp"
 #include "solve_sqrt_kernels.hpp"
+#include "records.hpp"
 
 namespace rk {
 
-template <int P>
-__device__ __forceinline__ void load_state(const SolveArgs& a, int n, int blk, int b, double (&mf)[P],
-                                           double (&Lf)[P][P]) {
-    const size_t B = (size_t)a.B;
-    const double* mi = a.mean + ((size_t)n * a.D + blk) * P * B + b;
-    const double* vi = a.var + ((size_t)n * a.D + blk) * P * P * B + b;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        mf[i] = mi[(size_t)i * B];
-#pragma unroll
-        for (int j = 0; j < P; ++j) Lf[i][j] = vi[((size_t)i * P + j) * B];
-    }
-}
-
 // backward: SIM = false -> smooth_mv (square_root.py:209-219), SIM = true -> smooth_sim + draw (square_root.py:252-261)
+// (the stores of this file's kernels stay written out: through accessor functions the instances at the register limit
+// spilled more, bwd_sqrt_kernel up to 500 B at n_bstate 5 .. 7; DESIGN.md, "Batch-minor records")
 template <int P, bool SIM>
 __global__ void __launch_bounds__(64) bwd_sqrt_kernel(SolveArgs a) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
@@ -50,7 +39,7 @@ __global__ void __launch_bounds__(64) bwd_sqrt_kernel(SolveArgs a) {
     double Q[P][P], LR[P][P];
     load_block_consts<P>(a, blk, b, Q, LR);
     double ms[P], Ls[P][P], xn[P];
-    load_state<P>(a, a.N, blk, b, ms, Ls);                       // carry = filt[N]
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, ms, Ls);   // carry = filt[N]
     if (SIM) {
         double z[P];
         normals<P>(a.seed, traj, (uint32_t)a.N, (uint32_t)blk, PURPOSE_SMOOTH, z);
@@ -67,7 +56,7 @@ __global__ void __launch_bounds__(64) bwd_sqrt_kernel(SolveArgs a) {
     }
     for (int n = a.N - 1; n >= 1; --n) {
         double mf[P], Lf[P][P], mp[P], Lp[P][P], G[P][P], JL[P][P];
-        load_state<P>(a, n, blk, b, mf, Lf);
+        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n, blk, b, mf, Lf);
         sqrt_predict<P>(Q, LR, mf, Lf, mp, Lp);                  // pred[n+1] re-evaluated from filt[n]
         sqrt_gain<P>(Q, Lf, Lp, G, JL);
         double dm[P], gm[P];
@@ -124,7 +113,10 @@ __global__ void __launch_bounds__(64) bwd_sqrt_kernel(SolveArgs a) {
 // mean: ~250 instead of ~850 instructions on the one-lane-per-block chain whose length is the run time at small batches
 // (7.3 -> 2.x ms at n_deriv = 3 on the headline shape).  Same arithmetic in the same order as bwd_sqrt_kernel<P, false>, which
 // stays as the path without a workspace.
-__host__ __device__ inline size_t sqrt_rec_doubles(int p) { return 3 * (size_t)p * p + p; }
+struct SqrtGainRec {       // element offsets of the record's fields and its doubles, n_bstate = p
+    int G, JL, GR, mp, width;
+    constexpr explicit SqrtGainRec(int p) : G(0), JL(p * p), GR(2 * p * p), mp(3 * p * p), width(3 * p * p + p) {}
+};
 
 template <int P>
 __global__ void __launch_bounds__(64) sqrt_gain_kernel(SolveArgs a, double* __restrict__ ws) {
@@ -134,19 +126,20 @@ __global__ void __launch_bounds__(64) sqrt_gain_kernel(SolveArgs a, double* __re
     const int n = 1 + (int)(l / per_step), blk = (int)((l % per_step) / B), b = (int)(l % B);
     double Q[P][P], LR[P][P], mf[P], Lf[P][P], mp[P], Lp[P][P], G[P][P], JL[P][P], GR[P][P];
     load_block_consts<P>(a, blk, b, Q, LR);
-    load_state<P>(a, n, blk, b, mf, Lf);
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n, blk, b, mf, Lf);
     sqrt_predict<P>(Q, LR, mf, Lf, mp, Lp);                      // pred[n+1] re-evaluated from filt[n]
     sqrt_gain<P>(Q, Lf, Lp, G, JL);
     mm<P, P, P>(G, LR, GR);
-    double* rec = ws + ((size_t)n * a.D + blk) * sqrt_rec_doubles(P) * B + b;
+    constexpr SqrtGainRec REC(P);
+    double* rec = ws + ((size_t)n * a.D + blk) * REC.width * B + b;
 #pragma unroll
     for (int i = 0; i < P; ++i) {
-        rec[(size_t)(3 * P * P + i) * B] = mp[i];
+        rec[(size_t)(REC.mp + i) * B] = mp[i];
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-            rec[(size_t)(i * P + j) * B] = G[i][j];
-            rec[(size_t)(P * P + i * P + j) * B] = JL[i][j];
-            rec[(size_t)(2 * P * P + i * P + j) * B] = GR[i][j];
+            rec[(size_t)(REC.G + i * P + j) * B] = G[i][j];
+            rec[(size_t)(REC.JL + i * P + j) * B] = JL[i][j];
+            rec[(size_t)(REC.GR + i * P + j) * B] = GR[i][j];
         }
     }
 }
@@ -158,20 +151,21 @@ __global__ void __launch_bounds__(64) bwd_sqrt_chain_kernel(SolveArgs a, const d
     const int blk = l / a.B, b = l - blk * a.B;
     const size_t B = (size_t)a.B;
     double ms[P], Ls[P][P];
-    load_state<P>(a, a.N, blk, b, ms, Ls);                       // carry = filt[N]
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, ms, Ls);   // carry = filt[N]
     struct Rec { double G[P][P], JL[P][P], GR[P][P], mp[P], mf[P]; };
+    constexpr SqrtGainRec REC(P);
     auto load = [&](int n, Rec& q) {
-        const double* rec = ws + ((size_t)n * a.D + blk) * sqrt_rec_doubles(P) * B + b;
+        const double* rec = ws + ((size_t)n * a.D + blk) * REC.width * B + b;
         const double* mi = a.mean + ((size_t)n * a.D + blk) * P * B + b;
 #pragma unroll
         for (int i = 0; i < P; ++i) {
-            q.mp[i] = rec[(size_t)(3 * P * P + i) * B];
+            q.mp[i] = rec[(size_t)(REC.mp + i) * B];
             q.mf[i] = mi[(size_t)i * B];
 #pragma unroll
             for (int j = 0; j < P; ++j) {
-                q.G[i][j] = rec[(size_t)(i * P + j) * B];
-                q.JL[i][j] = rec[(size_t)(P * P + i * P + j) * B];
-                q.GR[i][j] = rec[(size_t)(2 * P * P + i * P + j) * B];
+                q.G[i][j] = rec[(size_t)(REC.G + i * P + j) * B];
+                q.JL[i][j] = rec[(size_t)(REC.JL + i * P + j) * B];
+                q.GR[i][j] = rec[(size_t)(REC.GR + i * P + j) * B];
             }
         }
     };
@@ -225,7 +219,10 @@ __global__ void __launch_bounds__(64) bwd_sqrt_chain_kernel(SolveArgs a, const d
 // carry; the gain, the conditional factor L_sim = add_sqrt(G R^{1/2}, J L_f) and the draw's own part mu_f + L_sim z are
 // evaluated for all steps at once into a record [G | mu- | mu_f + L_sim z] of p^2 + 2 p doubles, and the chain is one
 // matrix-vector product per step.  Same arithmetic and the same normals as bwd_sqrt_kernel<P, true>.
-__host__ __device__ inline size_t sqrt_sim_rec_doubles(int p) { return (size_t)p * p + 2 * p; }
+struct SqrtSimRec {        // element offsets of the record's fields and its doubles, n_bstate = p
+    int G, mp, w, width;
+    constexpr explicit SqrtSimRec(int p) : G(0), mp(p * p), w(p * p + p), width(p * p + 2 * p) {}
+};
 
 template <int P>
 __global__ void __launch_bounds__(64) sqrt_sim_gain_kernel(SolveArgs a, double* __restrict__ ws) {
@@ -236,7 +233,7 @@ __global__ void __launch_bounds__(64) sqrt_sim_gain_kernel(SolveArgs a, double* 
     const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
     double Q[P][P], LR[P][P], mf[P], Lf[P][P], mp[P], Lp[P][P], G[P][P], JL[P][P], GR[P][P], Lsim[P][P], z[P];
     load_block_consts<P>(a, blk, b, Q, LR);
-    load_state<P>(a, n, blk, b, mf, Lf);
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n, blk, b, mf, Lf);
     sqrt_predict<P>(Q, LR, mf, Lf, mp, Lp);
     sqrt_gain<P>(Q, Lf, Lp, G, JL);
     mm<P, P, P>(G, LR, GR);
@@ -244,16 +241,17 @@ __global__ void __launch_bounds__(64) sqrt_sim_gain_kernel(SolveArgs a, double* 
     normals<P>(a.seed, traj, (uint32_t)n, (uint32_t)blk, PURPOSE_SMOOTH, z);
 #pragma unroll
     for (int j = 0; j < P; ++j) z[j] = Lsim[j][j] < 0.0 ? -z[j] : z[j];
-    double* rec = ws + ((size_t)n * a.D + blk) * sqrt_sim_rec_doubles(P) * B + b;
+    constexpr SqrtSimRec REC(P);
+    double* rec = ws + ((size_t)n * a.D + blk) * REC.width * B + b;
 #pragma unroll
     for (int i = 0; i < P; ++i) {
         double w = 0.0;                                          // (the order of bwd_sqrt_kernel: (mu_f + G dx) + L z, L z summed first)
 #pragma unroll
         for (int k = 0; k < P; ++k) w = fma(Lsim[i][k], z[k], w);
-        rec[(size_t)(P * P + i) * B] = mp[i];
-        rec[(size_t)(P * P + P + i) * B] = w;
+        rec[(size_t)(REC.mp + i) * B] = mp[i];
+        rec[(size_t)(REC.w + i) * B] = w;
 #pragma unroll
-        for (int j = 0; j < P; ++j) rec[(size_t)(i * P + j) * B] = G[i][j];
+        for (int j = 0; j < P; ++j) rec[(size_t)(REC.G + i * P + j) * B] = G[i][j];
     }
 }
 
@@ -267,7 +265,7 @@ __global__ void __launch_bounds__(64) bwd_sqrt_sim_chain_kernel(SolveArgs a, con
     double xn[P];
     {
         double ms[P], Ls[P][P], z[P];
-        load_state<P>(a, a.N, blk, b, ms, Ls);                   // x_N ~ N(filt[N])
+        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, ms, Ls);   // x_N ~ N(filt[N])
         normals<P>(a.seed, traj, (uint32_t)a.N, (uint32_t)blk, PURPOSE_SMOOTH, z);
 #pragma unroll
         for (int j = 0; j < P; ++j) z[j] = Ls[j][j] < 0.0 ? -z[j] : z[j];
@@ -281,16 +279,17 @@ __global__ void __launch_bounds__(64) bwd_sqrt_sim_chain_kernel(SolveArgs a, con
         }
     }
     struct Rec { double G[P][P], mp[P], w[P], mf[P]; };
+    constexpr SqrtSimRec REC(P);
     auto load = [&](int n, Rec& q) {
-        const double* rec = ws + ((size_t)n * a.D + blk) * sqrt_sim_rec_doubles(P) * B + b;
+        const double* rec = ws + ((size_t)n * a.D + blk) * REC.width * B + b;
         const double* mi = a.mean + ((size_t)n * a.D + blk) * P * B + b;
 #pragma unroll
         for (int i = 0; i < P; ++i) {
-            q.mp[i] = rec[(size_t)(P * P + i) * B];
-            q.w[i] = rec[(size_t)(P * P + P + i) * B];
+            q.mp[i] = rec[(size_t)(REC.mp + i) * B];
+            q.w[i] = rec[(size_t)(REC.w + i) * B];
             q.mf[i] = mi[(size_t)i * B];
 #pragma unroll
-            for (int j = 0; j < P; ++j) q.G[i][j] = rec[(size_t)(i * P + j) * B];
+            for (int j = 0; j < P; ++j) q.G[i][j] = rec[(size_t)(REC.G + i * P + j) * B];
         }
     };
     constexpr int RD = P <= 4 ? 4 : 2;
@@ -327,7 +326,7 @@ __global__ void __launch_bounds__(64) bwd_sqrt_sim_chain_kernel(SolveArgs a, con
 
 size_t sqrt_ws_doubles(const rk_solve_cfg* c, int mode) {
     if (mode == RK_MODE_FILTER || c->n_steps < 2) return 0;
-    const size_t rec = mode == RK_MODE_MV ? sqrt_rec_doubles(c->n_bstate) : sqrt_sim_rec_doubles(c->n_bstate);
+    const size_t rec = mode == RK_MODE_MV ? SqrtGainRec(c->n_bstate).width : SqrtSimRec(c->n_bstate).width;
     return (size_t)c->n_steps * c->n_block * rec * (size_t)c->n_traj;
 }
 
@@ -352,7 +351,7 @@ __global__ void __launch_bounds__(64) sqrt_pred_kernel(SolveArgs a) {
     } else {
         double Q[P][P], LR[P][P], mf[P], Lf[P][P];
         load_block_consts<P>(a, blk, b, Q, LR);
-        load_state<P>(a, n - 1, blk, b, mf, Lf);
+        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mf, Lf);
         sqrt_predict<P>(Q, LR, mf, Lf, mup, Lp);
     }
     double* mpo = a.mean_pred + ((size_t)n * a.D + blk) * P * B + b;

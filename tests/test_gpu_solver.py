@@ -754,3 +754,48 @@ def test_square_root_sim_law_is_L_Lt(ra):
             # ... and the factor itself in the covariance slot is NOT what is sampled
             assert np.max(np.abs(Chat - L[n, blk]) / (se_cov + 1e-300)) > 20.0
     assert worst > 0.0
+
+
+@pytest.mark.parametrize("kalman", ["standard", "square-root"])
+def test_batch_minor_stride_halves_equal_whole(ra, kalman):
+    """The batch-minor stride of the lane kernels' records (csrc/records.hpp): 70 trajectories (two waves per block, the second
+    partial, the block boundary inside a wave) solved as one plan, and as two plans of 35, the second with traj_offset = 35, give
+    the same bits -- mv(), sim() and fenrir's solve_mv (deterministic: its halves are two calls on the halved inputs).  A wrong
+    stride B reads or writes a neighbour's element, which a tolerance check against the oracle at B <= 7 can miss."""
+    from rodeo_amd.inference.fenrir import solve_mv as fenrir_solve_mv
+    B, h, N, t_max = 70, 35, 3, 0.15
+    s = fitz_problem(ra, N=N, t_max=t_max, sigma=.1, B=B, seed=7)
+    prior = s["prior"]
+    if kalman == "square-root":
+        prior = (prior[0], np.linalg.cholesky(prior[1]))
+    g = ra.interrogate.interrogate_kramer
+
+    def plan(sl, off):
+        return ra.SolvePlan(ra.ode.fitzhugh_nagumo, s["W"], s["x0"][sl], 0.0, t_max, N, g, prior, kalman_type=kalman,
+                            traj_offset=off, batch_minor=True, theta=s["theta"][sl])
+    plans = [plan(slice(None), 0), plan(slice(0, h), 0), plan(slice(h, B), h)]
+    for p in plans:
+        p.mv(None)
+    (m, v), (m0, v0), (m1, v1) = (p.state_host() for p in plans)
+    assert m.shape == (B, N + 1, 2, 3) and np.all(np.isfinite(m)) and np.all(np.isfinite(v))
+    assert np.array_equal(m[:h], m0) and np.array_equal(m[h:], m1)
+    assert np.array_equal(v[:h], v0) and np.array_equal(v[h:], v1)
+    for p in plans:
+        p.sim(5)
+    x, x0, x1 = (p.x_host() for p in plans)
+    assert np.array_equal(x[:h], x0) and np.array_equal(x[h:], x1)
+    assert not np.array_equal(x[:h], x[h:])
+
+    rng = np.random.default_rng(3)
+    obs_t = np.array([1, 3]) * t_max / N
+    Y = rng.standard_normal((2, 2, 1))
+    Dw = np.zeros((2, 2, 1, 3)); Dw[..., 0] = 1.0
+    Om = np.full((2, 2, 1, 1), 0.01 if kalman == "standard" else 0.1)       # (square-root: the factor of 0.01)
+
+    def fen(sl):
+        return fenrir_solve_mv(None, ra.ode.fitzhugh_nagumo, s["W"], s["x0"][sl], 0.0, t_max, N, g, prior, Y, obs_t, Dw, Om,
+                               kalman_type=kalman, theta=s["theta"][sl])
+    (fm, fv), (fm0, fv0), (fm1, fv1) = fen(slice(None)), fen(slice(0, h)), fen(slice(h, B))
+    assert fm.shape == (B, N + 1, 2, 3) and np.all(np.isfinite(fm)) and np.all(np.isfinite(fv))
+    assert np.array_equal(fm[:h], fm0) and np.array_equal(fm[h:], fm1)
+    assert np.array_equal(fv[:h], fv0) and np.array_equal(fv[h:], fv1)
