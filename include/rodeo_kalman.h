@@ -306,6 +306,24 @@ int rk_dalton_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in,
                     const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
                     int32_t n_obs, int32_t n_bobs);
 
+/* solve_evidence (an addition): the solver's own marginal likelihood log p(Z_{1:N} = 0), the evidence of the interrogations
+ * under the prior, with its per-block parts quad_b = sum_n z_{n,b}^2 / s_{n,b} and logdet_b = sum_n log s_{n,b} (z the
+ * innovation, s its forecast variance):  logdens = -1/2 sum_b (quad_b + logdet_b) - n_block n_steps log(2 pi) / 2, the
+ * blocks summed in block order.  The density is the plain Gaussian one, without the 1e-8 threshold of utils.py:60-78 (so it
+ * is not rk_dalton_loglik's marginal term wherever that rule drops a step); a zero, negative or non-finite s gives inf or
+ * NaN.  Under prior_var_b -> c_b prior_var_b (the factor times sqrt(c_b) in the square-root form) quad_b becomes
+ * quad_b / c_b and logdet_b becomes logdet_b + n_steps log c_b, so c_b = quad_b / n_steps maximises the evidence.
+ * Served: n_bmeas = 1, interrogate rodeo / schober / kramer (not chkrebtii: it draws from the predicted variance), any
+ * built-in right-hand side or a user one with n_bmeas = 1; kalman_type standard with n_bstate 2..6 (2..5 with three or more
+ * blocks) or square-root with n_bstate 2..8.  Routes: the p = 3 MFMA tiles (standard, n_block 1..4, what the tile solver
+ * accepts in filter mode; evidence_tile3_kernels.hpp) unless RK_EVIDENCE_LANES=1 (read per call), else the lane kernels
+ * (evidence_kernels.hpp).  What is not served is refused on cfg alone -- RK_ERR_INVALID (a non-positive size) or
+ * RK_ERR_UNSUPPORTED -- before the handle or any pointer is looked at.
+ * Outputs (device, overwritten; each element has one writer, no atomics): logdens (n_traj); quad and logdet
+ * (n_block, n_traj) batch-minor, block b of trajectory t at [b * n_traj + t].  No per-step state is written anywhere.    */
+int rk_solve_evidence(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, double* logdens, double* quad,
+                      double* logdet);
+
 /* dalton_at: rk_dalton_loglik for observations whose times need not be grid nodes (an addition: the reference places every
  * observation by searchsorted on the grid).  obs / obs_weight / obs_var as for rk_dalton_loglik, in time order.  The device
  * array `table` (n_obs, 4) holds per observation: node, off-grid flag, pre slot, post slot or -1.  With the flag clear the

@@ -12,6 +12,7 @@ from . import ode
 from . import utils
 from . import inference
 from .solve import solve_sim, solve_mv, solve_mv_at, SolvePlan
+from .evidence import solve_evidence, evidence_scale, evidence_at, Evidence
 from .prior.ibm import ibm_init
 from .prior.indep_init import indep_init
 from .device import Device, DeviceArray, default_device

@@ -71,6 +71,9 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_DALTONNG_OBS       */ {"rk::daltonng_obs_kernel<rk::UserObsT>", "daltonng_kernels.hpp", "daltonng_obs_kernel"},
     /* JIT_DALTON_AT          */ {"rk::dalton_fwd_at_kernel<rk::UserRhsT, {P}, {I}, {M}>", "dalton_at_kernels.hpp", "dalton_fwd_at_kernel<user>"},
     /* JIT_DALTON_AT_TILE3    */ {"rk::dalton_fwd_at_tile3_kernel<rk::UserRhsT, {I}>", "dalton_at_tile3_kernels.hpp", "dalton_fwd_at_tile3_kernel<user>"},
+    /* JIT_EVIDENCE           */ {"rk::evidence_kernel<rk::UserRhsT, {P}, {I}>", "evidence_kernels.hpp", "evidence_kernel<user>"},
+    /* JIT_EVIDENCE_TILE3     */ {"rk::evidence_tile3_kernel<rk::UserRhsT, {I}>", "evidence_tile3_kernels.hpp", "evidence_tile3_kernel<user>"},
+    /* JIT_EVIDENCE_SQRT      */ {"rk::evidence_sqrt_kernel<rk::UserRhsT, {P}, {I}>", "evidence_kernels.hpp", "evidence_sqrt_kernel<user>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -416,6 +419,40 @@ int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const
     void* params[] = {&args, (void*)op, (void*)sp, &out};
     return launch_jit(h, jit_key(tile ? JIT_DALTON_AT_TILE3 : JIT_DALTON_AT, c->rhs_id, c, n_bobs),
                       tile ? dalton_tile_geom(a.B, c->n_block, true) : dalton_lane_geom(a.B, true), params);
+}
+
+// solve_evidence around a user right-hand side (evidence_tile3_kernels.hpp / evidence_kernels.hpp).  Its own check of the
+// configuration against the registration: n_block and n_bmeas = 1 only -- the n_bstate range is evidence.hip's, per Kalman
+// form (user_rhs_check's bound of 6 is the standard lane kernels'; the square-root lanes serve 2..8, like user_forward_sqrt).
+int user_evidence_check(const rk_solve_cfg* c) {
+    const UserRhs* u;
+    const int rc = user_rhs(c->rhs_id, &u);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
+               "evidence: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
+    return RK_OK;
+}
+
+// Does evidence_tile3_kernel exist for this user right-hand side (n_bstate = 3, standard form, up to four blocks, NDEP == 1)?
+// Decided by building that kernel itself once (cached): the build that answers is the one the launch uses.
+bool user_evidence_tile_available(const rk_solve_cfg* c) {
+    if (user_evidence_check(c) || c->kalman_type != RK_KALMAN_STANDARD || c->n_bstate != 3 || c->n_block > 4) return false;
+    const int rc = jit_lookup(jit_key(JIT_EVIDENCE_TILE3, c->rhs_id, c), nullptr, nullptr);
+    if (rc && getenv("RK_JIT_VERBOSE")) fprintf(stderr, "[rk] evidence tile kernel not available for user rhs %d: %s\n", c->rhs_id, rk_last_error());
+    return rc == RK_OK;
+}
+
+// the launch, like the built-in instances of evidence.hip; route: 0 tiles, 1 lanes, 2 square-root lanes
+int user_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int route, double* logdens, double* quad,
+                  double* logdet) {
+    const int rc = user_evidence_check(c);
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, &logdens, &quad, &logdet};
+    const JitKind kind = route == 0 ? JIT_EVIDENCE_TILE3 : (route == 1 ? JIT_EVIDENCE : JIT_EVIDENCE_SQRT);
+    const LaunchGeom g = route == 0 ? dalton_tile_geom(a.B, c->n_block, false)
+                                    : (route == 1 ? fwd_lane_geom(a.B) : fwd_sqrt_geom(a.B, c->n_block));
+    return launch_jit(h, jit_key(kind, c->rhs_id, c), g, params);
 }
 
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,

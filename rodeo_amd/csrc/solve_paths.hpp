@@ -53,6 +53,9 @@ enum JitKind : int {
     JIT_DALTONNG_OBS = 17,    // daltonng_obs_kernel (logy_x and the final sum; no right-hand side)
     JIT_DALTON_AT = 18,       // dalton_fwd_at_kernel (dalton_at's log-likelihood)
     JIT_DALTON_AT_TILE3 = 19, // dalton_fwd_at_tile3_kernel (dalton_at's log-likelihood on the p = 3 tiles)
+    JIT_EVIDENCE = 20,        // evidence_kernel (solve_evidence, standard form on the lanes)
+    JIT_EVIDENCE_TILE3 = 21,  // evidence_tile3_kernel (solve_evidence on the p = 3 tiles)
+    JIT_EVIDENCE_SQRT = 22,   // evidence_sqrt_kernel (solve_evidence, square-root form)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -65,6 +68,12 @@ int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Da
                 bool tile, double* out);
 int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const DaltonAt& s, int n_bobs,
                    bool tile, double* out);
+// solve_evidence: the configuration against the registration, whether the tile kernel builds, and the launch; route: 0 tiles,
+// 1 lanes, 2 square-root lanes (evidence.hip's EvRoute)
+int user_evidence_check(const rk_solve_cfg* c);
+bool user_evidence_tile_available(const rk_solve_cfg* c);
+int user_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int route, double* logdens, double* quad,
+                  double* logdet);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them
