@@ -324,6 +324,24 @@ int rk_dalton_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in,
 int rk_solve_evidence(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, double* logdens, double* quad,
                       double* logdet);
 
+/* solve_mv_dynamic / solve_sim_dynamic (an addition): the solver with a per-step calibrated prior scale.  At step n -> n + 1
+ * block b predicts mu- = Q mu and P = Q Sigma Q^T, interrogates at mu- (W~ = ode_weight + wgt_meas, a = mean_meas), forms the
+ * innovation z = 0 - (W~ mu- + a) and r = W~ prior_var W~^T and takes c = max(z^2 / r, scale_min) as the scale of prior_var for
+ * this step: Sigma- = P + c prior_var, var_meas from this Sigma- (rodeo), then the usual update with forecast variance s.
+ * mode = RK_MODE_MV smooths with these predictions into out->mean_state / var_state, RK_MODE_SIM samples into out->x_state
+ * (draws as in rk_solve_sim; mean_state / var_state then hold the filtered moments).  All records are RK_LAYOUT_BATCH_MINOR.
+ * Further outputs (device, overwritten; each element has one writer, no atomics, no workspace): scale (n_steps, n_block,
+ * n_traj), block b of step n of trajectory t at [(n * n_block + b) * n_traj + t]; logdens (n_traj), the log-evidence
+ * -1/2 sum_b sum_n (z^2 / s + log s) - n_block n_steps log(2 pi) / 2 of rk_solve_evidence under the scaled prior.
+ * With scale_min = 0 a step whose z is exactly 0 has c = 0 and s = 0: inf / NaN as the arithmetic produces them.
+ * Served: kalman_type standard, n_bmeas = 1, n_bstate 2..5 (2..4 with three or more blocks), interrogate rodeo / schober /
+ * kramer (not chkrebtii: its point is drawn from the predicted variance, which here depends on the point), any built-in
+ * right-hand side or a user one with n_bmeas = 1; one lane per trajectory forward, one per (trajectory, block) backward.  What is not served is refused on cfg,
+ * mode and scale_min alone -- RK_ERR_INVALID (a non-positive size, another mode, a negative or non-finite scale_min) or
+ * RK_ERR_UNSUPPORTED -- before the handle or any pointer is looked at.                                                      */
+int rk_solve_dynamic(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                     double scale_min, double* scale, double* logdens);
+
 /* dalton_at: rk_dalton_loglik for observations whose times need not be grid nodes (an addition: the reference places every
  * observation by searchsorted on the grid).  obs / obs_weight / obs_var as for rk_dalton_loglik, in time order.  The device
  * array `table` (n_obs, 4) holds per observation: node, off-grid flag, pre slot, post slot or -1.  With the flag clear the

@@ -1,0 +1,225 @@
+// solve_mv_dynamic / solve_sim_dynamic (an addition): host side of rk_solve_dynamic, the solver with
+// the prior variance of every step scaled, per block, by the estimate made at that step (dynamic_kernels.hpp), and the two
+// backward kernels.  One route: the lanes on batch-minor records -- dynamic_fwd_kernel, one lane per trajectory, then
+// dynamic_bwd_mv_kernel or dynamic_bwd_sim_kernel, one lane per (trajectory, block): bwd_mv_kernel / bwd_sim_kernel of
+// solve_small.hip with the prediction re-evaluated as Q Sigma_f[n] Q^T + scale[n] R.  Standard form, n_bstate 2..5 (2..4 with
+// three or more blocks).  Nothing but the outputs is written; there is no workspace.
+#include <cmath>
+#include "common.hpp"
+#include "rhs.hpp"
+#include "solve_args.hpp"
+#include "solve_paths.hpp"
+#include "dynamic_kernels.hpp"
+#include "records.hpp"
+
+namespace rk {
+
+// ---- backward passes: one lane per (block, trajectory) -----------------------------------------------------------
+template <int P>
+__global__ void __launch_bounds__(64) dynamic_bwd_mv_kernel(SolveArgs a, const double* __restrict__ scale) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= a.B * a.D) return;
+    const int blk = l / a.B, b = l - blk * a.B;
+    const size_t B = (size_t)a.B;
+    double Q[P][P], R[P][P];
+    load_block_consts<P>(a, blk, b, Q, R);
+
+    double ms[P], Ss[P][P];                    // carry: smoothed moments at n+1 (solve.py:279-282)
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, ms, Ss);
+    double mf[P], Sf[P][P], c = 0.0;
+    if (a.N >= 2) {
+        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
+        c = *bm_item(scale, 1, B, a.D, a.N - 1, blk, b);
+    }
+    for (int n = a.N - 1; n >= 1; --n) {
+        // software prefetch of the next (earlier) filtered state and its step's scale while this step computes
+        double mfn[P], Sfn[P][P], cn = 0.0;
+        if (n >= 2) {
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
+            cn = *bm_item(scale, 1, B, a.D, n - 1, blk, b);
+        }
+        double mp[P], Sp[P][P], T[P][P], G[P][P];
+        dynamic_propagate<P>(Q, mf, Sf, mp, Sp);         // pred[n+1] re-evaluated from filt[n] and scale[n]
+        dynamic_add_noise<P>(Sp, c, R, Sp);
+        smooth_gain<P>(Q, Sf, Sp, T, G);
+        smooth_mv_block<P>(G, mf, Sf, mp, Sp, ms, Ss);
+        store_moments<P>(a.mean, a.var, B, a.D, n, blk, b, ms, Ss);
+        if (n >= 2) {
+            c = cn;
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                mf[i] = mfn[i];
+#pragma unroll
+                for (int j = 0; j < P; ++j) Sf[i][j] = Sfn[i][j];
+            }
+        }
+    }
+    // time 0 keeps (ode_init, 0) written by the forward pass (solve.py:295-301)
+}
+
+template <int P>
+__global__ void __launch_bounds__(64) dynamic_bwd_sim_kernel(SolveArgs a, const double* __restrict__ scale) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= a.B * a.D) return;
+    const int blk = l / a.B, b = l - blk * a.B;
+    const size_t B = (size_t)a.B;
+    const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
+    double Q[P][P], R[P][P];
+    load_block_consts<P>(a, blk, b, Q, R);
+
+    auto store_x = [&](int n, const double (&x)[P]) {
+        double* xo = bm_item(a.x, P, B, a.D, n, blk, b);
+#pragma unroll
+        for (int i = 0; i < P; ++i) xo[(size_t)i * B] = x[i];
+    };
+
+    double mf[P], Sf[P][P], xn[P], z[P], c = 0.0;
+    // terminal draw x_N ~ N(filt[N]) (solve.py:182-186)
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, mf, Sf);
+    normals<P>(a.seed, traj, (uint32_t)a.N, (uint32_t)blk, PURPOSE_SMOOTH, z);
+    mvn_draw<P>(mf, Sf, z, xn);
+    store_x(a.N, xn);
+    if (a.N >= 2) {
+        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
+        c = *bm_item(scale, 1, B, a.D, a.N - 1, blk, b);
+    }
+    for (int n = a.N - 1; n >= 1; --n) {
+        double mfn[P], Sfn[P][P], cn = 0.0;
+        if (n >= 2) {
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
+            cn = *bm_item(scale, 1, B, a.D, n - 1, blk, b);
+        }
+        double mp[P], Sp[P][P], T[P][P], G[P][P], msim[P], Ssim[P][P];
+        dynamic_propagate<P>(Q, mf, Sf, mp, Sp);
+        dynamic_add_noise<P>(Sp, c, R, Sp);
+        smooth_gain<P>(Q, Sf, Sp, T, G);
+        smooth_sim_block<P>(G, T, mf, Sf, mp, xn, msim, Ssim);
+        normals<P>(a.seed, traj, (uint32_t)n, (uint32_t)blk, PURPOSE_SMOOTH, z);
+        mvn_draw<P>(msim, Ssim, z, xn);
+        store_x(n, xn);
+        if (n >= 2) {
+            c = cn;
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                mf[i] = mfn[i];
+#pragma unroll
+                for (int j = 0; j < P; ++j) Sf[i][j] = Sfn[i][j];
+            }
+        }
+    }
+    // x[0] = ode_init exactly (solve.py:196-204)
+    double x0[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) x0[i] = a.mean[((size_t)blk * P + i) * B + b];
+    store_x(0, x0);
+}
+
+// ---- dispatch ---------------------------------------------------------------------------------------------------
+constexpr int DYNAMIC_PMIN = 2, DYNAMIC_PMAX = 5;
+// largest n_bstate of the forward instances: with three blocks at n_bstate = 5 the lane needs more scratch than evidence_kernel
+// at the same (RHS, P) (716 / 588 / 588 against 604 / 500 / 548 B for Lorenz63), which is the rule an instance ships by
+constexpr int DYNAMIC_PMAX_THREE_BLOCKS = 4;
+template <class RHS>
+constexpr int dynamic_pmax() { return RHS::D >= 3 ? DYNAMIC_PMAX_THREE_BLOCKS : DYNAMIC_PMAX; }
+
+// Is this call served?  Decided on the configuration, the mode and scale_min alone: RK_OK, RK_ERR_INVALID (sizes, mode,
+// scale_min) or RK_ERR_UNSUPPORTED.
+static int dynamic_check(const rk_solve_cfg* c, int mode, double scale_min) {
+    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
+               "dynamic: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", c->n_traj,
+               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
+    RK_REQUIRE(mode == RK_MODE_MV || mode == RK_MODE_SIM, RK_ERR_INVALID, "dynamic: mode must be RK_MODE_MV or RK_MODE_SIM, got %d",
+               mode);
+    RK_REQUIRE(std::isfinite(scale_min) && scale_min >= 0.0, RK_ERR_INVALID, "dynamic: scale_min must be finite and >= 0, got %g",
+               scale_min);
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
+               "dynamic: unknown kalman_type %d", c->kalman_type);
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "dynamic: kalman_type square-root is not built");
+    RK_REQUIRE(c->interrogate != RK_INTERROGATE_CHKREBTII, RK_ERR_UNSUPPORTED,
+               "dynamic: interrogate_chkrebtii is not served (its point is drawn from the predicted variance, which here "
+               "depends on the point through the scale)");
+    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_KRAMER, RK_ERR_UNSUPPORTED,
+               "dynamic: interrogate id %d is not supported (rodeo, schober, kramer)", c->interrogate);
+    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "dynamic: n_bmeas = 1 only (the dense / indep_init form is not served), "
+               "got %d", c->n_bmeas);
+    RK_REQUIRE(c->n_bstate >= DYNAMIC_PMIN && c->n_bstate <= DYNAMIC_PMAX, RK_ERR_UNSUPPORTED,
+               "dynamic: n_bstate in %d..%d, got %d", DYNAMIC_PMIN, DYNAMIC_PMAX, c->n_bstate);
+    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= DYNAMIC_PMAX_THREE_BLOCKS, RK_ERR_UNSUPPORTED,
+               "dynamic: n_bstate up to %d with three or more blocks (the lane kernel spills more than solve_evidence's), got %d",
+               DYNAMIC_PMAX_THREE_BLOCKS, c->n_bstate);
+    if (is_user_rhs(c->rhs_id)) return user_dynamic_check(c);
+    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "dynamic: unknown rhs_id %d", c->rhs_id);
+    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "dynamic: rhs %d needs another n_block than %d",
+               c->rhs_id, c->n_block);
+    return RK_OK;
+}
+
+template <class RHS>
+static int launch_dynamic_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double scale_min, double* scale,
+                              double* logdens) {
+    const LaunchGeom g = fwd_lane_geom(a.B);
+    bool ok = false;
+    dispatch_int<DYNAMIC_PMIN, dynamic_pmax<RHS>()>(c->n_bstate, [&](auto P) {
+        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
+            LaunchTimer t(h, "dynamic_fwd_kernel");
+            hipLaunchKernelGGL((dynamic_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, scale_min, scale, logdens);
+            t.stop();
+            ok = true;
+        });
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dynamic: no kernel for rhs %d, n_bstate %d, interrogate %d", c->rhs_id, c->n_bstate,
+               c->interrogate);
+    RK_HIP(hipGetLastError());
+    return RK_OK;
+}
+
+static int launch_dynamic_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const double* scale) {
+    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
+    const bool sim = mode == RK_MODE_SIM;
+    LaunchTimer t(h, sim ? "dynamic_bwd_sim_kernel" : "dynamic_bwd_mv_kernel");
+    const bool ok = dispatch_int<DYNAMIC_PMIN, DYNAMIC_PMAX>(c->n_bstate, [&](auto P) {
+        if (sim) hipLaunchKernelGGL((dynamic_bwd_sim_kernel<P>), grid, block, 0, h->stream, a, scale);
+        else hipLaunchKernelGGL((dynamic_bwd_mv_kernel<P>), grid, block, 0, h->stream, a, scale);
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dynamic: no backward kernel for n_bstate %d", c->n_bstate);
+    t.stop();
+    RK_HIP(hipGetLastError());
+    return RK_OK;
+}
+
+}  // namespace rk
+
+using namespace rk;
+
+extern "C" {
+
+int rk_solve_dynamic(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                     double scale_min, double* scale, double* logdens) {
+    RK_REQUIRE(c, RK_ERR_INVALID, "rk_solve_dynamic: null cfg");
+    int rc = dynamic_check(c, mode, scale_min);                     // (the configuration alone, before anything else is looked at)
+    if (rc) return rc;
+    RK_REQUIRE(h && out && scale && logdens, RK_ERR_INVALID, "rk_solve_dynamic: null argument");
+    rc = check_cfg(c, in);
+    if (rc) return rc;
+    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID, "rk_solve_dynamic: out->mean_state / var_state must not be NULL");
+    RK_REQUIRE(mode != RK_MODE_SIM || out->x_state, RK_ERR_INVALID, "rk_solve_dynamic: RK_MODE_SIM needs out->x_state");
+    rc = begin_solve(h);
+    if (rc) return rc;
+    SolveArgs a;
+    make_args(c, in, out, a);
+    if (is_user_rhs(c->rhs_id)) {
+        rc = user_dynamic(h, c, a, scale_min, scale, logdens);
+    } else {
+        rc = RK_ERR_UNSUPPORTED;
+        with_builtin_rhs(c->rhs_id, [&](auto rhs) {
+            using RHS = decltype(rhs);
+            rc = check_n_theta<RHS>(c, a);
+            if (rc) return;
+            rc = launch_dynamic_fwd<RHS>(h, c, a, scale_min, scale, logdens);
+        });
+    }
+    if (rc) return rc;
+    return launch_dynamic_bwd(h, c, a, mode, scale);
+}
+
+}  // extern "C"

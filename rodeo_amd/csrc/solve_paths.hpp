@@ -56,6 +56,7 @@ enum JitKind : int {
     JIT_EVIDENCE = 20,        // evidence_kernel (solve_evidence, standard form on the lanes)
     JIT_EVIDENCE_TILE3 = 21,  // evidence_tile3_kernel (solve_evidence on the p = 3 tiles)
     JIT_EVIDENCE_SQRT = 22,   // evidence_sqrt_kernel (solve_evidence, square-root form)
+    JIT_DYNAMIC = 23,         // dynamic_fwd_kernel (solve_mv_dynamic / solve_sim_dynamic, the forward lanes)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -74,6 +75,9 @@ int user_evidence_check(const rk_solve_cfg* c);
 bool user_evidence_tile_available(const rk_solve_cfg* c);
 int user_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int route, double* logdens, double* quad,
                   double* logdet);
+// solve_mv_dynamic / solve_sim_dynamic: the configuration against the registration and the forward launch (dynamic.hip)
+int user_dynamic_check(const rk_solve_cfg* c);
+int user_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double scale_min, double* scale, double* logdens);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them
