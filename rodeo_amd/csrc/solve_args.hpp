@@ -13,6 +13,9 @@ struct SolveArgs {
     uint64_t seed, traj_offset;
     const double *W, *x0, *Q, *R, *theta;
     int W_b, x0_b, Q_b, R_b, theta_b;
+    // p = 3 tile path, solve_mv: the filtered rows 1 .. N-1 are packed in place (tile3_pack.hpp).  Set by tile3_solve
+    // alone; zero for every other caller and in the hiprtc builds.
+    int pack = 0;
     double *mean, *var, *mean_pred, *var_pred, *x;
 };
 

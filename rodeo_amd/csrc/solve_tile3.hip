@@ -57,9 +57,14 @@ __device__ __forceinline__ int lds_byte(int s, int g, int which, int idx) {
 // other, which evens out the load of the SIMDs (a speed consideration only -- any placement gives the same results).
 // The producer waves of the backward kernels (bwd_mv_tile3_kernel, fenrir_bwd_tile3_kernel): wave 1 + q owns the chunks
 // ch = q (mod 3) and hands [M-, G~^T, M_f] of every (step, tile) of a chunk over in LDS buffer ch & 1.
+// What the producers read as filt[n]: the whole natural tile (Fenrir); the natural tile with Sigma_f's lower triangle
+// taken from the upper one (solve_mv); or the packed 72-byte records of tile3_pack.hpp (solve_mv behind a packing forward
+// kernel), which hold the upper triangle only -- so the last two give the same bits.
+enum { FILT_NATURAL = 0, FILT_NATURAL_SYM = 1, FILT_PACKED = 2 };
+
 __device__ __forceinline__ void tile3_gain_producers(const SolveArgs& a, const double* __restrict__ tiles, int D, int tw, int wave,
                                                      int lane, int n_tiles, size_t tstride, int n_chunks, char* lds_raw,
-                                                     char* zones) {
+                                                     char* zones, const int filt) {
     constexpr int P = 3;
     // ---------------- producers: one lane per (step-in-chunk, tile) ----------------
     const int p = wave - 1;
@@ -86,8 +91,21 @@ __device__ __forceinline__ void tile3_gain_producers(const SolveArgs& a, const d
 #pragma unroll
     for (int i = 0; i < 6; ++i) { const int j = 64 * i + lane; frow[i] = j / 24; fcol[i] = (j % 24) * 16; }
     const char* const wave_tiles = (const char*)(tiles + (size_t)tw * 4 * TILE_DOUBLES);
+    // Packed: the zone is the image of the chunk's groups instead, 12 or 15 whole stripe rows in ascending order (5 groups =
+    // 5760 B of the 6 KiB); the pieces behind them are not fetched.  The rows lie in 1 .. N-1 (tile3_pack.hpp, invariant 1).
+    auto chunk_lo = [&](int ch) { const int n_lo = a.N - CHUNK - ch * CHUNK; return n_lo < 1 ? 1 : n_lo; };
     auto fetch = [&](int ch) {
         const int n_hi = a.N - 1 - ch * CHUNK;
+        if (filt == FILT_PACKED) {
+            const int n_lo = chunk_lo(ch), n_rows = tile3_pack_chunk_rows(n_lo, n_hi);
+            const char* const first = wave_tiles + (size_t)tile3_pack_chunk_first_row(n_lo) * tstride * 8;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                // (INVARIANT of lds_barrier(), as below)
+                if (frow[i] < n_rows) lds_dma16(first + (size_t)frow[i] * tstride * 8 + fcol[i], zone_lds + 1024 * i);
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const int n = n_hi - frow[i];                        // rows past the start (n < 1) are clamped, never handed over
@@ -108,17 +126,30 @@ __device__ __forceinline__ void tile3_gain_producers(const SolveArgs& a, const d
             if (ch1 < n_chunks) {
                 lds_dma_wait_all();
                 double buf[TILE_DOUBLES];
+                if (filt == FILT_PACKED) {
+                    // this lane's record: 9 doubles at an 8-byte boundary (72-byte stride: no bank conflict), into the
+                    // slots of the natural tile's upper triangle and mean column
+                    const int n_lo = chunk_lo(ch1), n = a.N - 1 - ch1 * CHUNK - s;
+                    const double* const rec = (const double*)(zone + tile3_pack_zone_byte(n_lo, n < n_lo ? n_lo : n, g));
 #pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const double2 v = *(const double2*)(zone + 96 * lane + 16 * k);      // lane = 4 s + g
-                    buf[2 * k] = v.x; buf[2 * k + 1] = v.y;
+                    for (int i = 0; i < P; ++i) {
+#pragma unroll
+                        for (int j = i; j < P; ++j) buf[i * 4 + j] = buf[j * 4 + i] = rec[tile3_pack_slot(i, j)];
+                        buf[i * 4 + 3] = rec[tile3_pack_slot(i, 3)];
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) {
+                        const double2 v = *(const double2*)(zone + 96 * lane + 16 * k);      // lane = 4 s + g
+                        buf[2 * k] = v.x; buf[2 * k + 1] = v.y;
+                    }
                 }
                 lds_reads_done();
                 if (ch1 + 3 < n_chunks) fetch(ch1 + 3);
 #pragma unroll
                 for (int i = 0; i < P; ++i) {
 #pragma unroll
-                    for (int j = 0; j < P; ++j) Sf[i][j] = buf[i * 4 + j];
+                    for (int j = 0; j < P; ++j) Sf[i][j] = buf[filt == FILT_NATURAL || i <= j ? i * 4 + j : j * 4 + i];
                     mf[i] = buf[i * 4 + 3];
                 }
                 predict_block<P>(Q, R, mf, Sf, mp, Sp);          // pred[n+1] from filt[n]   (standard.py:57-59)
@@ -185,7 +216,12 @@ __global__ void __launch_bounds__(256) bwd_mv_tile3_kernel(SolveArgs a, double* 
     const int role = wave;
 
     if (role >= 1) {
-        tile3_gain_producers(a, tiles, D, tw, role, lane, n_tiles, tstride, n_chunks, lds_raw, zones);
+        // (a ragged last tile-wave is never packed: the forward kernel takes the same decision)
+        // (two copies of the producers with the layout a constant in each: the natural one is then the code it was)
+        if (a.pack && tile3_pack_full_wave(tw, n_tiles))
+            tile3_gain_producers(a, tiles, D, tw, role, lane, n_tiles, tstride, n_chunks, lds_raw, zones, FILT_PACKED);
+        else
+            tile3_gain_producers(a, tiles, D, tw, role, lane, n_tiles, tstride, n_chunks, lds_raw, zones, FILT_NATURAL_SYM);
     } else {
         // ---------------- consumer: the carry recursion on MFMA tiles ----------------
         const TileCoord tc = tile_coord<1>(tw, lane, n_tiles);              // (b, blk) not needed here
@@ -259,7 +295,14 @@ __global__ void __launch_bounds__(256) bwd_mv_tile3_kernel(SolveArgs a, double* 
                     }
                 }
             }
-            lds_barrier();   
+            // Packed rows (a.pack, tile3_pack.hpp): the natural rows this tick wrote, n_hi .. n_hi - cnt + 1, lie over packed
+            // records of this workgroup's own stripe, and stripe row m holds records of steps >= m - 1 only (invariant 2):
+            // steps of this chunk and, in its lowest row, of the next one.  A producer has a chunk's records in its
+            // landing zone at lds_dma_wait_all() of stage 1, THREE barriers before the chunk is smoothed: the loads of
+            // chunk t + 1 were complete before the barrier that ended tick t - 2, the stores above were issued behind the
+            // one that ended tick t - 1.  No other workgroup reads or writes this stripe.  So only consumed records are
+            // overwritten, and this barrier need not wait for the stores (lds_barrier()).
+            lds_barrier();
         }
     }
 }
@@ -309,7 +352,7 @@ __device__ __forceinline__ void fenrir_tile3_body(const SolveArgs& a, const doub
     char* const lds_raw = lds_all;
 
     if (wave >= 1) {
-        tile3_gain_producers(a, tiles, D, tw, wave, lane, n_tiles, tstride, n_chunks, lds_raw, zones);
+        tile3_gain_producers(a, tiles, D, tw, wave, lane, n_tiles, tstride, n_chunks, lds_raw, zones, FILT_NATURAL);
     } else {
         // ---------------- consumer: the backward filter on MFMA tiles ----------------
         __builtin_amdgcn_s_setprio(3);
@@ -781,9 +824,10 @@ __global__ void __launch_bounds__(256, 2) bwd_sim_tile3_kernel(SolveArgs a, doub
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------
-// Note on occupancy: the forward recursion is one dependent chain per wave (about 290 cycles per step: 7 MFMAs + 27
-// VALU operations issued in order), so a launch takes n_steps x that latency however few waves there are; fewer tiles
-// per wave or more waves per workgroup change nothing (measured, round 1) -- only more trajectories raise throughput.
+// Note on occupancy: the forward recursion is one dependent chain per wave (the headline step: about 240 cycles, 7 MFMAs,
+// 13 VALU operations and one store issued in order), so a launch takes n_steps x that latency however few waves there
+// are; fewer tiles per wave or more waves per workgroup change nothing (measured, round 1) -- only more trajectories
+// raise throughput.
 template <class RHS>
 static int launch_fwd_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles) {
     const LaunchGeom g = fwd_tile_geom(a.B, RHS::D);
@@ -828,12 +872,29 @@ int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs&
     return tile3_solve(h, c, a, tiles, RK_MODE_SIM, &lp);
 }
 
+// solve_mv packs the filtered rows in place (tile3_pack.hpp) where the forward instance is the headline loop, the one
+// that honours SolveArgs::pack: a built-in right-hand side in tile form at n_block = 2, not chkrebtii; N >= 16; and the
+// whole tile array inside one store window of the forward kernel.  RK_TILE3_PACK = 0 (read per call) keeps the natural
+// rows: same bits, for parity tests and measurements.
+template <class RHS>
+static bool tile3_packs(const rk_solve_cfg* c, const SolveArgs& a, int mode) {
+    if (!(rhs_has_tile_form<RHS>::value && RHS::D == 2) || mode != RK_MODE_MV || c->interrogate == RK_INTERROGATE_CHKREBTII) return false;
+    const char* const force = getenv("RK_TILE3_PACK");
+    if (force && force[0] == '0') return false;
+    const size_t array_bytes = (size_t)(a.N + 1) * a.B * RHS::D * TILE_DOUBLES * sizeof(double);
+    return a.N >= T3P_MIN_STEPS && array_bytes < 0x7fff0000ull;
+}
+
 int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp) {
     int rc = RK_ERR_UNSUPPORTED;
+    SolveArgs ap = a;
     if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, JIT_TILE3);
-    else with_builtin_rhs(c->rhs_id, [&](auto rhs) { rc = launch_fwd_tile<decltype(rhs)>(h, c, a, tiles); });     // (tile3_supported: a built-in id)
+    else with_builtin_rhs(c->rhs_id, [&](auto rhs) {                                                  // (tile3_supported: a built-in id)
+        ap.pack = tile3_packs<decltype(rhs)>(c, a, mode);
+        rc = launch_fwd_tile<decltype(rhs)>(h, c, ap, tiles);
+    });
     if (rc || mode == RK_MODE_FILTER) return rc;
-    return tile3_backward(h, a, tiles, mode, lp);
+    return tile3_backward(h, ap, tiles, mode, lp);
 }
 
 // the smoothing (RK_MODE_MV) or sampling (RK_MODE_SIM) pass over RK_LAYOUT_TILE3 records

@@ -7,6 +7,7 @@
 #include "mfma_tile.hpp"
 #include "philox.hpp"
 #include "solve_args.hpp"
+#include "tile3_pack.hpp"
 
 namespace rk {
 
@@ -153,15 +154,17 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
     // The store goes to row soff / row_bytes of the open window and moves soff on by one row.  The second asm hands
     // the MFMA's result on to its readers and clobbers memory: the store stays in front of them, in its own step
     // (in an unrolled loop hipcc otherwise collects the stores of several steps behind the last one's first MFMA).
-#define RK_STORE_BEHIND(M_, mfma_result)                                               \
+    // RK_STORE_AT: the same store at the per-lane offset voff_, soff moved on by adv_ bytes.
+#define RK_STORE_AT(M_, mfma_result, voff_, adv_)                                      \
     do {                                                                               \
         asm("" : "+v"(M_) : "v"(mfma_result));                                         \
         u32x2 bits_;                                                                   \
         __builtin_memcpy(&bits_, &M_, 8);                                              \
-        __builtin_amdgcn_raw_buffer_store_b64(bits_, rsrc, bvoff, (int)soff, 0);       \
-        soff += (uint32_t)row_bytes;                                                   \
+        __builtin_amdgcn_raw_buffer_store_b64(bits_, rsrc, voff_, (int)soff, 0);       \
+        soff += (adv_);                                                                \
         asm volatile("" : "+v"(mfma_result) : : "memory");                             \
     } while (0)
+#define RK_STORE_BEHIND(M_, mfma_result) RK_STORE_AT(M_, mfma_result, bvoff, (uint32_t)row_bytes)
 
     if constexpr (rhs_has_tile_form<RHS>::value && D == 2 && ITG != RK_INTERROGATE_CHKREBTII) {
         // The headline path.  A step is ONE dependent chain for its wave (seven MFMAs, thirteen VALU instructions, one
@@ -180,9 +183,30 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
 #define RK_AFTER(in, res) asm("" : "+v"(in) : "v"(res))
         // One step, written once: the time loop below runs it four times per iteration (the loop's counter, compare and
         // taken branch -- behind which this SIMD's only wave refetches -- once per four steps) and a tail of up to three.
-        auto step = [&]() __attribute__((always_inline)) {
+        // Where a step's state goes is fixed in front of the loop, for the four steps of an iteration: voff[j] is the lane's
+        // byte offset of step j, soff moves on once per iteration.  Natural layout: the lane's slot in time row j, four
+        // rows per iteration.  Packed (a.pack and all four tiles of the wave exist; tile3_pack.hpp): the lane's slot in
+        // the group of four 72-byte records, which fills the wave's stripe of THREE rows, shifted by one row; the lower
+        // triangle joins the lanes without a slot.  Same loop body for both, no branch in it.
+        const bool pack = a.pack && tile3_pack_full_wave(blockIdx.x, n_tiles);
+        int voff[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int gb = tile3_pack_group_byte(j, tc.g, tile3_pack_slot(r < 3 ? r : 0, c));
+            const uint32_t packed = (uint32_t)tile3_pack_row(0, gb) * (uint32_t)row_bytes + (uint32_t)tile3_pack_col(gb);
+            const bool slot = st && (!pack || tile3_pack_slot(r, c) >= 0);
+            voff[j] = slot ? (int)(pack ? packed : (uint32_t)bvoff + (uint32_t)j * (uint32_t)row_bytes) : (int)0x80000000;
+        }
+        const uint32_t quad_bytes = (pack ? 3u : 4u) * (uint32_t)row_bytes;
+        if (pack) {                                                 // row 0 stays natural (the packed record of step 0 is in row 1)
+            const __amdgpu_buffer_rsrc_t first = __builtin_amdgcn_make_buffer_rsrc((void*)row0, 0, (int)SLICE, 0x00020000);
+            u32x2 bits;
+            __builtin_memcpy(&bits, &M, 8);
+            __builtin_amdgcn_raw_buffer_store_b64(bits, first, bvoff, 0, 0);
+        }
+        auto step = [&](int vo) __attribute__((always_inline)) {
             double U = MF(M, Qt, 0.0);                              // (Q~ M)^T                         (standard.py:57-59)
-            RK_STORE_BEHIND(M, U);                                  // the state of time n
+            RK_STORE_AT(M, U, vo, 0u);                              // the state of time n
             double B0 = MF(Y0, M, 0.0);                             // row 0 of Q~ M in every row: mu-_0 in column 3
             RK_AFTER(U, B0);
             double MpT = MF(Qt0, U, RtT);                           // M-^T with row 3 zeroed: the offset entry of X_w must not enter Z0
@@ -209,9 +233,12 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
         };
         for (int n0 = 0; n0 < a.N;) {
             const int n1 = open_window(n0);
-            const uint32_t soff_quads = (uint32_t)((n1 - n0) & ~3) * (uint32_t)row_bytes;   // soff counts the loop
-            while (soff != soff_quads) { step(); step(); step(); step(); }
-            for (int i = (n1 - n0) & 3; i > 0; --i) step();
+            const uint32_t soff_quads = (uint32_t)((n1 - n0) >> 2) * quad_bytes;           // soff counts the loop
+            while (soff != soff_quads) { step(voff[0]); step(voff[1]); step(voff[2]); step(voff[3]); soff += quad_bytes; }
+            const int tail = (n1 - n0) & 3;
+            if (tail > 0) step(voff[0]);
+            if (tail > 1) step(voff[1]);
+            if (tail > 2) step(voff[2]);
             n0 = n1;
         }
         store_last_row(M);
@@ -385,6 +412,7 @@ __global__ void __launch_bounds__(64 * TileWaves<RHS::D>::value) fwd_tile3_kerne
     }
     store_last_row(M);
 #undef RK_STORE_BEHIND
+#undef RK_STORE_AT
 }
 
 }  // namespace rk
