@@ -74,25 +74,9 @@ __global__ void __launch_bounds__(64) dalton_fwd_at_kernel(SolveArgs a, DaltonOb
     const int b = blockIdx.x * 32 + (lane & 31);
     double acc = 0.0;
     if (b < a.B) {
-        double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA];
-#pragma unroll
-        for (int blk = 0; blk < D; ++blk) {
-            load_block_consts<P>(a, blk, b, Q[blk], R[blk]);
-#pragma unroll
-            for (int j = 0; j < P; ++j) W[blk][j] = ld(a.W, (size_t)blk * P + j, a.W_b, a.B, b);
-        }
-#pragma unroll
-        for (int k = 0; k < RHS::NTHETA; ++k) th[k] = a.theta ? ld(a.theta, k, a.theta_b, a.B, b) : 0.0;
-
-        double mu[D][P], S[D][P][P];
-#pragma unroll
-        for (int blk = 0; blk < D; ++blk)
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                mu[blk][i] = ld(a.x0, (size_t)blk * P + i, a.x0_b, a.B, b);
-#pragma unroll
-                for (int j = 0; j < P; ++j) S[blk][i][j] = 0.0;
-            }
+        double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA], mu[D][P], S[D][P][P];
+        lane_load_model<RHS, P>(a, b, Q, R, W, th);
+        lane_load_init<D, P>(a, b, mu, S);
         // an observation at t_min contributes log p(y_0 | x_0) to the joint density and does not update x_0 (dalton.py:206-215)
         int i = 0;
         if (o.n_obs > 0 && s.tab[0] == 0 && s.tab[1] == 0) {
@@ -143,9 +127,8 @@ __global__ void __launch_bounds__(64) dalton_fwd_at_kernel(SolveArgs a, DaltonOb
 #pragma unroll
                 for (int blk = 0; blk < D; ++blk) predict_block<P>(Q[blk], R[blk], mu[blk], S[blk], mup[blk], Sp[blk]);
             }
-            const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;
             double wgt[D][P], am[D], V[D];
-            interrogate_traj<RHS, P, ITG>(W, th, t, mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
+            interrogate_traj<RHS, P, ITG>(W, th, step_time(a, n), mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
             const bool node_here = i < o.n_obs && s.tab[4 * i + 1] == 0 && s.tab[4 * i] == n + 1;
             const bool obs_here = joint && node_here;
 #pragma unroll
@@ -159,8 +142,7 @@ __global__ void __launch_bounds__(64) dalton_fwd_at_kernel(SolveArgs a, DaltonOb
             if (node_here) ++i;
         }
     }
-    const double marg = __shfl_down(acc, 32, 64);                         // lane l < 32 reads lane l + 32
-    if (lane < 32 && b < a.B) logdens[b] = acc - marg;
+    store_joint_minus_marginal(acc, lane, b, a.B, logdens);
 }
 
 }  // namespace rk

@@ -28,28 +28,16 @@ struct DaltonObs {
 template <int P, int MO>
 __device__ __forceinline__ void dalton_observe(const DaltonObs& o, size_t ib, double (&m)[P], double (&S)[P][P], double& acc) {
     const double LOG_2PI = 1.83787706640934548356;
-    double D[MO][P], y[MO], Wf[MO][MO], DS[MO][P], X[MO][P], z[MO];
+    double D[MO][P], y[MO], Om[MO][MO], Wf[MO][MO], DS[MO][P], z[MO];
 #pragma unroll
     for (int j = 0; j < MO; ++j) {
         y[j] = o.obs[ib * MO + j];
 #pragma unroll
         for (int k = 0; k < P; ++k) D[j][k] = o.obs_w[(ib * MO + j) * P + k];
+#pragma unroll
+        for (int l = 0; l < MO; ++l) Om[j][l] = o.obs_v[(ib * MO + j) * MO + l];
     }
-#pragma unroll
-    for (int j = 0; j < MO; ++j) {
-        z[j] = y[j] - dot<P>(D[j], m);
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-            double t = D[j][0] * S[0][c];
-#pragma unroll
-            for (int k = 1; k < P; ++k) t = fma(D[j][k], S[k][c], t);
-            DS[j][c] = t;                                                   // D Sigma
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < MO; ++j)
-#pragma unroll
-        for (int l = 0; l < MO; ++l) Wf[j][l] = dot<P>(DS[j], D[l]) + o.obs_v[(ib * MO + j) * MO + l];    // var_fore
+    observe_forecast<P, MO>(D, y, Om, m, S, z, DS, Wf);
     if constexpr (MO == 1) {
         if (fabs(Wf[0][0]) > 1e-8) acc += -0.5 * (z[0] * z[0] / Wf[0][0] + log(Wf[0][0])) - 0.5 * LOG_2PI;
     } else {
@@ -67,57 +55,24 @@ __device__ __forceinline__ void dalton_observe(const DaltonObs& o, size_t ib, do
             if (fabs(w[k]) > 1e-8) acc += -0.5 * (zk * zk / w[k] + log(w[k])) - 0.5 * LOG_2PI;
         }
     }
-#pragma unroll
-    for (int j = 0; j < MO; ++j)
-#pragma unroll
-        for (int r = 0; r < P; ++r) X[j][r] = dot<P>(S[r], D[j]);           // (Sigma D^T)^T
-    lu_solve<MO, P>(Wf, X);                                                 // K^T
-#pragma unroll
-    for (int r = 0; r < P; ++r) {
-        double t = X[0][r] * z[0];
-#pragma unroll
-        for (int j = 1; j < MO; ++j) t = fma(X[j][r], z[j], t);
-        double dS[P];
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-            double u = X[0][r] * DS[0][c];
-#pragma unroll
-            for (int j = 1; j < MO; ++j) u = fma(X[j][r], DS[j][c], u);
-            dS[c] = u;
-        }
-        m[r] = m[r] + t;
-#pragma unroll
-        for (int c = 0; c < P; ++c) S[r][c] = S[r][c] - dS[c];
-    }
+    observe_apply<P, MO>(D, z, DS, Wf, m, S);
 }
 
-// z forecast, log-density and update of one block (x_meas = 0, n_bmeas = 1): update_block_m1 with a division, whose
-// forecast variance the log-density shares
+// z forecast, log-density and update of one block (x_meas = 0, n_bmeas = 1): update_z with a division per gain element,
+// whose forecast variance the log-density shares
 template <int P>
 __device__ __forceinline__ void dalton_update_z(const double (&Wm)[P], double am, double V, const double (&mup)[P],
                                                 const double (&Sp)[P][P], double (&mu)[P], double (&S)[P][P], double& acc) {
     const double LOG_2PI = 1.83787706640934548356;
-    const double yhat = dot<P>(Wm, mup) + am;
-    double WS[P], SW[P];
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-        double s = Wm[0] * Sp[0][j];
-#pragma unroll
-        for (int i = 1; i < P; ++i) s = fma(Wm[i], Sp[i][j], s);
-        WS[j] = s;
-    }
-    const double s = dot<P>(WS, Wm) + V;                                    // var_fore
-    const double innov = 0.0 - yhat;
+    double innov, s;
+    update_z<P, GAIN_DIVIDE>(Wm, am, V, mup, Sp, mu, S, innov, s);
     if (fabs(s) > 1e-8) acc += -0.5 * (innov * innov / s + log(s)) - 0.5 * LOG_2PI;
-#pragma unroll
-    for (int i = 0; i < P; ++i) SW[i] = dot<P>(Sp[i], Wm);
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        const double K = SW[i] / s;
-        mu[i] = fma(K, innov, mup[i]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) S[i][j] = fma(-K, WS[j], Sp[i][j]);
-    }
+}
+
+// the end of the two-filters-per-wave kernels: lane l < 32 holds trajectory b's joint sum, lane l + 32 its marginal one
+__device__ __forceinline__ void store_joint_minus_marginal(double acc, int lane, int b, int B, double* logdens) {
+    const double marg = __shfl_down(acc, 32, 64);                         // lane l < 32 reads lane l + 32
+    if (lane < 32 && b < B) logdens[b] = acc - marg;
 }
 
 // STORE = false (log-likelihood): a wave holds 32 trajectories, lanes 0..31 run their joint filters and lanes 32..63 their
@@ -133,39 +88,12 @@ __global__ void __launch_bounds__(64) dalton_fwd_kernel(SolveArgs a, DaltonObs o
     double acc = 0.0;
     if (b < a.B) {
         const size_t B = (size_t)a.B;
-        double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA];
-#pragma unroll
-        for (int blk = 0; blk < D; ++blk) {
-            load_block_consts<P>(a, blk, b, Q[blk], R[blk]);
-#pragma unroll
-            for (int j = 0; j < P; ++j) W[blk][j] = ld(a.W, (size_t)blk * P + j, a.W_b, a.B, b);
-        }
-#pragma unroll
-        for (int k = 0; k < RHS::NTHETA; ++k) th[k] = a.theta ? ld(a.theta, k, a.theta_b, a.B, b) : 0.0;
-
-        double mu[D][P], S[D][P][P];
-#pragma unroll
-        for (int blk = 0; blk < D; ++blk)
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                mu[blk][i] = ld(a.x0, (size_t)blk * P + i, a.x0_b, a.B, b);
-#pragma unroll
-                for (int j = 0; j < P; ++j) S[blk][i][j] = 0.0;
-            }
+        double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA], mu[D][P], S[D][P][P];
+        lane_load_model<RHS, P>(a, b, Q, R, W, th);
+        lane_load_init<D, P>(a, b, mu, S);
         if constexpr (STORE) {                                              // time 0: (ode_init, 0) (dalton.py:362-370)
-#pragma unroll
-            for (int blk = 0; blk < D; ++blk)
-#pragma unroll
-                for (int i = 0; i < P; ++i) {
-                    const size_t em = (size_t)blk * P + i;
-                    a.mean[em * B + b] = mu[blk][i];
-                    if (a.mean_pred) a.mean_pred[em * B + b] = mu[blk][i];
-#pragma unroll
-                    for (int j = 0; j < P; ++j) {
-                        a.var[(em * P + j) * B + b] = 0.0;
-                        if (a.mean_pred) a.var_pred[(em * P + j) * B + b] = 0.0;
-                    }
-                }
+            store_moments_all<D, P>(a.mean, a.var, B, 0, b, mu, S);
+            if (a.mean_pred) store_moments_all<D, P>(a.mean_pred, a.var_pred, B, 0, b, mu, S);
         }
         // an observation at t_min contributes log p(y_0 | x_0) to the joint density and does not update x_0 (dalton.py:206-215)
         int i = 0;
@@ -187,14 +115,12 @@ __global__ void __launch_bounds__(64) dalton_fwd_kernel(SolveArgs a, DaltonObs o
         }
 
         const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
-        const size_t mstride = (size_t)D * P * B, vstride = (size_t)D * P * P * B;
         for (int n = 0; n < a.N; ++n) {
             double mup[D][P], Sp[D][P][P];
 #pragma unroll
             for (int blk = 0; blk < D; ++blk) predict_block<P>(Q[blk], R[blk], mu[blk], S[blk], mup[blk], Sp[blk]);
-            const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;
             double wgt[D][P], am[D], V[D];
-            interrogate_traj<RHS, P, ITG>(W, th, t, mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
+            interrogate_traj<RHS, P, ITG>(W, th, step_time(a, n), mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
             const bool obs_here = joint && i < o.n_obs && o.obs_ind[i] == n + 1;
 #pragma unroll
             for (int blk = 0; blk < D; ++blk) {
@@ -206,37 +132,12 @@ __global__ void __launch_bounds__(64) dalton_fwd_kernel(SolveArgs a, DaltonObs o
             }
             if (obs_here) ++i;
             if constexpr (STORE) {
-                double* mo = a.mean + (size_t)(n + 1) * mstride + b;
-                double* vo = a.var + (size_t)(n + 1) * vstride + b;
-#pragma unroll
-                for (int blk = 0; blk < D; ++blk)
-#pragma unroll
-                    for (int r = 0; r < P; ++r) {
-                        const size_t em = (size_t)blk * P + r;
-                        mo[em * B] = mu[blk][r];
-#pragma unroll
-                        for (int c = 0; c < P; ++c) vo[(em * P + c) * B] = S[blk][r][c];
-                    }
-                if (a.mean_pred) {
-                    double* mpo = a.mean_pred + (size_t)(n + 1) * mstride + b;
-                    double* vpo = a.var_pred + (size_t)(n + 1) * vstride + b;
-#pragma unroll
-                    for (int blk = 0; blk < D; ++blk)
-#pragma unroll
-                        for (int r = 0; r < P; ++r) {
-                            const size_t em = (size_t)blk * P + r;
-                            mpo[em * B] = mup[blk][r];
-#pragma unroll
-                            for (int c = 0; c < P; ++c) vpo[(em * P + c) * B] = Sp[blk][r][c];
-                        }
-                }
+                store_moments_all<D, P>(a.mean, a.var, B, n + 1, b, mu, S);
+                if (a.mean_pred) store_moments_all<D, P>(a.mean_pred, a.var_pred, B, n + 1, b, mup, Sp);
             }
         }
     }
-    if constexpr (!STORE) {
-        const double marg = __shfl_down(acc, 32, 64);                     // lane l < 32 reads lane l + 32
-        if (lane < 32 && b < a.B) logdens[b] = acc - marg;
-    }
+    if constexpr (!STORE) store_joint_minus_marginal(acc, lane, b, a.B, logdens);
 }
 
 }  // namespace rk

@@ -42,52 +42,6 @@ struct NgWs {
 
 __host__ __device__ constexpr int ng_rec_doubles(int p) { return 3 * p * p + 2 * p + 2; }
 
-// Kalman update (standard.py:93-102, LU) of one block on an observation held in registers: dalton_observe without the
-// forecast log-density, which DALTON's non-Gaussian form does not use.  A padded row (zero weight, unit variance, zero
-// datum) is an exact no-op: its forecast row / column is a unit vector that the pivot search never picks for another column.
-template <int P, int MO>
-__device__ __forceinline__ void ng_observe(const double (&D)[MO][P], const double (&y)[MO], const double (&Om)[MO][MO],
-                                           double (&m)[P], double (&S)[P][P]) {
-    double Wf[MO][MO], DS[MO][P], X[MO][P], z[MO];
-#pragma unroll
-    for (int j = 0; j < MO; ++j) {
-        z[j] = y[j] - dot<P>(D[j], m);
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-            double t = D[j][0] * S[0][c];
-#pragma unroll
-            for (int k = 1; k < P; ++k) t = fma(D[j][k], S[k][c], t);
-            DS[j][c] = t;                                                   // D Sigma
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < MO; ++j)
-#pragma unroll
-        for (int l = 0; l < MO; ++l) Wf[j][l] = dot<P>(DS[j], D[l]) + Om[j][l];
-#pragma unroll
-    for (int j = 0; j < MO; ++j)
-#pragma unroll
-        for (int r = 0; r < P; ++r) X[j][r] = dot<P>(S[r], D[j]);           // (Sigma D^T)^T
-    lu_solve<MO, P>(Wf, X);                                                 // K^T
-#pragma unroll
-    for (int r = 0; r < P; ++r) {
-        double t = X[0][r] * z[0];
-#pragma unroll
-        for (int j = 1; j < MO; ++j) t = fma(X[j][r], z[j], t);
-        double dS[P];
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-            double u = X[0][r] * DS[0][c];
-#pragma unroll
-            for (int j = 1; j < MO; ++j) u = fma(X[j][r], DS[j][c], u);
-            dS[c] = u;
-        }
-        m[r] = m[r] + t;
-#pragma unroll
-        for (int c = 0; c < P; ++c) S[r][c] = S[r][c] - dS[c];
-    }
-}
-
 // (weight, datum, variance) of the pseudo-observation of blocks BLK .. D-1 at the predicted means mup (dalton.py:614-622):
 // one evaluation of the log-likelihood per block with that block's active components seeded, the other blocks constants,
 // which yields exactly the diagonal Hessian block the reference keeps.
@@ -157,7 +111,8 @@ __device__ __forceinline__ void ng_observe_block(int blk, const double (&Dm)[OBS
                                                  const double (&Om)[OBS::D][MO][MO], double (&m)[P], double (&S)[P][P]) {
     if constexpr (BLK < OBS::D) {
         if constexpr (OBS::NACT[BLK] > 0) {
-            if (blk == BLK) ng_observe<P, MO>(Dm[BLK], yh[BLK], Om[BLK], m, S);
+            // (dalton_observe without the forecast log-density, which DALTON's non-Gaussian form does not use)
+            if (blk == BLK) observe_update<P, MO>(Dm[BLK], yh[BLK], Om[BLK], m, S);
         }
         ng_observe_block<OBS, P, MO, BLK + 1>(blk, Dm, yh, Om, m, S);
     }
@@ -179,42 +134,20 @@ __global__ void __launch_bounds__(64) daltonng_fwd_kernel(SolveArgs a, NgObs o, 
     const size_t B = (size_t)a.B;
     double* const mean = joint ? a.mean : zm;
     double* const var = joint ? a.var : zv;
-    double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA];
-#pragma unroll
-    for (int blk = 0; blk < D; ++blk) {
-        load_block_consts<P>(a, blk, b, Q[blk], R[blk]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) W[blk][j] = ld(a.W, (size_t)blk * P + j, a.W_b, a.B, b);
-    }
-#pragma unroll
-    for (int k = 0; k < RHS::NTHETA; ++k) th[k] = a.theta ? ld(a.theta, k, a.theta_b, a.B, b) : 0.0;
-
-    double mu[D][P], S[D][P][P];
-#pragma unroll
-    for (int blk = 0; blk < D; ++blk)
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const size_t em = (size_t)blk * P + i;
-            mu[blk][i] = ld(a.x0, em, a.x0_b, a.B, b);
-            mean[em * B + b] = mu[blk][i];                                  // time 0: (ode_init, 0) (dalton.py:689-693)
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                S[blk][i][j] = 0.0;
-                var[(em * P + j) * B + b] = 0.0;
-            }
-        }
+    double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA], mu[D][P], S[D][P][P];
+    lane_load_model<RHS, P>(a, b, Q, R, W, th);
+    lane_load_init<D, P>(a, b, mu, S);
+    store_moments_all<D, P>(mean, var, B, 0, b, mu, S);                     // time 0: (ode_init, 0) (dalton.py:689-693)
     // an observation at t_min does not enter the filter (dalton.py:671); it enters logy_x
     int i = (joint && o.n_obs > 0 && o.obs_ind[0] == 0) ? 1 : 0;
 
     const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
-    const size_t mstride = (size_t)D * P * B, vstride = (size_t)D * P * P * B;
     for (int n = 0; n < a.N; ++n) {
         double mup[D][P], Sp[D][P][P];
 #pragma unroll
         for (int blk = 0; blk < D; ++blk) predict_block<P>(Q[blk], R[blk], mu[blk], S[blk], mup[blk], Sp[blk]);
-        const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;
         double wgt[D][P], am[D], V[D];
-        interrogate_traj<RHS, P, ITG>(W, th, t, mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
+        interrogate_traj<RHS, P, ITG>(W, th, step_time(a, n), mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
         const bool obs_here = joint && i < o.n_obs && o.obs_ind[i] == n + 1;
         double Dm[D][MO][P], yh[D][MO], Om[D][MO][MO];
         if (obs_here) {
@@ -225,6 +158,7 @@ __global__ void __launch_bounds__(64) daltonng_fwd_kernel(SolveArgs a, NgObs o, 
                 for (int k = 0; k < OBS::NY; ++k) y[blk][k] = o.y[((size_t)i * D + blk) * OBS::NY + k];
             ng_pseudo_obs<OBS, P, MO, 0>(y, mup, (double)i, th, Dm, yh, Om);
         }
+        const size_t mstride = (size_t)D * P * B, vstride = (size_t)D * P * P * B;
         double* mo = mean + (size_t)(n + 1) * mstride + b;
         double* vo = var + (size_t)(n + 1) * vstride + b;
 #pragma unroll
@@ -235,7 +169,7 @@ __global__ void __launch_bounds__(64) daltonng_fwd_kernel(SolveArgs a, NgObs o, 
             update_block_m1<P>(Wm, am[blk], V[blk], mup[blk], Sp[blk], mu[blk], S[blk]);
             if (obs_here) ng_observe_block<OBS, P, MO, 0>(blk, Dm, yh, Om, mu[blk], S[blk]);
 #pragma unroll
-            for (int r = 0; r < P; ++r) {
+            for (int r = 0; r < P; ++r) {                                   // store_moments, written out
                 const size_t em = (size_t)blk * P + r;
                 mo[em * B] = mu[blk][r];
 #pragma unroll
@@ -243,20 +177,6 @@ __global__ void __launch_bounds__(64) daltonng_fwd_kernel(SolveArgs a, NgObs o, 
             }
         }
         if (obs_here) ++i;
-    }
-}
-
-// filtered moments of (time n, block blk, trajectory b) from batch-minor buffers
-template <int P>
-__device__ __forceinline__ void ng_load(const double* m, const double* v, int D, size_t B, int n, int blk, int b, double (&mf)[P],
-                                        double (&Sf)[P][P]) {
-    const double* mi = m + ((size_t)n * D + blk) * P * B + b;
-    const double* vi = v + ((size_t)n * D + blk) * P * P * B + b;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        mf[i] = mi[(size_t)i * B];
-#pragma unroll
-        for (int j = 0; j < P; ++j) Sf[i][j] = vi[((size_t)i * P + j) * B];
     }
 }
 
@@ -303,11 +223,11 @@ __global__ void __launch_bounds__(64) daltonng_gain_kernel(SolveArgs a, NgWs w) 
     const int b = (int)(l % B), blk = (int)((l / B) % a.D), r = (int)(l / (B * a.D));
     double Q[P][P], R[P][P];
     load_block_consts<P>(a, blk, b, Q, R);
-    double* rec = w.rec + ((size_t)r * a.D + blk) * E * B + b;
+    double* rec = bm_item(w.rec, E, B, a.D, r, blk, b);
 #pragma unroll
     for (int z = 0; z < 2; ++z) {
         double mf[P], Sf[P][P], mp[P], Sp[P][P], T[P][P], G[P][P], GT[P][P], A[P][P];
-        ng_load<P>(z ? w.zm : w.jm, z ? w.zv : w.jv, a.D, B, r + 1, blk, b, mf, Sf);
+        load_moments_bm<P>(z ? w.zm : w.jm, z ? w.zv : w.jv, B, a.D, r + 1, blk, b, mf, Sf);
         predict_block<P>(Q, R, mf, Sf, mp, Sp);                             // pred[n+1] re-evaluated from filt[n]
         smooth_gain<P>(Q, Sf, Sp, T, G);
         mm_nt<P, P, P>(G, T, GT);
@@ -347,8 +267,8 @@ __global__ void __launch_bounds__(64) daltonng_chain_kernel(SolveArgs a, NgWs w,
     const int blk = l / a.B, b = l - blk * a.B;
     const size_t B = (size_t)a.B;
     double ms[P], Sf[P][P], mz[P], Sz[P][P], A[P][P];
-    ng_load<P>(w.jm, w.jv, a.D, B, a.N, blk, b, ms, Sf);
-    ng_load<P>(w.zm, w.zv, a.D, B, a.N, blk, b, mz, Sz);
+    load_moments_bm<P>(w.jm, w.jv, B, a.D, a.N, blk, b, ms, Sf);
+    load_moments_bm<P>(w.zm, w.zv, B, a.D, a.N, blk, b, mz, Sz);
     double acc_y = ng_masked<P, false>(Sf, A);                              // logpdf(mu_f,N; mu_f,N, Sigma_f,N)
     double acc_z = ng_masked<P, true>(Sz, A);                               // logpdf(mu_s,N; mu^Z_f,N, Sigma^Z_f,N)
     {
@@ -360,15 +280,15 @@ __global__ void __launch_bounds__(64) daltonng_chain_kernel(SolveArgs a, NgWs w,
     }
     int i = o.n_obs - 1;
     auto keep = [&](int slot, const double (&m)[P]) {
-        double* so = w.sm + ((size_t)slot * a.D + blk) * P * B + b;
+        double* so = bm_item(w.sm, P, B, a.D, slot, blk, b);
 #pragma unroll
         for (int e = 0; e < P; ++e) so[(size_t)e * B] = m[e];
     };
     if (i >= 0 && o.obs_ind[i] == a.N) { keep(i, ms); --i; }
     for (int n = a.N - 1; n >= 1; --n) {
-        const double* rec = w.rec + ((size_t)(n - 1) * a.D + blk) * E * B + b;
-        const double* mfp = w.jm + ((size_t)n * a.D + blk) * P * B + b;
-        const double* mzp = w.zm + ((size_t)n * a.D + blk) * P * B + b;
+        const double* rec = bm_item(w.rec, E, B, a.D, n - 1, blk, b);
+        const double* mfp = bm_item(w.jm, P, B, a.D, n, blk, b);
+        const double* mzp = bm_item(w.zm, P, B, a.D, n, blk, b);
         double G[P][P], GZ[P][P], d[P], dz[P], gm[P], gz[P], rr[P], Ar[P];
 #pragma unroll
         for (int r = 0; r < P; ++r) {

@@ -47,13 +47,7 @@ __device__ __forceinline__ void dynamic_add_noise(const double (&Pp)[P][P], doub
 template <int P>
 __device__ __forceinline__ double dynamic_quadform(const double (&w)[P], const double (&M)[P][P]) {
     double wM[P];
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-        double t = w[0] * M[0][j];
-#pragma unroll
-        for (int i = 1; i < P; ++i) t = fma(w[i], M[i][j], t);
-        wM[j] = t;
-    }
+    row_mat<P>(w, M, wM);
     return dot<P>(wM, w);
 }
 
@@ -67,46 +61,19 @@ __global__ void __launch_bounds__(64) dynamic_fwd_kernel(SolveArgs a, double sca
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     const size_t B = (size_t)a.B;
-    double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA];
-#pragma unroll
-    for (int blk = 0; blk < D; ++blk) {
-        load_block_consts<P>(a, blk, b, Q[blk], R[blk]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) W[blk][j] = ld(a.W, (size_t)blk * P + j, a.W_b, a.B, b);
-    }
-#pragma unroll
-    for (int k = 0; k < RHS::NTHETA; ++k) th[k] = a.theta ? ld(a.theta, k, a.theta_b, a.B, b) : 0.0;
-    double mu[D][P], S[D][P][P], q[D];
+    double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA], mu[D][P], S[D][P][P], q[D] = {};
     LogProd l[D];
-    // time index 0: (ode_init, 0) (solve.py:114-121)
-#pragma unroll
-    for (int blk = 0; blk < D; ++blk) {
-        q[blk] = 0.0;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const size_t em = (size_t)blk * P + i;
-            mu[blk][i] = ld(a.x0, em, a.x0_b, a.B, b);
-            a.mean[em * B + b] = mu[blk][i];
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                S[blk][i][j] = 0.0;
-                a.var[(em * P + j) * B + b] = 0.0;
-            }
-        }
-    }
+    lane_load_model<RHS, P>(a, b, Q, R, W, th);
+    lane_load_init<D, P>(a, b, mu, S);
+    store_moments_all<D, P>(a.mean, a.var, B, 0, b, mu, S);                                   // time index 0
     const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
-    const size_t mstride = (size_t)D * P * B, vstride = (size_t)D * P * P * B;
     for (int n = 0; n < a.N; ++n) {
         double mup[D][P], Sp[D][P][P];
 #pragma unroll
         for (int blk = 0; blk < D; ++blk) dynamic_propagate<P>(Q[blk], mu[blk], S[blk], mup[blk], Sp[blk]);
-        const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;     // solve.py:74
         double wgt[D][P], am[D], V[D];
         // (Sp holds P here: of the three served interrogations only rodeo reads it, for a var_meas that is formed below instead)
-        interrogate_traj<RHS, P, ITG>(W, th, t, mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
-        double* mo = a.mean + (size_t)(n + 1) * mstride + b;
-        double* vo = a.var + (size_t)(n + 1) * vstride + b;
-        double* so = scale + (size_t)n * D * B + b;
+        interrogate_traj<RHS, P, ITG>(W, th, step_time(a, n), mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
 #pragma unroll
         for (int blk = 0; blk < D; ++blk) {
             double Wm[P], z, s, rs;
@@ -121,14 +88,8 @@ __global__ void __launch_bounds__(64) dynamic_fwd_kernel(SolveArgs a, double sca
             evidence_update_z<P>(Wm, am[blk], Vb, mup[blk], Sp[blk], mu[blk], S[blk], z, s, rs);
             q[blk] = fma(z * z, rs, q[blk]);
             l[blk].mul(s);
-            so[(size_t)blk * B] = c;
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                const size_t em = (size_t)blk * P + i;
-                mo[em * B] = mu[blk][i];
-#pragma unroll
-                for (int j = 0; j < P; ++j) vo[(em * P + j) * B] = S[blk][i][j];
-            }
+            *bm_item(scale, 1, B, D, n, blk, b) = c;
+            store_moments<P>(a.mean, a.var, B, D, n + 1, blk, b, mu[blk], S[blk]);
         }
     }
     double tot = 0.0;

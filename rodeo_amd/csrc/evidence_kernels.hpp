@@ -44,33 +44,13 @@ struct LogProd {
 };
 
 // z forecast and update of one block (standard.py:93-102 for n_bmeas = 1, x_meas = 0) that hands back the innovation and
-// its forecast variance s with the reciprocal rs = 1 / s (one division for the gain and the caller's z^2 / s): dalton_update_z
-// without the log-density and its threshold
+// its forecast variance s with the reciprocal rs = 1 / s (one division for the gain and the caller's z^2 / s): update_z with
+// that reciprocal multiplied onto the gain
 template <int P>
 __device__ __forceinline__ void evidence_update_z(const double (&Wm)[P], double am, double V, const double (&mup)[P],
                                                   const double (&Sp)[P][P], double (&mu)[P], double (&S)[P][P],
                                                   double& innov, double& s, double& rs) {
-    const double yhat = dot<P>(Wm, mup) + am;
-    double WS[P], SW[P];
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-        double t = Wm[0] * Sp[0][j];
-#pragma unroll
-        for (int i = 1; i < P; ++i) t = fma(Wm[i], Sp[i][j], t);
-        WS[j] = t;
-    }
-    s = dot<P>(WS, Wm) + V;                                                 // var_fore
-    rs = 1.0 / s;
-    innov = 0.0 - yhat;
-#pragma unroll
-    for (int i = 0; i < P; ++i) SW[i] = dot<P>(Sp[i], Wm);
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        const double K = SW[i] * rs;
-        mu[i] = fma(K, innov, mup[i]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) S[i][j] = fma(-K, WS[j], Sp[i][j]);
-    }
+    rs = update_z<P, GAIN_RCP>(Wm, am, V, mup, Sp, mu, S, innov, s);
 }
 
 // standard form, one lane per trajectory (dalton_fwd_kernel's layout without the second filter)
@@ -82,19 +62,11 @@ __global__ void __launch_bounds__(64) evidence_kernel(SolveArgs a, double* __res
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     const size_t B = (size_t)a.B;
-    double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA];
-#pragma unroll
-    for (int blk = 0; blk < D; ++blk) {
-        load_block_consts<P>(a, blk, b, Q[blk], R[blk]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) W[blk][j] = ld(a.W, (size_t)blk * P + j, a.W_b, a.B, b);
-    }
-#pragma unroll
-    for (int k = 0; k < RHS::NTHETA; ++k) th[k] = a.theta ? ld(a.theta, k, a.theta_b, a.B, b) : 0.0;
-    double mu[D][P], S[D][P][P], q[D];
+    double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA], mu[D][P], S[D][P][P], q[D];
     LogProd l[D];
+    lane_load_model<RHS, P>(a, b, Q, R, W, th);
 #pragma unroll
-    for (int blk = 0; blk < D; ++blk) {
+    for (int blk = 0; blk < D; ++blk) {                                     // lane_load_init, written out
         q[blk] = 0.0;
 #pragma unroll
         for (int i = 0; i < P; ++i) {
@@ -108,9 +80,8 @@ __global__ void __launch_bounds__(64) evidence_kernel(SolveArgs a, double* __res
         double mup[D][P], Sp[D][P][P];
 #pragma unroll
         for (int blk = 0; blk < D; ++blk) predict_block<P>(Q[blk], R[blk], mu[blk], S[blk], mup[blk], Sp[blk]);
-        const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;
         double wgt[D][P], am[D], V[D];
-        interrogate_traj<RHS, P, ITG>(W, th, t, mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
+        interrogate_traj<RHS, P, ITG>(W, th, step_time(a, n), mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
 #pragma unroll
         for (int blk = 0; blk < D; ++blk) {
             double Wm[P], z, s, rs;
@@ -141,7 +112,7 @@ __device__ __forceinline__ void evidence_sqrt_forecast(const double (&W)[P], dou
     innov = 0.0 - (dot<P>(W, mup) + a);
     double s2 = 0.0;
 #pragma unroll
-    for (int j = 0; j < P; ++j) {
+    for (int j = 0; j < P; ++j) {                                     // row_mat, written out
         double t = W[0] * Lp[0][j];
 #pragma unroll
         for (int i = 1; i < P; ++i) t = fma(W[i], Lp[i][j], t);
@@ -191,7 +162,7 @@ __global__ void __launch_bounds__(64) evidence_sqrt_kernel(SolveArgs a, double* 
             load_block_consts<P>(a, blk, b, Q, LR);
             sqrt_predict<P>(Q, LR, mu, L, mup, Lp);
         }
-        const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;  // solve.py:74
+        const double t = step_time(a, n);
         double X[D][P];                                   // the whole trajectory's points, in every one of its lanes
 #pragma unroll
         for (int bb = 0; bb < D; ++bb)
@@ -219,7 +190,7 @@ __global__ void __launch_bounds__(64) evidence_sqrt_kernel(SolveArgs a, double* 
             if constexpr (ITG == RK_INTERROGATE_RODEO) {                                // interrogate.py:110-113 on the factor
                 double WL[P];
 #pragma unroll
-                for (int j = 0; j < P; ++j) {
+                for (int j = 0; j < P; ++j) {                         // row_mat, written out
                     double s = W[0] * Lp[0][j];
 #pragma unroll
                     for (int i = 1; i < P; ++i) s = fma(W[i], Lp[i][j], s);

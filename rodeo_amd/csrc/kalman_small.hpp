@@ -24,31 +24,97 @@ __device__ __forceinline__ void predict_block(const double (&Q)[P][P], const dou
 
 // standard.py:93-102 for n_bmeas = 1, x_meas = 0 (solve.py:51):
 //   yhat = W mu- + a ; S = (W Sigma-) W^T + V ; K = Sigma- W^T / S ; mu = mu- + K (0 - yhat) ; Sigma = Sigma- - K (W Sigma-)
-template <int P>
-__device__ __forceinline__ void update_block_m1(const double (&W)[P], double a, double V,
-                                                const double (&mup)[P], const double (&Sp)[P][P],
-                                                double (&mu)[P], double (&S)[P][P]) {
+// The one body of the lane filters' scalar z updates; it hands back the innovation 0 - yhat and its forecast variance s.
+// GAIN is how K = Sigma- W^T / s is divided, the only thing in which the filters differ: fast_rcp(s) multiplied (the solver's
+// forward filter), one IEEE division per element (DALTON, whose log-density shares s), or the reciprocal 1.0 / s multiplied
+// (solve_evidence and the dynamic solver, whose z^2 / s uses the same reciprocal).  Returns the reciprocal it multiplied with
+// (0 under GAIN_DIVIDE, which has none).
+enum GainRule { GAIN_FAST_RCP, GAIN_DIVIDE, GAIN_RCP };
+template <int P, GainRule GAIN>
+__device__ __forceinline__ double update_z(const double (&W)[P], double a, double V, const double (&mup)[P],
+                                         const double (&Sp)[P][P], double (&mu)[P], double (&S)[P][P], double& innov,
+                                         double& s) {
     const double yhat = dot<P>(W, mup) + a;
     double WS[P], SW[P];
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-        double s = W[0] * Sp[0][j];
-#pragma unroll
-        for (int i = 1; i < P; ++i) s = fma(W[i], Sp[i][j], s);
-        WS[j] = s;
-    }
-    const double Smm = dot<P>(WS, W) + V;
+    row_mat<P>(W, Sp, WS);
+    s = dot<P>(WS, W) + V;                                                  // var_fore
+    innov = 0.0 - yhat;
 #pragma unroll
     for (int i = 0; i < P; ++i) SW[i] = dot<P>(Sp[i], W);
-    const double rS = fast_rcp(Smm);
-    const double innov = 0.0 - yhat;
+    double rs = 0.0;
+    if constexpr (GAIN == GAIN_FAST_RCP) rs = fast_rcp(s);
+    if constexpr (GAIN == GAIN_RCP) rs = 1.0 / s;
 #pragma unroll
     for (int i = 0; i < P; ++i) {
-        const double K = SW[i] * rS;
+        const double K = GAIN == GAIN_DIVIDE ? SW[i] / s : SW[i] * rs;
         mu[i] = fma(K, innov, mup[i]);
 #pragma unroll
         for (int j = 0; j < P; ++j) S[i][j] = fma(-K, WS[j], Sp[i][j]);
     }
+    return rs;
+}
+
+template <int P>
+__device__ __forceinline__ void update_block_m1(const double (&W)[P], double a, double V,
+                                                const double (&mup)[P], const double (&Sp)[P][P],
+                                                double (&mu)[P], double (&S)[P][P]) {
+    double innov, s;
+    update_z<P, GAIN_FAST_RCP>(W, a, V, mup, Sp, mu, S, innov, s);
+}
+
+// standard.py:93-102 (LU) of one block on a vector observation y = D x + N(0, Om) held in registers, in two halves so that a
+// caller can put the forecast's log-density between them (dalton_observe): observe_forecast gives the innovation z, D Sigma
+// and the forecast variance Wf; observe_apply solves for the gain (Wf is destroyed) and updates (m, S).  A padded row (zero
+// weight, unit variance, zero datum) is an exact no-op: its forecast row / column is a unit vector that the pivot search never
+// picks for another column.
+template <int P, int MO>
+__device__ __forceinline__ void observe_forecast(const double (&D)[MO][P], const double (&y)[MO], const double (&Om)[MO][MO],
+                                                 const double (&m)[P], const double (&S)[P][P], double (&z)[MO],
+                                                 double (&DS)[MO][P], double (&Wf)[MO][MO]) {
+#pragma unroll
+    for (int j = 0; j < MO; ++j) {
+        z[j] = y[j] - dot<P>(D[j], m);
+        row_mat<P>(D[j], S, DS[j]);                                         // D Sigma
+    }
+#pragma unroll
+    for (int j = 0; j < MO; ++j)
+#pragma unroll
+        for (int l = 0; l < MO; ++l) Wf[j][l] = dot<P>(DS[j], D[l]) + Om[j][l];    // var_fore
+}
+template <int P, int MO>
+__device__ __forceinline__ void observe_apply(const double (&D)[MO][P], const double (&z)[MO], const double (&DS)[MO][P],
+                                              double (&Wf)[MO][MO], double (&m)[P], double (&S)[P][P]) {
+    double X[MO][P];
+#pragma unroll
+    for (int j = 0; j < MO; ++j)
+#pragma unroll
+        for (int r = 0; r < P; ++r) X[j][r] = dot<P>(S[r], D[j]);           // (Sigma D^T)^T
+    lu_solve<MO, P>(Wf, X);                                                 // K^T
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        double t = X[0][r] * z[0];
+#pragma unroll
+        for (int j = 1; j < MO; ++j) t = fma(X[j][r], z[j], t);
+        double dS[P];
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            double u = X[0][r] * DS[0][c];
+#pragma unroll
+            for (int j = 1; j < MO; ++j) u = fma(X[j][r], DS[j][c], u);
+            dS[c] = u;
+        }
+        m[r] = m[r] + t;
+#pragma unroll
+        for (int c = 0; c < P; ++c) S[r][c] = S[r][c] - dS[c];
+    }
+}
+// both halves: the update without a log-density
+template <int P, int MO>
+__device__ __forceinline__ void observe_update(const double (&D)[MO][P], const double (&y)[MO], const double (&Om)[MO][MO],
+                                               double (&m)[P], double (&S)[P][P]) {
+    double z[MO], DS[MO][P], Wf[MO][MO];
+    observe_forecast<P, MO>(D, y, Om, m, S, z, DS, Wf);
+    observe_apply<P, MO>(D, z, DS, Wf, m, S);
 }
 
 // standard.py:175-176:  T = Sigma_f Q^T ;  G = solve(Sigma-, T^T)^T  (LU with partial pivoting, utils.py:119)

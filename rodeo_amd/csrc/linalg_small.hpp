@@ -81,6 +81,18 @@ __device__ __forceinline__ void mv(const double (&A)[R][K], const double (&x)[K]
     }
 }
 
+// out = w S of a row vector (1xP) and S (PxP): one row of mm, k ascending, a product, then fused multiply-adds
+template <int P>
+__device__ __forceinline__ void row_mat(const double (&w)[P], const double (&S)[P][P], double (&out)[P]) {
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        double s = w[0] * S[0][j];
+#pragma unroll
+        for (int k = 1; k < P; ++k) s = fma(w[k], S[k][j], s);
+        out[j] = s;
+    }
+}
+
 template <int K>
 __device__ __forceinline__ double dot(const double (&a)[K], const double (&b)[K]) {
     double s = a[0] * b[0];

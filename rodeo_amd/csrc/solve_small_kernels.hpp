@@ -6,6 +6,7 @@
 #include "kalman_small.hpp"
 #include "philox.hpp"
 #include "solve_args.hpp"
+#include "lane_filter.hpp"
 
 namespace rk {
 
@@ -54,13 +55,7 @@ __device__ __forceinline__ void interrogate_traj(const double (&W)[RHS::D][P], c
                 V[blk] = 0.0;                                     // interrogate.py:60
             } else {
                 double WS[P];                                     // interrogate.py:110-113 / :26-29
-#pragma unroll
-                for (int j = 0; j < P; ++j) {
-                    double s = W[blk][0] * Sp[blk][0][j];
-#pragma unroll
-                    for (int i = 1; i < P; ++i) s = fma(W[blk][i], Sp[blk][i][j], s);
-                    WS[j] = s;
-                }
+                row_mat<P>(W[blk], Sp[blk], WS);
                 V[blk] = dot<P>(WS, W[blk]);
             }
         }
@@ -76,16 +71,9 @@ __global__ void __launch_bounds__(64) fwd_kernel(SolveArgs a) {
     const size_t B = (size_t)a.B;
 
     double Q[D][P][P], R[D][P][P], W[D][P], th[RHS::NTHETA];
-#pragma unroll
-    for (int blk = 0; blk < D; ++blk) {
-        load_block_consts<P>(a, blk, b, Q[blk], R[blk]);
-#pragma unroll
-        for (int j = 0; j < P; ++j) W[blk][j] = ld(a.W, (size_t)blk * P + j, a.W_b, a.B, b);
-    }
-#pragma unroll
-    for (int k = 0; k < RHS::NTHETA; ++k) th[k] = a.theta ? ld(a.theta, k, a.theta_b, a.B, b) : 0.0;
+    lane_load_model<RHS, P>(a, b, Q, R, W, th);
 
-    double mu[D][P], S[D][P][P];
+    double mu[D][P], S[D][P][P];                         // lane_load_init, written out
 #pragma unroll
     for (int blk = 0; blk < D; ++blk)
 #pragma unroll
@@ -95,7 +83,7 @@ __global__ void __launch_bounds__(64) fwd_kernel(SolveArgs a) {
             for (int j = 0; j < P; ++j) S[blk][i][j] = 0.0;
         }
 
-    // time index 0: (ode_init, 0) for filt and pred (solve.py:114-121)
+    // time index 0: (ode_init, 0) for filt and pred (solve.py:114-121); store_moments_all, written out
 #pragma unroll
     for (int blk = 0; blk < D; ++blk)
 #pragma unroll
@@ -111,45 +99,23 @@ __global__ void __launch_bounds__(64) fwd_kernel(SolveArgs a) {
         }
 
     const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
-    const size_t mstride = (size_t)D * P * B, vstride = (size_t)D * P * P * B;
     for (int n = 0; n < a.N; ++n) {
         double mup[D][P], Sp[D][P][P];
 #pragma unroll
         for (int blk = 0; blk < D; ++blk) predict_block<P>(Q[blk], R[blk], mu[blk], S[blk], mup[blk], Sp[blk]);
 
-        const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;     // solve.py:74
         double wgt[D][P], am[D], V[D];
-        interrogate_traj<RHS, P, ITG>(W, th, t, mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
+        interrogate_traj<RHS, P, ITG>(W, th, step_time(a, n), mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
 
-        double* mo = a.mean + (size_t)(n + 1) * mstride + b;
-        double* vo = a.var + (size_t)(n + 1) * vstride + b;
 #pragma unroll
         for (int blk = 0; blk < D; ++blk) {
             double Wm[P];
 #pragma unroll
             for (int j = 0; j < P; ++j) Wm[j] = W[blk][j] + wgt[blk][j];                      // solve.py:79
             update_block_m1<P>(Wm, am[blk], V[blk], mup[blk], Sp[blk], mu[blk], S[blk]);
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                const size_t em = (size_t)blk * P + i;
-                mo[em * B] = mu[blk][i];
-#pragma unroll
-                for (int j = 0; j < P; ++j) vo[(em * P + j) * B] = S[blk][i][j];
-            }
+            store_moments<P>(a.mean, a.var, B, D, n + 1, blk, b, mu[blk], S[blk]);
         }
-        if (STORE_PRED) {
-            double* mpo = a.mean_pred + (size_t)(n + 1) * mstride + b;
-            double* vpo = a.var_pred + (size_t)(n + 1) * vstride + b;
-#pragma unroll
-            for (int blk = 0; blk < D; ++blk)
-#pragma unroll
-                for (int i = 0; i < P; ++i) {
-                    const size_t em = (size_t)blk * P + i;
-                    mpo[em * B] = mup[blk][i];
-#pragma unroll
-                    for (int j = 0; j < P; ++j) vpo[(em * P + j) * B] = Sp[blk][i][j];
-                }
-        }
+        if (STORE_PRED) store_moments_all<D, P>(a.mean_pred, a.var_pred, B, n + 1, b, mup, Sp);
     }
 }
 
@@ -188,14 +154,11 @@ __global__ void __launch_bounds__(64) interrogate_kernel(SolveArgs a, double t, 
                 double z[P], WL[P];
                 normals<P>(a.seed, traj, (uint32_t)step, (uint32_t)blk, PURPOSE_INTERROGATE, z);
                 double shift = 0.0;
+                row_mat<P>(W[blk], Sp[blk], WL);
 #pragma unroll
                 for (int j = 0; j < P; ++j) {
-                    double sj = W[blk][0] * Sp[blk][0][j];
-#pragma unroll
-                    for (int i = 1; i < P; ++i) sj = fma(W[blk][i], Sp[blk][i][j], sj);
-                    WL[j] = sj;
-                    shift = fma(sj, Sp[blk][j][j] < 0.0 ? -z[j] : z[j], shift);
-                    var_meas[((size_t)blk * P + j) * B + b] = sj;
+                    shift = fma(WL[j], Sp[blk][j][j] < 0.0 ? -z[j] : z[j], shift);
+                    var_meas[((size_t)blk * P + j) * B + b] = WL[j];
                     wgt_meas[((size_t)blk * P + j) * B + b] = 0.0;
                 }
 #pragma unroll

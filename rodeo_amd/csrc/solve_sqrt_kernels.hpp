@@ -6,6 +6,7 @@
 #include "kalman_small.hpp"
 #include "philox.hpp"
 #include "solve_args.hpp"
+#include "lane_filter.hpp"
 #include "sqrt_small.hpp"
 
 namespace rk {
@@ -66,10 +67,10 @@ __global__ void __launch_bounds__(64) fwd_sqrt_kernel(SolveArgs a) {
             load_block_consts<P>(a, blk, b, Q, LR);
             sqrt_predict<P>(Q, LR, mu, L, mup, Lp);
         }
-        const double t = a.t_min + (a.t_max - a.t_min) * (double)(n + 1) / (double)a.N;  // solve.py:74
+        const double t = step_time(a, n);
         // ---- interrogation (interrogate.py) with the factor standing where the reference puts it ----
         double am, vm[KV], wgt[P], WL[P];
-        if constexpr (ITG != RK_INTERROGATE_KRAMER) {
+        if constexpr (ITG != RK_INTERROGATE_KRAMER) {                 // row_mat, written out
 #pragma unroll
             for (int j = 0; j < P; ++j) {
                 double s = W[0] * Lp[0][j];
