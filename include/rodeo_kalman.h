@@ -342,6 +342,28 @@ int rk_solve_evidence(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* i
 int rk_solve_dynamic(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
                      double scale_min, double* scale, double* logdens);
 
+/* solve_sim_draws (an addition): n_draws sample paths per trajectory from one forward filter.  Runs the forward pass of
+ * rk_solve_filter (cfg must carry RK_FLAG_BATCH_MINOR; out->mean_state / var_state hold the filtered moments afterwards), then
+ * one backward kernel, one lane per (chunk of draws, block, trajectory), which does the work that no draw changes -- the
+ * record's load, the prediction, the smoothing gain, Sigma_f - G T^T and its factor -- once per step for its chunk.  A chunk is
+ * 1, 2 or rk_sim_draws_chunk() = 4 draws: the smallest whose waves fit the device one per SIMD, else the largest.
+ * THE SEED LAW: draw s is the path rk_solve_sim writes under the seed cfg->seed + s (mod 2^64) -- Philox is keyed with
+ * (seed + s, traj_offset + trajectory, step, block, smoothing purpose) -- up to rounding.
+ * keep: NULL for every node (K = n_steps + 1), else a device array of n_keep = K grid indices in 0..n_steps, strictly
+ * increasing; only those nodes are written (node 0 is ode_init).  An array that breaks the rule loses rows but never writes
+ * outside x_draws.  x_draws (device, overwritten, each element has one writer): (n_draws, K, n_block, n_bstate, n_traj)
+ * batch-minor, element i of (draw s, kept row k, block b, trajectory t) at [(((s * K + k) * n_block + b) * n_bstate + i) *
+ * n_traj + t].  No workspace; out->x_state is not used.
+ * Served: kalman_type standard, n_bmeas = 1, n_bstate 2..6, any n_block, interrogate rodeo / schober / kramer (not
+ * chkrebtii: its forward pass depends on the key, so the draws cannot share one filter), any built-in right-hand side or a
+ * user one with n_bmeas = 1; n_draws 1..65535.  What is not served is refused on cfg alone -- RK_ERR_INVALID (a
+ * non-positive size, RK_FLAG_BATCH_MINOR missing) or RK_ERR_UNSUPPORTED -- before the handle or any pointer is looked at;
+ * then n_draws and n_keep (RK_ERR_INVALID).  RK_SIM_DRAWS_CHUNK = 1, 2 or 4 (read per call) fixes the chunk, for tests and
+ * measurements; the draws do not depend on it.                                                                            */
+int rk_solve_sim_draws(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t n_draws,
+                       const int32_t* keep, int32_t n_keep, double* x_draws);
+int rk_sim_draws_chunk(void);
+
 /* dalton_at: rk_dalton_loglik for observations whose times need not be grid nodes (an addition: the reference places every
  * observation by searchsorted on the grid).  obs / obs_weight / obs_var as for rk_dalton_loglik, in time order.  The device
  * array `table` (n_obs, 4) holds per observation: node, off-grid flag, pre slot, post slot or -1.  With the flag clear the

@@ -135,6 +135,8 @@ SIGNATURES = {
     "rk_daltonng_solve": (C.c_int, [_H, _P, _P, _P, _I, _I, _P, _P, _I]),
     "rk_solve_evidence": (C.c_int, [_H, _P, _P, _P, _P, _P]),
     "rk_solve_dynamic": (C.c_int, [_H, _P, _P, _P, _I, _D, _P, _P]),
+    "rk_solve_sim_draws": (C.c_int, [_H, _P, _P, _P, _I, _P, _I, _P]),
+    "rk_sim_draws_chunk": (C.c_int, []),
     "rk_magi_logdens": (C.c_int, [_H, C.POINTER(MagiCfg), C.POINTER(MagiIn), _P]),
     "rk_fd_stencil": (C.c_int, [_H, _I, _I, _P, _P, _P]),
     "rk_fd_grad_hess": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P]),

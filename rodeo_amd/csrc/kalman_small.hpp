@@ -195,4 +195,42 @@ __device__ __forceinline__ void mvn_draw(const double (&mean)[P], const double (
     }
 }
 
+// smooth_sim_block and mvn_draw in the parts that depend on the draw and the parts that do not, for a caller that takes
+// several draws from one (G, T, filt) (sim_draws.hip): per step once smooth_sim_var and psd_factor, per draw smooth_sim_mean
+// and mvn_apply.  The products, their fma chains and their order are those of the two functions above.
+// var_sim = Sigma_f - G T^T
+template <int P>
+__device__ __forceinline__ void smooth_sim_var(const double (&G)[P][P], const double (&T)[P][P], const double (&Sf)[P][P],
+                                               double (&Ssim)[P][P]) {
+    double GT[P][P];
+    mm_nt<P, P, P>(G, T, GT);
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+#pragma unroll
+        for (int j = 0; j < P; ++j) Ssim[i][j] = Sf[i][j] - GT[i][j];
+}
+// mean_sim = mu_f + G (x_next - mu-)
+template <int P>
+__device__ __forceinline__ void smooth_sim_mean(const double (&G)[P][P], const double (&mf)[P], const double (&mp)[P],
+                                                const double (&xn)[P], double (&msim)[P]) {
+    double dm[P], gm[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) dm[i] = xn[i] - mp[i];
+    mv<P, P>(G, dm, gm);
+#pragma unroll
+    for (int i = 0; i < P; ++i) msim[i] = mf[i] + gm[i];
+}
+// x = mean + L z with L = psd_factor(var), lower triangular
+template <int P>
+__device__ __forceinline__ void mvn_apply(const double (&mean)[P], const double (&L)[P][P], const double (&z)[P],
+                                          double (&x)[P]) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        double s = mean[i];
+#pragma unroll
+        for (int k = 0; k <= i; ++k) s = fma(L[i][k], z[k], s);
+        x[i] = s;
+    }
+}
+
 }  // namespace rk
