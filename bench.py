@@ -6,6 +6,7 @@ probabilistic ODE solve, FitzHugh-Nagumo n_vars=2 q(n_deriv)=3, 4000 steps, `sol
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns its own N rank processes)
     python bench.py ... --dump-outputs DIR                        (also writes the last timed solve's results, dump_outputs())
+    python bench.py ... --full                                    (one rank: also times the CPU baseline, cpu_baseline())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W                  (the driver's launch: RANK / WORLD_SIZE from the env)
 
@@ -177,7 +178,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (one rank; about half a minute)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out after all")
     ap.add_argument("--require-rccl", action="store_true", help="N > 1: exit non-zero if RCCL does not come up on every rank")
     ap.add_argument("--comm", choices=["rccl", "host"], default="rccl", help="N > 1: what carries the barriers")
     ap.add_argument("--allow-host-fallback", action="store_true",
@@ -334,7 +337,7 @@ def main():
                 "note": "the filter recursion is sequential in time: one wave per SIMD at most, its time is n_steps x the "
                         "step's dependent instruction chain (7 fp64 MFMAs + 13 VALU ~ 240 cycles) whatever the batch up to "
                         "2048 trajectories (profiles/r01_c2_kernel_times_vs_batch.log)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(W, x0, theta, prior)
         print(json.dumps(out), flush=True)
 

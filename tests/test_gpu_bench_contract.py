@@ -1,11 +1,12 @@
 """bench.py end to end on the GPU: the one JSON line the driver reads (contract of the task brief: metric of BASELINE.json on
-its C2 workload, whole-job value, roofline of the dominant kernel from HIP events of the timed solves, cpu_baseline on a
-bounded sample), for the single-process launch and for the self-spawned two-rank launch on one GPU (RCCL refuses a shared
-device there: the host channel carries the barriers and the line says so)."""
+its C2 workload, whole-job value, roofline of the dominant kernel from HIP events of the timed solves; with --full also the
+cpu_baseline on a bounded sample), for the single-process launch, plain and with --full, and for the self-spawned two-rank
+launch on one GPU (RCCL refuses a shared device there: the host channel carries the barriers and the line says so)."""
 import json
 import os
 import subprocess
 import sys
+import time
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -38,8 +39,21 @@ def _common(d, n_gpus, steps, warmup, shared_gpu=False):
     assert 0.8 * d["ms_per_step"] < sum(d["kernels_ms"].values()) <= 1.02 * d["ms_per_step"]
 
 
-def test_single_process_line_with_cpu_baseline():
+def test_plain_run_is_lean():
+    """A plain run does what the headline figure needs and no more: no CPU baseline on its line, and at most 30 s of the
+    whole process, from start to exit, outside its warm-up and timed steps."""
+    t0 = time.perf_counter()
     d = _run("--steps", "5", "--warmup", "2")
+    total = time.perf_counter() - t0
+    _common(d, 1, 5, 2)
+    assert d["value"] > 2e9 and "cpu_baseline" not in d
+    outside = total - (5 + 2) * d["ms_per_step"] * 1e-3
+    print(f"plain run: {total:.2f} s in all, {outside:.2f} s outside its steps")
+    assert outside < 30.0, outside
+
+
+def test_single_process_line_with_cpu_baseline():
+    d = _run("--full", "--steps", "5", "--warmup", "2")
     _common(d, 1, 5, 2)
     assert d["value"] > 2e9                                        # (5.8e9 at the end of round 2)
     c = d["cpu_baseline"]
