@@ -1,117 +1,45 @@
 // solve_mv_dynamic / solve_sim_dynamic (an addition): host side of rk_solve_dynamic, the solver with
 // the prior variance of every step scaled, per block, by the estimate made at that step (dynamic_kernels.hpp), and the two
 // backward kernels.  One route: the lanes on batch-minor records -- dynamic_fwd_kernel, one lane per trajectory, then
-// dynamic_bwd_mv_kernel or dynamic_bwd_sim_kernel, one lane per (trajectory, block): bwd_mv_kernel / bwd_sim_kernel of
-// solve_small.hip with the prediction re-evaluated as Q Sigma_f[n] Q^T + scale[n] R.  Standard form, n_bstate 2..5 (2..4 with
-// three or more blocks).  Nothing but the outputs is written; there is no workspace.
+// dynamic_bwd_mv_kernel or dynamic_bwd_sim_kernel, one lane per (trajectory, block): the passes of bwd_mv_kernel /
+// bwd_sim_kernel (lane_backward.hpp: bwd_smooth_lane / bwd_sample_lane over bwd_walk) under the prediction policy ScaledPrior,
+// Q Sigma_f[n] Q^T + scale[n] R.  Standard form, n_bstate 2..5 (2..4 with three or more blocks).  No workspace.
 #include <cmath>
 #include "common.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
 #include "dynamic_kernels.hpp"
-#include "records.hpp"
+#include "lane_backward.hpp"
 
 namespace rk {
 
 // ---- backward passes: one lane per (block, trajectory) -----------------------------------------------------------
+// bwd_walk's prediction policy with the prior variance of step n -> n + 1 scaled by scale[n], which travels with filt[n]
+template <int P>
+struct ScaledPrior {
+    const double* __restrict__ scale;
+    using Datum = double;
+    __device__ __forceinline__ double fetch(const SolveArgs& a, const BwdLane<P>& ln, int n) const {
+        return *bm_item(scale, 1, ln.B, a.D, n, ln.blk, ln.b);
+    }
+    __device__ __forceinline__ void predict(const BwdLane<P>& ln, double c, const double (&mf)[P], const double (&Sf)[P][P],
+                                            double (&mp)[P], double (&Sp)[P][P]) const {
+        dynamic_propagate<P>(ln.Q, mf, Sf, mp, Sp);      // pred[n+1] from filt[n] and scale[n]
+        dynamic_add_noise<P>(Sp, c, ln.R, Sp);
+    }
+};
+
 template <int P>
 __global__ void __launch_bounds__(64) dynamic_bwd_mv_kernel(SolveArgs a, const double* __restrict__ scale) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= a.B * a.D) return;
-    const int blk = l / a.B, b = l - blk * a.B;
-    const size_t B = (size_t)a.B;
-    double Q[P][P], R[P][P];
-    load_block_consts<P>(a, blk, b, Q, R);
-
-    double ms[P], Ss[P][P];                    // carry: smoothed moments at n+1 (solve.py:279-282)
-    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, ms, Ss);
-    double mf[P], Sf[P][P], c = 0.0;
-    if (a.N >= 2) {
-        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
-        c = *bm_item(scale, 1, B, a.D, a.N - 1, blk, b);
-    }
-    for (int n = a.N - 1; n >= 1; --n) {
-        // software prefetch of the next (earlier) filtered state and its step's scale while this step computes
-        double mfn[P], Sfn[P][P], cn = 0.0;
-        if (n >= 2) {
-            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
-            cn = *bm_item(scale, 1, B, a.D, n - 1, blk, b);
-        }
-        double mp[P], Sp[P][P], T[P][P], G[P][P];
-        dynamic_propagate<P>(Q, mf, Sf, mp, Sp);         // pred[n+1] re-evaluated from filt[n] and scale[n]
-        dynamic_add_noise<P>(Sp, c, R, Sp);
-        smooth_gain<P>(Q, Sf, Sp, T, G);
-        smooth_mv_block<P>(G, mf, Sf, mp, Sp, ms, Ss);
-        store_moments<P>(a.mean, a.var, B, a.D, n, blk, b, ms, Ss);
-        if (n >= 2) {
-            c = cn;
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                mf[i] = mfn[i];
-#pragma unroll
-                for (int j = 0; j < P; ++j) Sf[i][j] = Sfn[i][j];
-            }
-        }
-    }
-    // time 0 keeps (ode_init, 0) written by the forward pass (solve.py:295-301)
+    BwdLane<P> ln;
+    if (ln.init(a)) bwd_smooth_lane<P>(a, ln, ScaledPrior<P>{scale});
 }
 
 template <int P>
 __global__ void __launch_bounds__(64) dynamic_bwd_sim_kernel(SolveArgs a, const double* __restrict__ scale) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= a.B * a.D) return;
-    const int blk = l / a.B, b = l - blk * a.B;
-    const size_t B = (size_t)a.B;
-    const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
-    double Q[P][P], R[P][P];
-    load_block_consts<P>(a, blk, b, Q, R);
-
-    auto store_x = [&](int n, const double (&x)[P]) {
-        double* xo = bm_item(a.x, P, B, a.D, n, blk, b);
-#pragma unroll
-        for (int i = 0; i < P; ++i) xo[(size_t)i * B] = x[i];
-    };
-
-    double mf[P], Sf[P][P], xn[P], z[P], c = 0.0;
-    // terminal draw x_N ~ N(filt[N]) (solve.py:182-186)
-    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, mf, Sf);
-    normals<P>(a.seed, traj, (uint32_t)a.N, (uint32_t)blk, PURPOSE_SMOOTH, z);
-    mvn_draw<P>(mf, Sf, z, xn);
-    store_x(a.N, xn);
-    if (a.N >= 2) {
-        load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
-        c = *bm_item(scale, 1, B, a.D, a.N - 1, blk, b);
-    }
-    for (int n = a.N - 1; n >= 1; --n) {
-        double mfn[P], Sfn[P][P], cn = 0.0;
-        if (n >= 2) {
-            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
-            cn = *bm_item(scale, 1, B, a.D, n - 1, blk, b);
-        }
-        double mp[P], Sp[P][P], T[P][P], G[P][P], msim[P], Ssim[P][P];
-        dynamic_propagate<P>(Q, mf, Sf, mp, Sp);
-        dynamic_add_noise<P>(Sp, c, R, Sp);
-        smooth_gain<P>(Q, Sf, Sp, T, G);
-        smooth_sim_block<P>(G, T, mf, Sf, mp, xn, msim, Ssim);
-        normals<P>(a.seed, traj, (uint32_t)n, (uint32_t)blk, PURPOSE_SMOOTH, z);
-        mvn_draw<P>(msim, Ssim, z, xn);
-        store_x(n, xn);
-        if (n >= 2) {
-            c = cn;
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                mf[i] = mfn[i];
-#pragma unroll
-                for (int j = 0; j < P; ++j) Sf[i][j] = Sfn[i][j];
-            }
-        }
-    }
-    // x[0] = ode_init exactly (solve.py:196-204)
-    double x0[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) x0[i] = a.mean[((size_t)blk * P + i) * B + b];
-    store_x(0, x0);
+    BwdLane<P> ln;
+    if (ln.init(a)) bwd_sample_lane<P>(a, ln, ScaledPrior<P>{scale});
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------
@@ -174,12 +102,12 @@ static int launch_dynamic_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArg
 }
 
 static int launch_dynamic_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const double* scale) {
-    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
+    const LaunchGeom g = bwd_lane_geom(a.B, a.D);
     const bool sim = mode == RK_MODE_SIM;
     LaunchTimer t(h, sim ? "dynamic_bwd_sim_kernel" : "dynamic_bwd_mv_kernel");
     const bool ok = dispatch_int<DYNAMIC_PMIN, DYNAMIC_PMAX>(c->n_bstate, [&](auto P) {
-        if (sim) hipLaunchKernelGGL((dynamic_bwd_sim_kernel<P>), grid, block, 0, h->stream, a, scale);
-        else hipLaunchKernelGGL((dynamic_bwd_mv_kernel<P>), grid, block, 0, h->stream, a, scale);
+        if (sim) hipLaunchKernelGGL((dynamic_bwd_sim_kernel<P>), g.grid, g.block, 0, h->stream, a, scale);
+        else hipLaunchKernelGGL((dynamic_bwd_mv_kernel<P>), g.grid, g.block, 0, h->stream, a, scale);
     });
     RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dynamic: no backward kernel for n_bstate %d", c->n_bstate);
     t.stop();

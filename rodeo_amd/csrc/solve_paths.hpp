@@ -163,6 +163,8 @@ constexpr int tile_waves(int D) { return D <= 4 ? 1 : (D + 3) / 4; }
 inline LaunchGeom fwd_lane_geom(int B) { return {dim3(div_up(B, 64)), dim3(64)}; }
 // fwd_sqrt_kernel: 64 / D trajectories per wave (solve_sqrt_kernels.hpp)
 inline LaunchGeom fwd_sqrt_geom(int B, int D) { return {dim3(div_up(B, 64 / D)), dim3(64)}; }
+// the backward lane kernels of lane_backward.hpp, one (block, trajectory) per lane (bwd_sim_draws_kernel adds grid.y)
+inline LaunchGeom bwd_lane_geom(int B, int D) { return {dim3(div_up(B * D, 64)), dim3(64)}; }
 // fwd_tile3_kernel, fwd_tile4_kernel, fwd_tilen_kernel: whole trajectories in one wave up to four blocks, beyond that one
 // workgroup of tile_waves(D) waves per trajectory
 inline LaunchGeom fwd_tile_geom(int B, int D) {

@@ -10,7 +10,7 @@
 // The whole N-step recursion of a trajectory runs inside ONE kernel launch; the state lives in VGPRs and only the
 // filtered / smoothed moments touch HBM, in the batch-minor layout of include/rodeo_kalman.h (512 B per wave per
 // element row).  Predicted moments are re-evaluated from the filtered ones in the backward pass instead of being
-// stored (they are a pure function of filt[n], Q, R: standard.py:57-59).
+// stored (they are a pure function of filt[n], Q, R: standard.py:57-59): bwd_walk of lane_backward.hpp under StaticPrior.
 #include "common.hpp"
 #include "kalman_small.hpp"
 #include "philox.hpp"
@@ -18,92 +18,21 @@
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
 #include "solve_small_kernels.hpp"
-#include "records.hpp"
+#include "lane_backward.hpp"
 
 namespace rk {
 
 // ---- backward passes: one lane per (block, trajectory) -----------------------------------------------------------
 template <int P>
 __global__ void __launch_bounds__(64) bwd_mv_kernel(SolveArgs a) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= a.B * a.D) return;
-    const int blk = l / a.B, b = l - blk * a.B;
-    const size_t B = (size_t)a.B;
-    double Q[P][P], R[P][P];
-    load_block_consts<P>(a, blk, b, Q, R);
-
-    double ms[P], Ss[P][P];                    // carry: smoothed moments at n+1 (solve.py:279-282)
-    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, ms, Ss);
-    double mf[P], Sf[P][P];
-    if (a.N >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
-    for (int n = a.N - 1; n >= 1; --n) {
-        // software prefetch of the next (earlier) filtered state while this step computes
-        double mfn[P], Sfn[P][P];
-        if (n >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
-        double mp[P], Sp[P][P], T[P][P], G[P][P];
-        predict_block<P>(Q, R, mf, Sf, mp, Sp);          // pred[n+1] re-evaluated from filt[n]
-        smooth_gain<P>(Q, Sf, Sp, T, G);
-        smooth_mv_block<P>(G, mf, Sf, mp, Sp, ms, Ss);
-        store_moments<P>(a.mean, a.var, B, a.D, n, blk, b, ms, Ss);
-        if (n >= 2) {
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                mf[i] = mfn[i];
-#pragma unroll
-                for (int j = 0; j < P; ++j) Sf[i][j] = Sfn[i][j];
-            }
-        }
-    }
-    // time 0 keeps (ode_init, 0) written by the forward pass (solve.py:295-301)
+    BwdLane<P> ln;
+    if (ln.init(a)) bwd_smooth_lane<P>(a, ln, StaticPrior<P>{});
 }
 
 template <int P>
 __global__ void __launch_bounds__(64) bwd_sim_kernel(SolveArgs a) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= a.B * a.D) return;
-    const int blk = l / a.B, b = l - blk * a.B;
-    const size_t B = (size_t)a.B;
-    const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
-    double Q[P][P], R[P][P];
-    load_block_consts<P>(a, blk, b, Q, R);
-
-    auto store_x = [&](int n, const double (&x)[P]) {
-        double* xo = a.x + ((size_t)n * a.D + blk) * P * B + b;
-#pragma unroll
-        for (int i = 0; i < P; ++i) xo[(size_t)i * B] = x[i];
-    };
-
-    double mf[P], Sf[P][P], xn[P], z[P];
-    // terminal draw x_N ~ N(filt[N]) (solve.py:182-186)
-    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, mf, Sf);
-    normals<P>(a.seed, traj, (uint32_t)a.N, (uint32_t)blk, PURPOSE_SMOOTH, z);
-    mvn_draw<P>(mf, Sf, z, xn);
-    store_x(a.N, xn);
-    if (a.N >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
-    for (int n = a.N - 1; n >= 1; --n) {
-        double mfn[P], Sfn[P][P];
-        if (n >= 2) load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
-        double mp[P], Sp[P][P], T[P][P], G[P][P], msim[P], Ssim[P][P];
-        predict_block<P>(Q, R, mf, Sf, mp, Sp);
-        smooth_gain<P>(Q, Sf, Sp, T, G);
-        smooth_sim_block<P>(G, T, mf, Sf, mp, xn, msim, Ssim);
-        normals<P>(a.seed, traj, (uint32_t)n, (uint32_t)blk, PURPOSE_SMOOTH, z);
-        mvn_draw<P>(msim, Ssim, z, xn);
-        store_x(n, xn);
-        if (n >= 2) {
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                mf[i] = mfn[i];
-#pragma unroll
-                for (int j = 0; j < P; ++j) Sf[i][j] = Sfn[i][j];
-            }
-        }
-    }
-    // x[0] = ode_init exactly (solve.py:196-204)
-    double x0[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) x0[i] = a.mean[((size_t)blk * P + i) * B + b];
-    store_x(0, x0);
+    BwdLane<P> ln;
+    if (ln.init(a)) bwd_sample_lane<P>(a, ln, StaticPrior<P>{});
 }
 
 // ---- Gaussian observation log-posterior reduction (docs/examples/parameter.md:188-210) ---------------------------
@@ -202,11 +131,11 @@ static int small_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a)
 
 template <bool SIM>
 static int small_backward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
-    const dim3 grid(div_up(a.B * a.D, 64)), block(64);
+    const LaunchGeom g = bwd_lane_geom(a.B, a.D);
     LaunchTimer t(h, SIM ? "bwd_sim_kernel" : "bwd_mv_kernel");
     const bool ok = dispatch_int<2, 9>(c->n_bstate, [&](auto P) {
-        if (SIM) hipLaunchKernelGGL((bwd_sim_kernel<P>), grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((bwd_mv_kernel<P>), grid, block, 0, h->stream, a);
+        if (SIM) hipLaunchKernelGGL((bwd_sim_kernel<P>), g.grid, g.block, 0, h->stream, a);
+        else hipLaunchKernelGGL((bwd_mv_kernel<P>), g.grid, g.block, 0, h->stream, a);
     });
     RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "small-block path supports n_bstate in [2, 9] for the backward pass, got %d", c->n_bstate);
     t.stop();
