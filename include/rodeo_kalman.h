@@ -342,6 +342,30 @@ int rk_solve_evidence(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* i
 int rk_solve_dynamic(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
                      double scale_min, double* scale, double* logdens);
 
+/* solve_mv_grid / solve_sim_grid (an addition): rk_solve_mv / rk_solve_sim on a non-uniform grid that the whole batch shares.
+ * Node n sits at t[n] (n = 0..n_steps, strictly increasing; cfg->t_min / t_max are not read), step n -> n + 1 takes the prior
+ * pair (q, r)[slot[n]] in place of in->prior_weight / prior_var -- steps of one length share a slot -- and interrogates at
+ * t[n+1].  The smoothing gain of step n is formed with that step's q.  Pairs are (n_slots, d, p, p) row-major, or
+ * (n_slots, d, p, p, B) batch-minor where q_batched / r_batched say so; slots are clamped to 0..n_slots-1.  in->prior_weight /
+ * prior_var must still be given (slot 0's, by convention) but are not read by the kernels.
+ * mode = RK_MODE_MV smooths into out->mean_state / var_state, RK_MODE_SIM samples into out->x_state (Philox keys as in
+ * rk_solve_sim; mean_state / var_state then hold the filtered moments).  All records are RK_LAYOUT_BATCH_MINOR and cfg->flags
+ * must carry RK_FLAG_BATCH_MINOR.  No workspace.
+ * Served: kalman_type standard, n_bmeas = 1, n_bstate 2..6 (2..5 with three or more blocks), the four interrogations, any
+ * built-in right-hand side or a user one with n_bmeas = 1; one lane per trajectory forward (grid_kernels.hpp), one per
+ * (trajectory, block) backward (grid.hip).  What is not served is refused on cfg and mode alone -- RK_ERR_INVALID (a
+ * non-positive size, another mode, RK_FLAG_BATCH_MINOR missing) or RK_ERR_UNSUPPORTED -- before the handle or any pointer is
+ * looked at.                                                                                                               */
+typedef struct {
+    const double*  t;                                    /* (n_steps + 1) node times on the device                */
+    const int32_t* slot;                                 /* (n_steps) slot of every step on the device            */
+    const double  *q, *r;                                /* (n_slots, d, p, p [,B]): Q, R of every slot            */
+    int32_t        q_batched, r_batched;
+    int32_t        n_slots;
+} rk_grid_in;
+int rk_solve_grid(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                  const rk_grid_in* g);
+
 /* solve_sim_draws (an addition): n_draws sample paths per trajectory from one forward filter.  Runs the forward pass of
  * rk_solve_filter (cfg must carry RK_FLAG_BATCH_MINOR; out->mean_state / var_state hold the filtered moments afterwards), then
  * one backward kernel, one lane per (chunk of draws, block, trajectory), which does the work that no draw changes -- the

@@ -76,6 +76,11 @@ class DaltonAtIn(C.Structure):
                 ("prior_batched", C.c_int32)]
 
 
+class GridIn(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("slot", C.c_void_p), ("q", C.c_void_p), ("r", C.c_void_p),
+                ("q_batched", C.c_int32), ("r_batched", C.c_int32), ("n_slots", C.c_int32)]
+
+
 class OpCfg(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_state", C.c_int32), ("n_meas", C.c_int32), ("kalman_type", C.c_int32)]
 
@@ -135,6 +140,7 @@ SIGNATURES = {
     "rk_daltonng_solve": (C.c_int, [_H, _P, _P, _P, _I, _I, _P, _P, _I]),
     "rk_solve_evidence": (C.c_int, [_H, _P, _P, _P, _P, _P]),
     "rk_solve_dynamic": (C.c_int, [_H, _P, _P, _P, _I, _D, _P, _P]),
+    "rk_solve_grid": (C.c_int, [_H, _P, _P, _P, _I, C.POINTER(GridIn)]),
     "rk_solve_sim_draws": (C.c_int, [_H, _P, _P, _P, _I, _P, _I, _P]),
     "rk_sim_draws_chunk": (C.c_int, []),
     "rk_magi_logdens": (C.c_int, [_H, C.POINTER(MagiCfg), C.POINTER(MagiIn), _P]),

@@ -28,6 +28,7 @@ struct ScaledPrior {
         dynamic_propagate<P>(ln.Q, mf, Sf, mp, Sp);      // pred[n+1] from filt[n] and scale[n]
         dynamic_add_noise<P>(Sp, c, ln.R, Sp);
     }
+    __device__ __forceinline__ const auto& trans(const BwdLane<P>& ln, const Datum&) const { return ln.Q; }
 };
 
 template <int P>

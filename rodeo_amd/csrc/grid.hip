@@ -1,0 +1,154 @@
+// solve_mv_grid / solve_sim_grid (an addition): host side of rk_solve_grid, the solver on a
+// non-uniform grid shared by the batch -- every step has its own length, hence its own prior pair (Q, R), named by a slot
+// (grid_kernels.hpp) -- and the two backward kernels.  One route: the lanes on batch-minor records -- grid_fwd_kernel, one
+// lane per trajectory, then grid_bwd_mv_kernel or grid_bwd_sim_kernel, one lane per (trajectory, block): the passes of
+// bwd_mv_kernel / bwd_sim_kernel (lane_backward.hpp: bwd_smooth_lane / bwd_sample_lane over bwd_walk) under the prediction
+// policy SlotPrior, Q_n Sigma_f[n] Q_n^T + R_n with the gain from Q_n.  Standard form, n_bmeas = 1.  No workspace.
+#include <cmath>
+#include "common.hpp"
+#include "rhs.hpp"
+#include "solve_args.hpp"
+#include "solve_paths.hpp"
+#include "grid_kernels.hpp"
+#include "lane_backward.hpp"
+
+namespace rk {
+
+// ---- backward passes: one lane per (block, trajectory) -----------------------------------------------------------
+// bwd_walk's prediction policy with the prior pair of step n -> n + 1, which is fetched next to filt[n] (so one step ahead of
+// its use, like the record) and is the transition matrix of that step's smoothing gain.  The lane's own Q, R are not read.
+template <int P>
+struct SlotPrior {
+    GridArgs g;
+    struct Datum { double Q[P][P], R[P][P]; };
+    __device__ __forceinline__ Datum fetch(const SolveArgs& a, const BwdLane<P>& ln, int n) const {
+        Datum c;
+        grid_load_pair<P>(g, a.B, a.D, grid_slot(g, n), ln.blk, ln.b, c.Q, c.R);
+        return c;
+    }
+    __device__ __forceinline__ void predict(const BwdLane<P>&, const Datum& c, const double (&mf)[P], const double (&Sf)[P][P],
+                                            double (&mp)[P], double (&Sp)[P][P]) const {
+        predict_block<P>(c.Q, c.R, mf, Sf, mp, Sp);       // pred[n+1] from filt[n] and the pair of step n
+    }
+    __device__ __forceinline__ const auto& trans(const BwdLane<P>&, const Datum& c) const { return c.Q; }
+};
+
+template <int P>
+__global__ void __launch_bounds__(64) grid_bwd_mv_kernel(SolveArgs a, GridArgs g) {
+    BwdLane<P> ln;
+    if (ln.init(a)) bwd_smooth_lane<P>(a, ln, SlotPrior<P>{g});
+}
+
+template <int P>
+__global__ void __launch_bounds__(64) grid_bwd_sim_kernel(SolveArgs a, GridArgs g) {
+    BwdLane<P> ln;
+    if (ln.init(a)) bwd_sample_lane<P>(a, ln, SlotPrior<P>{g});
+}
+
+// ---- dispatch ---------------------------------------------------------------------------------------------------
+// n_bstate of the forward instances: an instance ships only if it needs no more scratch than fwd_kernel at the same
+// (RHS, P, ITG) -- DESIGN.md section 7 (15) has the figures of every instance and of the ones that are left out
+constexpr int GRID_PMIN = 2, GRID_PMAX = 6;
+constexpr int GRID_PMAX_THREE_BLOCKS = 5;
+template <class RHS>
+constexpr int grid_pmax() { return RHS::D >= 3 ? GRID_PMAX_THREE_BLOCKS : GRID_PMAX; }
+
+// Is this call served?  Decided on the configuration and the mode alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
+static int grid_check(const rk_solve_cfg* c, int mode) {
+    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
+               "grid: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", c->n_traj,
+               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
+    RK_REQUIRE(mode == RK_MODE_MV || mode == RK_MODE_SIM, RK_ERR_INVALID, "grid: mode must be RK_MODE_MV or RK_MODE_SIM, got %d",
+               mode);
+    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "grid: cfg->flags must carry RK_FLAG_BATCH_MINOR (the records "
+               "are the batch-minor ones)");
+    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "grid: RK_FLAG_STORE_PRED is not served");
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
+               "grid: unknown kalman_type %d", c->kalman_type);
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "grid: kalman_type square-root is not built");
+    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_CHKREBTII, RK_ERR_UNSUPPORTED,
+               "grid: interrogate id %d is not supported (rodeo, schober, kramer, chkrebtii)", c->interrogate);
+    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "grid: n_bmeas = 1 only (the dense / indep_init form is not served), got %d",
+               c->n_bmeas);
+    RK_REQUIRE(c->n_bstate >= GRID_PMIN && c->n_bstate <= GRID_PMAX, RK_ERR_UNSUPPORTED, "grid: n_bstate in %d..%d, got %d",
+               GRID_PMIN, GRID_PMAX, c->n_bstate);
+    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= GRID_PMAX_THREE_BLOCKS, RK_ERR_UNSUPPORTED,
+               "grid: n_bstate up to %d with three or more blocks, got %d", GRID_PMAX_THREE_BLOCKS, c->n_bstate);
+    if (is_user_rhs(c->rhs_id)) return user_grid_check(c);
+    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "grid: unknown rhs_id %d", c->rhs_id);
+    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "grid: rhs %d needs another n_block than %d",
+               c->rhs_id, c->n_block);
+    return RK_OK;
+}
+
+template <class RHS>
+static int launch_grid_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga) {
+    const LaunchGeom g = fwd_lane_geom(a.B);
+    bool ok = false;
+    dispatch_int<GRID_PMIN, grid_pmax<RHS>()>(c->n_bstate, [&](auto P) {
+        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
+            LaunchTimer t(h, "grid_fwd_kernel");
+            hipLaunchKernelGGL((grid_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga);
+            t.stop();
+            ok = true;
+        });
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "grid: no kernel for rhs %d, n_bstate %d, interrogate %d", c->rhs_id, c->n_bstate,
+               c->interrogate);
+    RK_HIP(hipGetLastError());
+    return RK_OK;
+}
+
+static int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga) {
+    const LaunchGeom g = bwd_lane_geom(a.B, a.D);
+    const bool sim = mode == RK_MODE_SIM;
+    LaunchTimer t(h, sim ? "grid_bwd_sim_kernel" : "grid_bwd_mv_kernel");
+    const bool ok = dispatch_int<GRID_PMIN, GRID_PMAX>(c->n_bstate, [&](auto P) {
+        if (sim) hipLaunchKernelGGL((grid_bwd_sim_kernel<P>), g.grid, g.block, 0, h->stream, a, ga);
+        else hipLaunchKernelGGL((grid_bwd_mv_kernel<P>), g.grid, g.block, 0, h->stream, a, ga);
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "grid: no backward kernel for n_bstate %d", c->n_bstate);
+    t.stop();
+    RK_HIP(hipGetLastError());
+    return RK_OK;
+}
+
+}  // namespace rk
+
+using namespace rk;
+
+extern "C" {
+
+int rk_solve_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                  const rk_grid_in* g) {
+    RK_REQUIRE(c, RK_ERR_INVALID, "rk_solve_grid: null cfg");
+    int rc = grid_check(c, mode);                                   // (the configuration alone, before anything else is looked at)
+    if (rc) return rc;
+    RK_REQUIRE(h && out && g, RK_ERR_INVALID, "rk_solve_grid: null argument");
+    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
+               "rk_solve_grid: grid needs t, slot, q, r and n_slots >= 1 (got %d)", g->n_slots);
+    rc = check_cfg(c, in);
+    if (rc) return rc;
+    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID, "rk_solve_grid: out->mean_state / var_state must not be NULL");
+    RK_REQUIRE(mode != RK_MODE_SIM || out->x_state, RK_ERR_INVALID, "rk_solve_grid: RK_MODE_SIM needs out->x_state");
+    rc = begin_solve(h);
+    if (rc) return rc;
+    SolveArgs a;
+    make_args(c, in, out, a);
+    const GridArgs ga{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
+    if (is_user_rhs(c->rhs_id)) {
+        rc = user_grid(h, c, a, ga);
+    } else {
+        rc = RK_ERR_UNSUPPORTED;
+        with_builtin_rhs(c->rhs_id, [&](auto rhs) {
+            using RHS = decltype(rhs);
+            rc = check_n_theta<RHS>(c, a);
+            if (rc) return;
+            rc = launch_grid_fwd<RHS>(h, c, a, ga);
+        });
+    }
+    if (rc) return rc;
+    return launch_grid_bwd(h, c, a, mode, ga);
+}
+
+}  // extern "C"

@@ -2,7 +2,8 @@
 // backward passes"): the lane and its model constants, the walk down the filtered records -- load, prefetch, re-evaluated
 // prediction, smoothing gain, rotation -- under a prediction policy and a step, a sampled path's stores, and the smoothing and
 // one-draw sampling passes built from them: bwd_mv_kernel / bwd_sim_kernel (solve_small.hip), dynamic_bwd_mv_kernel /
-// dynamic_bwd_sim_kernel (dynamic.hip); bwd_sim_draws_kernel (sim_draws.hip) mirrors them.  Ahead-of-time code only.
+// dynamic_bwd_sim_kernel (dynamic.hip), grid_bwd_mv_kernel / grid_bwd_sim_kernel (grid.hip); bwd_sim_draws_kernel
+// (sim_draws.hip) mirrors them.  Ahead-of-time code only.
 #pragma once
 #include "records.hpp"
 #include "kalman_small.hpp"
@@ -51,8 +52,10 @@ __device__ __forceinline__ void load_path_init(const SolveArgs& a, const BwdLane
 }
 
 // ---- the walk ------------------------------------------------------------------------------------------------------------
-// A prediction policy has Datum, what it needs of a node next to the node's moments, fetch(a, ln, n) and predict(ln, datum,
-// mf, Sf, mp, Sp).  The static prior's: predict_block, nothing to fetch (the dynamic solver's is ScaledPrior in dynamic.hip).
+// A prediction policy has Datum, what it needs of a node next to the node's moments, fetch(a, ln, n), predict(ln, datum,
+// mf, Sf, mp, Sp) and trans(ln, datum), the transition matrix of the step that the smoothing gain needs.  The static prior's:
+// predict_block, nothing to fetch, the lane's Q (the dynamic solver's is ScaledPrior in dynamic.hip, the grid solver's SlotPrior
+// in grid.hip, the one whose Q changes from step to step).
 template <int P>
 struct StaticPrior {
     struct Datum {};
@@ -61,6 +64,7 @@ struct StaticPrior {
                                             double (&mp)[P], double (&Sp)[P][P]) const {
         predict_block<P>(ln.Q, ln.R, mf, Sf, mp, Sp);
     }
+    __device__ __forceinline__ const auto& trans(const BwdLane<P>& ln, const Datum&) const { return ln.Q; }
 };
 
 // Nodes n = N-1 .. 1 (none for N = 1): step(n, mf, Sf, mp, Sp, T, G) with filt[n], pred[n+1] re-evaluated from it and the
@@ -83,7 +87,7 @@ __device__ __forceinline__ void bwd_walk(const SolveArgs& a, const BwdLane<P>& l
         }
         double mp[P], Sp[P][P], T[P][P], G[P][P];
         pred.predict(ln, c, mf, Sf, mp, Sp);             // pred[n+1] re-evaluated from filt[n]
-        smooth_gain<P>(ln.Q, Sf, Sp, T, G);
+        smooth_gain<P>(pred.trans(ln, c), Sf, Sp, T, G);
         step(n, mf, Sf, mp, Sp, T, G);
         if (n >= 2) {
             c = cn;
@@ -97,7 +101,7 @@ __device__ __forceinline__ void bwd_walk(const SolveArgs& a, const BwdLane<P>& l
     }
 }
 
-// ---- the two passes, for the solver (StaticPrior) and the dynamic solver (ScaledPrior) -------------------------------------
+// ---- the two passes, for the solver (StaticPrior), the dynamic solver (ScaledPrior) and the grid solver (SlotPrior) -------
 // solve.py:257-301: smoothing in place over the filtered moments; time 0 keeps the forward pass's (ode_init, 0) (295-301)
 template <int P, class Pred>
 __device__ __forceinline__ void bwd_smooth_lane(const SolveArgs& a, const BwdLane<P>& ln, const Pred& pred) {

@@ -75,6 +75,7 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_EVIDENCE_TILE3     */ {"rk::evidence_tile3_kernel<rk::UserRhsT, {I}>", "evidence_tile3_kernels.hpp", "evidence_tile3_kernel<user>"},
     /* JIT_EVIDENCE_SQRT      */ {"rk::evidence_sqrt_kernel<rk::UserRhsT, {P}, {I}>", "evidence_kernels.hpp", "evidence_sqrt_kernel<user>"},
     /* JIT_DYNAMIC            */ {"rk::dynamic_fwd_kernel<rk::UserRhsT, {P}, {I}>", "dynamic_kernels.hpp", "dynamic_fwd_kernel<user>"},
+    /* JIT_GRID               */ {"rk::grid_fwd_kernel<rk::UserRhsT, {P}, {I}>", "grid_kernels.hpp", "grid_fwd_kernel<user>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -474,6 +475,26 @@ int user_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double 
     SolveArgs args = a;
     void* params[] = {&args, &scale_min, &scale, &logdens};
     return launch_jit(h, jit_key(JIT_DYNAMIC, c->rhs_id, c), fwd_lane_geom(a.B), params);
+}
+
+// solve_mv_grid / solve_sim_grid around a user right-hand side (grid_kernels.hpp): the configuration against the registration
+// (n_block, n_bmeas = 1; the n_bstate range is grid.hip's) and the forward launch, like grid.hip's built-in instances.  The
+// backward kernels do not depend on the right-hand side: grid.hip launches its own.
+int user_grid_check(const rk_solve_cfg* c) {
+    const UserRhs* u;
+    const int rc = user_rhs(c->rhs_id, &u);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
+               "grid: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
+    return RK_OK;
+}
+
+int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g) {
+    const int rc = user_grid_check(c);
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&g};
+    return launch_jit(h, jit_key(JIT_GRID, c->rhs_id, c), fwd_lane_geom(a.B), params);
 }
 
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,

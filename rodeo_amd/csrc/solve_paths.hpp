@@ -17,6 +17,7 @@ struct SimLogpost;
 struct DaltonObs;
 struct DaltonAt;
 struct FenrirAt;
+struct GridArgs;
 
 // ---- lane-per-trajectory solver (solve_small.hip): helpers that DALTON (dalton.hip) and Fenrir (fenrir.hip) share ------
 int check_cfg(const rk_solve_cfg* c, const rk_solve_in* in);
@@ -57,6 +58,7 @@ enum JitKind : int {
     JIT_EVIDENCE_TILE3 = 21,  // evidence_tile3_kernel (solve_evidence on the p = 3 tiles)
     JIT_EVIDENCE_SQRT = 22,   // evidence_sqrt_kernel (solve_evidence, square-root form)
     JIT_DYNAMIC = 23,         // dynamic_fwd_kernel (solve_mv_dynamic / solve_sim_dynamic, the forward lanes)
+    JIT_GRID = 24,            // grid_fwd_kernel (solve_mv_grid / solve_sim_grid, the forward lanes)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -78,6 +80,9 @@ int user_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int ro
 // solve_mv_dynamic / solve_sim_dynamic: the configuration against the registration and the forward launch (dynamic.hip)
 int user_dynamic_check(const rk_solve_cfg* c);
 int user_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double scale_min, double* scale, double* logdens);
+// solve_mv_grid / solve_sim_grid: the configuration against the registration and the forward launch (grid.hip)
+int user_grid_check(const rk_solve_cfg* c);
+int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them

@@ -1,0 +1,158 @@
+"""
+``solve_mv_grid`` / ``solve_sim_grid`` (an addition): the solver on the grid it is given, where
+``solve_mv`` / ``solve_sim`` take ``t_min, t_max, n_steps`` and so one step length for the whole horizon.
+
+    solve_mv_grid (key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, kalman_type="standard", **params)
+        -> (mean (N+1, d, p), var (N+1, d, p, p))
+    solve_sim_grid(... same arguments ...)
+        -> x (N+1, d, p)
+
+THE GRID.  ``t_grid`` (N+1,) is finite and strictly increasing and is shared by the whole batch; node 0 is ``(ode_init, 0)``.
+Step n has length h_n = t[n+1] - t[n], predicts with the prior pair of that length and interrogates at t[n+1]; the backward
+passes are ``solve_mv``'s and ``solve_sim``'s with every step's own pair, in the prediction and in the smoothing gain.
+
+SLOTS.  ``prior_at(dt)`` -- the callable ``solve_mv_at`` takes, for the IBM prior ``lambda h: ibm_init(h, n_deriv, sigma)`` --
+is called once per SLOT: step n joins the first earlier slot whose representative length is within ``1e-12 * max h`` of h_n and
+opens a new one otherwise (``grid_slots``).  A ``np.linspace`` grid is one slot; a fully irregular grid costs N host calls of
+``prior_at`` and N pairs on the device.
+
+All of it runs on the device (``rk_solve_grid``): ``grid_fwd_kernel``, one lane per trajectory, then ``grid_bwd_mv_kernel`` or
+``grid_bwd_sim_kernel``, one lane per (trajectory, block), on batch-minor records.
+"""
+import ctypes as C
+import numpy as np
+from . import _lib
+from .solve import _KALMAN, _device_ode, _shape_rule, cached_plan
+from .inference._obs import _stack_pairs
+
+BSTATE = (2, 6)                                                     # n_bstate served
+BSTATE_THREE_BLOCKS = 5                                             # three or more blocks
+SLOT_TOL = 1e-12                                                    # of the longest step
+
+
+def _grid(t_grid):
+    """``t_grid`` as a float64 array, or the ValueError."""
+    try:
+        t = np.asarray(t_grid, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("t_grid must be a 1-D array of node times") from None
+    if t.ndim != 1:
+        raise ValueError(f"t_grid must be 1-D, one grid shared by the whole batch (per-trajectory grids are not built), got shape "
+                         f"{t.shape}")
+    if t.size < 2:
+        raise ValueError(f"t_grid needs at least two nodes, got {t.size}")
+    if not np.all(np.isfinite(t)):
+        raise ValueError("t_grid holds a non-finite time")
+    if not np.all(np.diff(t) > 0.0):
+        raise ValueError("t_grid must be strictly increasing")
+    return t
+
+
+def grid_slots(t_grid):
+    """
+    The slot rule: ``(h_rep, slot)`` with ``slot`` (N,) int32, the slot of every step, and ``h_rep`` (n_slots,) the
+    representative step length of every slot -- the length of the step that opened it.  Step n joins the first earlier slot
+    whose representative is within ``1e-12 * max h`` of h_n, else it opens a new one; slot[0] is 0.
+    """
+    h = np.diff(_grid(t_grid))
+    tol = SLOT_TOL * h.max()
+    rep = np.empty(len(h))
+    slot = np.empty(len(h), dtype=np.int32)
+    k = 0
+    for n, x in enumerate(h):
+        near = np.flatnonzero(np.abs(rep[:k] - x) <= tol)
+        if near.size:
+            slot[n] = near[0]
+        else:
+            rep[k], slot[n] = x, k
+            k += 1
+    return rep[:k].copy(), slot
+
+
+def _refusals(name, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params):
+    """Everything this build does not serve, raised before any device work; returns (ode, t, slot, pairs)."""
+    t = _grid(t_grid)
+    if kalman_type not in _KALMAN:
+        raise NotImplementedError(f"{name}: unknown kalman_type {kalman_type!r}")
+    if kalman_type != "standard":
+        raise NotImplementedError(f"{name}: kalman_type='square-root' is not built")
+    W = np.shape(ode_weight)
+    if len(W) not in (3, 4):
+        raise ValueError("ode_weight must have shape (n_block, n_bmeas, n_bstate) [+ a leading batch axis]")
+    d, m, p = W[-3:]
+    if m != 1:
+        raise NotImplementedError(f"{name} on the device: n_bmeas = 1 only (the dense / indep_init form is not served)")
+    if not BSTATE[0] <= p <= BSTATE[1]:
+        raise NotImplementedError(f"{name} on the device: n_bstate in {BSTATE[0]}..{BSTATE[1]}, got {p}")
+    if d >= 3 and p > BSTATE_THREE_BLOCKS:
+        raise NotImplementedError(f"{name} on the device: n_bstate up to {BSTATE_THREE_BLOCKS} with three or more blocks, got {p}")
+    if not callable(prior_at):
+        raise ValueError(f"{name}: prior_at must be a callable dt -> (wgt_state, var_state)")
+    h_rep, slot = grid_slots(t)
+    pairs = []
+    for h in h_rep:
+        try:
+            Qh, Rh = (np.asarray(a, dtype=np.float64) for a in prior_at(float(h)))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: prior_at(dt) must return the pair (wgt_state, var_state)") from None
+        for a in (Qh, Rh):
+            if a.ndim not in (3, 4) or a.shape[-3:] != (d, p, p):
+                raise ValueError(f"{name}: prior_at(dt) must return matrices of shape ({d}, {p}, {p}) or (B, {d}, {p}, {p}), got "
+                                 f"{Qh.shape} and {Rh.shape}")
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"{name}: prior_at({float(h)!r}) returned a non-finite matrix")
+        pairs.append((Qh, Rh))
+    ode = _device_ode(ode_fun, ode_weight, params)
+    if (ode.n_block, ode.n_bmeas) != (d, m):
+        raise ValueError(f"ODE '{ode.name}' has (n_block, n_bmeas) = ({ode.n_block}, {ode.n_bmeas}) but ode_weight has ({d}, {m})")
+    sizes = _shape_rule(ode, ode_weight, ode_init, pairs[0], params)[-1]     # ValueError: ranks, mismatched shapes, batch sizes
+    for Qh, Rh in pairs[1:]:
+        for a in (Qh, Rh):
+            if a.ndim == 4 and (not sizes or a.shape[0] != sizes[0]):
+                raise ValueError(f"{name}: prior_at returned a batch of {a.shape[0]} where the call has "
+                                 f"{sizes[0] if sizes else 'none (the first step decides)'}")
+    return ode, t, slot, pairs
+
+
+def _run(name, mode, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, kalman_type, params):
+    """The refusals, the cached batch-minor plan (its own prior pair is slot 0's), the staged grid and one rk_solve_grid."""
+    ode, t, slot, pairs = _refusals(name, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
+    plan = cached_plan(ode, ode_weight, ode_init, t[0], t[-1], len(slot), interrogate, pairs[0], kalman_type,
+                       batch_minor=True, **params)
+    (q, r), batched = _stack_pairs(pairs, plan.B)
+    d_t, d_slot, d_q, d_r = plan.staged("grid", t, slot, q, r)
+    g = _lib.GridIn(t=d_t.ptr, slot=d_slot.ptr, q=d_q.ptr, r=d_r.ptr, q_batched=batched, r_batched=batched, n_slots=len(pairs))
+    plan.launch(plan.dev.lib.rk_solve_grid, key, mode, mode, C.byref(g))
+    if plan.layout != _lib.LAYOUT_BATCH_MINOR:                       # (batch_minor=True: the records rk_solve_grid writes)
+        raise RuntimeError(f"{name}: the plan reports layout {plan.layout}, not the batch-minor records")
+    return plan
+
+
+def solve_mv_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, kalman_type="standard", **params):
+    """
+    Mean and variance of the solver on the nodes ``t_grid``: ``mean`` (N+1, d, p) and ``var`` (N+1, d, p, p), the strided
+    batch-first views ``solve_mv`` returns, with a leading B for batched inputs.  ``key``, ``ode_fun``, ``ode_weight``,
+    ``ode_init``, ``interrogate`` and ``**params`` are ``solve_mv``'s, with its batching rules (a leading batch axis on
+    ``ode_init``, ``**params`` and on what ``prior_at`` returns: a batched sigma gives a batched R).
+
+    ``t_grid`` (N+1,) is finite, strictly increasing and shared by the batch.  ``prior_at(dt)`` returns the prior
+    ``(wgt_state, var_state)`` for a step of length dt; it is called once per slot of ``grid_slots(t_grid)``, never more: once
+    for a uniform grid, N times on the host for a fully irregular one.
+
+    Refused before any device work: ValueError for a ``t_grid`` that is not 1-D (per-trajectory grids are not built), shorter
+    than 2, non-finite or not strictly increasing, for ``prior_at`` results of the wrong shape or non-finite, and for the shapes
+    ``solve_mv`` refuses; NotImplementedError for an unknown ``kalman_type``, for ``"square-root"`` (not built), n_bmeas > 1 and
+    n_bstate outside 2 .. 6 (2 .. 5 with three or more blocks).
+    """
+    return _run("solve_mv_grid", _lib.MODE_MV, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, kalman_type,
+                params).state_host()
+
+
+def solve_sim_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, kalman_type="standard", **params):
+    """
+    One sample solution per trajectory on the nodes ``t_grid``: ``x`` (N+1, d, p), a leading B for batched inputs (same
+    arguments, batching rules, slots and refusals as ``solve_mv_grid``).  ``key`` seeds the backward draws, keyed by
+    trajectory, step and block like ``solve_sim``'s; ``x[0]`` is ``ode_init``.
+    """
+    return _run("solve_sim_grid", _lib.MODE_SIM, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, kalman_type,
+                params).x_host()
