@@ -366,6 +366,27 @@ typedef struct {
 int rk_solve_grid(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
                   const rk_grid_in* g);
 
+/* dalton_grid (an addition): rk_dalton_loglik / rk_dalton_solve on rk_solve_grid's non-uniform grid, every observation on a node.
+ * obs / obs_weight / obs_var as for rk_dalton_loglik (n_bobs = 1..3); obs_ind (n_obs) holds the NODE of every observation,
+ * strictly increasing in 0..n_steps: node 0 enters the joint density only and does not update x_0, a node above n_steps never
+ * matches.  Step n -> n + 1 of the joint filter: the prediction with (q, r)[slot[n]], the interrogation at t[n+1], the z forecast
+ * log-density and update, then -- if node n + 1 is observed -- the conditioning on y, per block (z first, y second, as
+ * rk_dalton_loglik).  The marginal filter is the same without the conditioning.
+ * rk_dalton_grid_loglik: logdens (B, overwritten, one writer per element) = joint - marginal.
+ * rk_dalton_grid_solve: the joint filter's moments into out->mean_state / var_state (RK_LAYOUT_BATCH_MINOR), then rk_solve_grid's
+ * backward pass: mode = RK_MODE_MV smooths in place, RK_MODE_SIM samples into out->x_state (Philox keys as in rk_solve_sim).
+ * One route, the lanes (dalton_grid_kernels.hpp; no tile route, RK_DALTON_LANES is not read); no workspace.
+ * Served: kalman_type standard, n_bmeas = 1, n_bstate 2..6 (2..5 with three or more blocks), interrogate rodeo / schober /
+ * kramer, any built-in right-hand side or a user one with n_bmeas = 1; cfg->flags must carry RK_FLAG_BATCH_MINOR.  What is not
+ * served is refused on cfg, mode and n_bobs alone -- RK_ERR_INVALID (a non-positive size, another mode, RK_FLAG_BATCH_MINOR
+ * missing) or RK_ERR_UNSUPPORTED -- before the handle or any pointer is looked at.                                       */
+int rk_dalton_grid_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const double* obs, const double* obs_weight,
+                          const double* obs_var, const int32_t* obs_ind, int32_t n_obs, int32_t n_bobs, const rk_grid_in* g,
+                          double* logdens);
+int rk_dalton_grid_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                         const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
+                         int32_t n_obs, int32_t n_bobs, const rk_grid_in* g);
+
 /* solve_sim_draws (an addition): n_draws sample paths per trajectory from one forward filter.  Runs the forward pass of
  * rk_solve_filter (cfg must carry RK_FLAG_BATCH_MINOR; out->mean_state / var_state hold the filtered moments afterwards), then
  * one backward kernel, one lane per (chunk of draws, block, trajectory), which does the work that no draw changes -- the

@@ -99,7 +99,8 @@ static int launch_grid_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& 
     return RK_OK;
 }
 
-static int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga) {
+// (also the backward pass of rk_dalton_grid_solve, dalton_grid.hip: declared in solve_paths.hpp)
+int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga) {
     const LaunchGeom g = bwd_lane_geom(a.B, a.D);
     const bool sim = mode == RK_MODE_SIM;
     LaunchTimer t(h, sim ? "grid_bwd_sim_kernel" : "grid_bwd_mv_kernel");

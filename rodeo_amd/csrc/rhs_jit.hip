@@ -76,6 +76,8 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_EVIDENCE_SQRT      */ {"rk::evidence_sqrt_kernel<rk::UserRhsT, {P}, {I}>", "evidence_kernels.hpp", "evidence_sqrt_kernel<user>"},
     /* JIT_DYNAMIC            */ {"rk::dynamic_fwd_kernel<rk::UserRhsT, {P}, {I}>", "dynamic_kernels.hpp", "dynamic_fwd_kernel<user>"},
     /* JIT_GRID               */ {"rk::grid_fwd_kernel<rk::UserRhsT, {P}, {I}>", "grid_kernels.hpp", "grid_fwd_kernel<user>"},
+    /* JIT_DALTON_GRID        */ {"rk::dalton_grid_fwd_kernel<rk::UserRhsT, {P}, {I}, {M}, false>", "dalton_grid_kernels.hpp", "dalton_grid_fwd_kernel<loglik, user>"},
+    /* JIT_DALTON_GRID_STORE  */ {"rk::dalton_grid_fwd_kernel<rk::UserRhsT, {P}, {I}, {M}, true>", "dalton_grid_kernels.hpp", "dalton_grid_fwd_kernel<store, user>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -495,6 +497,29 @@ int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Grid
     SolveArgs args = a;
     void* params[] = {&args, (void*)&g};
     return launch_jit(h, jit_key(JIT_GRID, c->rhs_id, c), fwd_lane_geom(a.B), params);
+}
+
+// dalton_grid around a user right-hand side (dalton_grid_kernels.hpp): the configuration against the registration (n_block,
+// n_bmeas = 1; the n_bstate range is dalton_grid.hip's) and the forward launch, like dalton_grid.hip's built-in instances: the
+// log-likelihood form (joint and marginal filter in the two halves of a wave) or the joint filter's store form.  The backward
+// kernels do not depend on the right-hand side: grid.hip launches its own.
+int user_dalton_grid_check(const rk_solve_cfg* c) {
+    const UserRhs* u;
+    const int rc = user_rhs(c->rhs_id, &u);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
+               "dalton_grid: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
+    return RK_OK;
+}
+
+int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
+                     bool store, double* out) {
+    const int rc = user_dalton_grid_check(c);
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&o, (void*)&g, &out};
+    return launch_jit(h, jit_key(store ? JIT_DALTON_GRID_STORE : JIT_DALTON_GRID, c->rhs_id, c, n_bobs), dalton_lane_geom(a.B, !store),
+                      params);
 }
 
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,

@@ -59,6 +59,8 @@ enum JitKind : int {
     JIT_EVIDENCE_SQRT = 22,   // evidence_sqrt_kernel (solve_evidence, square-root form)
     JIT_DYNAMIC = 23,         // dynamic_fwd_kernel (solve_mv_dynamic / solve_sim_dynamic, the forward lanes)
     JIT_GRID = 24,            // grid_fwd_kernel (solve_mv_grid / solve_sim_grid, the forward lanes)
+    JIT_DALTON_GRID = 25,     // dalton_grid_fwd_kernel<.., false> (dalton_grid's log-likelihood)
+    JIT_DALTON_GRID_STORE = 26,  // dalton_grid_fwd_kernel<.., true> (dalton.solve_mv_grid / solve_sim_grid, the joint filter's moments)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -83,6 +85,12 @@ int user_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double 
 // solve_mv_grid / solve_sim_grid: the configuration against the registration and the forward launch (grid.hip)
 int user_grid_check(const rk_solve_cfg* c);
 int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g);
+// the backward pass on the grid (grid.hip): grid_bwd_mv_kernel / grid_bwd_sim_kernel on the batch-minor filtered moments
+int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga);
+// dalton_grid: the configuration against the registration and the forward launch (dalton_grid.hip)
+int user_dalton_grid_check(const rk_solve_cfg* c);
+int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
+                     bool store, double* out);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them

@@ -16,13 +16,16 @@ is called once per SLOT: step n joins the first earlier slot whose representativ
 opens a new one otherwise (``grid_slots``).  A ``np.linspace`` grid is one slot; a fully irregular grid costs N host calls of
 ``prior_at`` and N pairs on the device.
 
+TIMES AS NODES.  ``grid_with_times(t_grid, times)`` returns the grid with ``times`` put in as nodes and the node of every time:
+what ``rodeo_amd.inference.dalton``'s ``dalton_grid`` / ``solve_mv_grid`` / ``solve_sim_grid`` ask of the grid they are given.
+
 All of it runs on the device (``rk_solve_grid``): ``grid_fwd_kernel``, one lane per trajectory, then ``grid_bwd_mv_kernel`` or
 ``grid_bwd_sim_kernel``, one lane per (trajectory, block), on batch-minor records.
 """
 import ctypes as C
 import numpy as np
 from . import _lib
-from .solve import _KALMAN, _device_ode, _shape_rule, cached_plan
+from .solve import EVAL_AT_NODE_TOL, _KALMAN, _device_ode, _shape_rule, cached_plan
 from .inference._obs import _stack_pairs
 
 BSTATE = (2, 6)                                                     # n_bstate served
@@ -67,6 +70,49 @@ def grid_slots(t_grid):
             rep[k], slot[n] = x, k
             k += 1
     return rep[:k].copy(), slot
+
+
+def nodes_of_times(t, times):
+    """
+    The nearest node of every time and whether the time IS that node: ``(node, on)`` for a checked grid ``t`` and a 1-D float
+    array ``times`` inside it.  Time tau belongs to node k when |tau - t[k]| <= ``EVAL_AT_NODE_TOL`` times the shorter step
+    adjacent to node k -- the "is a node" rule of ``solve_mv_at`` / ``dalton_at`` with their constant.
+    """
+    k = np.clip(np.searchsorted(t, times), 1, len(t) - 1)
+    k = np.where(np.abs(times - t[k - 1]) <= np.abs(t[k] - times), k - 1, k)
+    h = np.diff(t)
+    shorter = np.minimum(np.concatenate([[np.inf], h]), np.concatenate([h, [np.inf]]))
+    return k, np.abs(times - t[k]) <= EVAL_AT_NODE_TOL * shorter[k]
+
+
+def _times(times, t, who):
+    """``times`` as a 1-D float64 array of finite times inside the checked grid ``t``, or the ValueError."""
+    try:
+        x = np.asarray(times, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: the times must be a 1-D array") from None
+    if x.ndim != 1:
+        raise ValueError(f"{who}: the times must be a 1-D array, got shape {x.shape}")
+    if not np.all(np.isfinite(x)):
+        raise ValueError(f"{who}: the times hold a non-finite time")
+    if np.any(x < t[0]) or np.any(x > t[-1]):
+        raise ValueError(f"{who}: the times must lie inside the grid [{t[0]}, {t[-1]}], got [{x.min()}, {x.max()}]")
+    return x
+
+
+def grid_with_times(t_grid, times):
+    """
+    A grid that has every one of ``times`` as a node: ``(t_new, node)`` with ``t_new`` the sorted union of ``t_grid`` and the times
+    -- a time that already is a node (within ``EVAL_AT_NODE_TOL`` of the shorter adjacent step) adds nothing -- and ``node`` the
+    index in ``t_new`` of every time, in the order given.  What ``dalton_grid`` and the two data-adaptive grid solvers of
+    ``rodeo_amd.inference.dalton`` ask of their ``t_grid``.  ValueError for a bad ``t_grid`` (``solve_mv_grid``'s rules) and for
+    times that are not 1-D, non-finite or outside [t_grid[0], t_grid[-1]].
+    """
+    t = _grid(t_grid)
+    x = _times(times, t, "grid_with_times")
+    k, on = nodes_of_times(t, x)
+    t_new = np.union1d(t, x[~on])
+    return t_new, np.searchsorted(t_new, np.where(on, t[k], x))
 
 
 def _refusals(name, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params):

@@ -7,6 +7,8 @@
   * ``solve_sim``: the same filter followed by the solver's sampler (:463-545).
   * ``dalton_at``: ``dalton`` with the observations at their own times, between grid nodes where they fall there (an
     addition; imported from this module, not re-exported by ``rodeo_amd.inference``).
+  * ``dalton_grid`` / ``solve_mv_grid`` / ``solve_sim_grid``: the three on a non-uniform grid shared by the batch, every observation
+    on a node (an addition, imported from this module like ``dalton_at``; ``rk_dalton_grid_loglik`` / ``rk_dalton_grid_solve``).
 All of it runs on the device (``rk_dalton_loglik`` / ``rk_dalton_loglik_at`` / ``rk_dalton_solve``): both filters of every parameter set in one
 kernel launch for ``dalton`` (only B doubles come back), the joint filter's moments and the solver's own backward kernels
 for ``solve_mv`` / ``solve_sim``.  At n_bstate = 3 with one observation per block and up to four blocks the filters run
@@ -31,7 +33,7 @@ import os
 import numpy as np
 from .. import _lib
 from ..solve import cached_plan
-from ._obs import _at_inputs, _at_layout, _refuse_config, _served, _stage_at  # noqa: F401  (_at_layout: importable here as before)
+from ._obs import _at_inputs, _at_layout, _refuse_config, _served, _stack_pairs, _stage_at  # noqa: F401  (_at_layout: importable here as before)
 from .logpost import obs_index
 
 _BMEAS = " (the dense / indep_init form is not served)"             # what dalton / dalton_at add to "n_bmeas = 1 only"
@@ -138,6 +140,121 @@ def dalton_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interro
     _lib.check(plan.dev.lib.rk_dalton_loglik_at(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), d_obs.ptr, d_w.ptr, d_v.ptr,
                                                 C.byref(at), int(table.shape[0]), n_bobs, out.ptr))
     return plan.per_traj(out)
+
+
+# --- DALTON on a non-uniform grid (an addition) ---------------------------------------------------
+
+def _obs_nodes(who, t, obs_times, n_obs):
+    """The node of every observation time on the checked grid ``t`` (int32, strictly increasing), or the ValueError."""
+    from ..grid import _times, nodes_of_times
+    if np.shape(obs_times) != (n_obs,):
+        raise ValueError(f"{who}: obs_times must have shape ({n_obs},), got {np.shape(obs_times)}")
+    x = _times(obs_times, t, who)
+    if np.any(np.diff(x) <= 0):
+        raise ValueError(f"{who}: obs_times must be strictly increasing")
+    node, on = nodes_of_times(t, x)
+    if not np.all(on):
+        raise ValueError(f"{who}: the observation time {float(x[~on][0])!r} is no node of t_grid (within EVAL_AT_NODE_TOL of the shorter "
+                         "adjacent step); rodeo_amd.grid_with_times(t_grid, obs_times) returns a grid that has every time as a node")
+    if np.any(np.diff(node) == 0):
+        raise ValueError(f"{who}: two observation times are the same node of t_grid (within EVAL_AT_NODE_TOL of a step)")
+    return node.astype(np.int32)
+
+
+def _on_grid(who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var,
+             kalman_type, params):
+    """
+    What the three grid calls do before their launch: ``dalton``'s refusals of the configuration and the observations
+    (``_served``), the observation times against the nodes, ``rodeo_amd.solve_mv_grid``'s refusals of the grid and ``prior_at``
+    (called once per slot) -- all before any device work -- then the cached batch-minor plan with the grid and the observations
+    staged on it.  Returns ``(plan, g, observation pointers and counts)``; the pointers are None for an empty observation set.
+    """
+    from .. import grid
+    obs, D, Om, n_bobs = _served(who, ode_weight, kalman_type, obs_data, obs_weight, obs_var, interrogate=interrogate, bmeas=_BMEAS)
+    node = _obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
+    ode, t, slot, pairs = grid._refusals(who, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
+    plan = cached_plan(ode, ode_weight, ode_init, t[0], t[-1], len(slot), interrogate, pairs[0], kalman_type, batch_minor=True,
+                       **params)
+    (q, r), batched = _stack_pairs(pairs, plan.B)
+    d_t, d_slot, d_q, d_r = plan.staged("grid", t, slot, q, r)
+    g = _lib.GridIn(t=d_t.ptr, slot=d_slot.ptr, q=d_q.ptr, r=d_r.ptr, q_batched=batched, r_batched=batched, n_slots=len(pairs))
+    ptrs = (None,) * 4
+    if len(node):
+        ptrs = tuple(a.ptr for a in plan.staged("dalton_grid", obs, D, Om, node))
+    return plan, g, ptrs + (len(node), n_bobs)
+
+
+def dalton_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", **params):
+    """
+    ``dalton`` on a non-uniform grid shared by the batch (an addition): log p(Y | Z) = joint - marginal, a float, or an array
+    (B,) for batched inputs.  ``t_grid`` (N+1,), ``prior_at(dt)`` (called once per slot of ``grid_slots(t_grid)``) and the batching
+    of what it returns are ``rodeo_amd.solve_mv_grid``'s; the observation arguments, n_bobs = 1 .. 3 and what is served
+    (kalman_type "standard", n_bmeas = 1, n_bstate 2 .. 6, 2 .. 5 with three or more blocks, rodeo / schober / kramer) are
+    ``dalton``'s.
+
+    EVERY OBSERVATION TIME MUST BE A NODE: time tau belongs to node k when |tau - t[k]| <= ``EVAL_AT_NODE_TOL`` times the shorter
+    adjacent step.  ``rodeo_amd.grid_with_times(t_grid, obs_times)`` returns the grid with the times put in.  Unlike
+    ``dalton_at``, the solver then interrogates the ODE at the observation times as well.  ValueError before any device work: a
+    time that is no node, times not strictly increasing, two times on one node, a non-finite time, a time outside
+    [t[0], t[-1]], and what ``solve_mv_grid`` and ``dalton`` refuse.
+
+    Step n -> n + 1 of the joint filter: the prediction with the step's own prior pair, the interrogation at t[n+1], the z
+    forecast log-density and update, then the conditioning on y if node n + 1 is observed (z first, y second, like ``dalton``);
+    the marginal filter is the same without y.  An observation on node 0 adds log p(y_0 | x_0) to the joint density and does not
+    update x_0.  An empty observation set gives 0.0.
+
+    THE 1e-8 RULE.  Like ``dalton`` (utils.py:60-78 of the reference), a forecast whose variance s has |s| <= 1e-8 adds nothing
+    to the log-density.  On a non-uniform grid the forecast variances of one run can lie on both sides of it, and a step can be
+    kept in one filter and dropped in the other: the value then jumps.  With short steps and a small prior scale (n_bstate >= 4
+    in particular) look at the scale of sigma before trusting a value.
+    """
+    if (getattr(ode_fun, "rhs_id", None) == _lib.RHS_FITZHUGH_NAGUMO and np.shape(ode_weight)[-1:] == (4,)
+            and np.shape(obs_weight)[2:3] == (3,)):                 # (dalton_grid.hip: dalton_grid_ships)
+        raise NotImplementedError("dalton_grid on the device: fitzhugh_nagumo at n_bstate = 4 with n_bobs = 3 is left out (its "
+                                  "kernel needs more scratch than dalton's and solve_mv_grid's); the two grid solvers serve it")
+    plan, g, (p_obs, p_w, p_v, p_ind, n_obs, n_bobs) = _on_grid(
+        "dalton_grid", ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var,
+        kalman_type, params)
+    plan.set_seed(key)
+    out = plan.dev.empty((plan.B,))
+    _lib.check(plan.dev.lib.rk_dalton_grid_loglik(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), p_obs, p_w, p_v, p_ind, n_obs,
+                                                  n_bobs, C.byref(g), out.ptr))
+    return plan.per_traj(out)
+
+
+def _solve_grid(who, mode, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight,
+                obs_var, kalman_type, params):
+    """The joint filter on the grid + ``rk_solve_grid``'s backward pass for `mode`; with no observations the plain grid solver."""
+    plan, g, (p_obs, p_w, p_v, p_ind, n_obs, n_bobs) = _on_grid(
+        who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var, kalman_type,
+        params)
+    if n_obs == 0:                                                  # p(X | Z): rodeo_amd.solve_mv_grid / solve_sim_grid itself
+        plan.launch(plan.dev.lib.rk_solve_grid, key, mode, mode, C.byref(g))
+    else:
+        plan.launch(plan.dev.lib.rk_dalton_grid_solve, key, mode, mode, p_obs, p_w, p_v, p_ind, n_obs, n_bobs, C.byref(g))
+    if plan.layout != _lib.LAYOUT_BATCH_MINOR:
+        raise RuntimeError(f"{who}: the plan reports layout {plan.layout}, not the batch-minor records")
+    return plan
+
+
+def solve_mv_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                  obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", **params):
+    """Mean and variance of p(X | Z, Y) on the nodes ``t_grid`` (an addition): ``(mean (N+1, d, p), var (N+1, d, p, p))`` with a
+    leading batch axis for batched inputs -- ``dalton_grid``'s joint filter, then ``rodeo_amd.solve_mv_grid``'s smoothing pass
+    with every step's own prior pair.  Arguments, the node rule and the refusals are ``dalton_grid``'s; with an empty
+    observation set the result is ``rodeo_amd.solve_mv_grid``'s."""
+    return _solve_grid("dalton.solve_mv_grid", _lib.MODE_MV, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                       obs_data, obs_times, obs_weight, obs_var, kalman_type, params).state_host()
+
+
+def solve_sim_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                   obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", **params):
+    """One draw from p(X | Z, Y) on the nodes ``t_grid`` (an addition): ``x (N+1, d, p)`` [+ a leading batch axis];
+    ``dalton_grid``'s joint filter, then ``rodeo_amd.solve_sim_grid``'s sampler (``key`` seeds ``solve_sim``'s Philox stream,
+    keyed by trajectory, step and block; ``x[0]`` is ``ode_init``).  Arguments and refusals are ``dalton_grid``'s."""
+    return _solve_grid("dalton.solve_sim_grid", _lib.MODE_SIM, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                       obs_data, obs_times, obs_weight, obs_var, kalman_type, params).x_host()
 
 
 # --- non-Gaussian observations (src/rodeo/inference/dalton.py:547-1039) -------------------------------------------------
