@@ -387,6 +387,28 @@ int rk_dalton_grid_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in
                          const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
                          int32_t n_obs, int32_t n_bobs, const rk_grid_in* g);
 
+/* fenrir_grid (an addition): rk_fenrir_backward / rk_fenrir_solve_mv on rk_solve_grid's non-uniform grid, every observation on a
+ * node.  Both entries run the forward pass of rk_solve_grid themselves (grid_fwd_kernel: out->mean_state / var_state receive
+ * the batch-minor filtered moments; Fenrir's forward pass is free of data), then the backward Markov-chain filter with every
+ * step's own pair (fenrir_grid.hip): the carry starts at filt[N]; for n = N-1 .. 0 the prediction of node n + 1 is re-evaluated
+ * from filt[n] with (q, r)[slot[n]], the chain steps with that q as its transition matrix, and the step conditions on y where
+ * node n is observed -- node 0 like any other.  obs / obs_weight / obs_var as for rk_fenrir_backward (n_bobs = 1..3); obs_node
+ * (n_obs) holds the NODE of every observation, strictly increasing in 0..n_steps; n_obs = 0 needs no observation arrays.
+ * rk_fenrir_grid_loglik: logdens (B, overwritten) = log p(Y | Z).  No atomics: with several blocks every lane writes its block's
+ * sum to the handle's scratch and a trajectory's sums are added in block order, so two calls give the same bits.
+ * rk_fenrir_grid_solve_mv: the backward filter's moments go to `workspace` (rk_fenrir_workspace_bytes, the same item), then
+ * rk_fenrir_solve_mv's smoothing sweep overwrites out->mean_state / var_state with mean and variance of p(X | Z, Y).
+ * Served: kalman_type standard, n_bmeas = 1, n_bstate 2..6 (2..5 with three or more blocks), the four interrogations, any
+ * built-in right-hand side or a user one with n_bmeas = 1; cfg->flags must carry RK_FLAG_BATCH_MINOR and not RK_FLAG_STORE_PRED.
+ * What is not served is refused on cfg and n_bobs alone -- RK_ERR_INVALID (a non-positive size, RK_FLAG_BATCH_MINOR missing) or
+ * RK_ERR_UNSUPPORTED -- before the handle or any pointer is looked at.                                                      */
+int rk_fenrir_grid_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
+                          const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
+                          const rk_grid_in* g, double* logdens);
+int rk_fenrir_grid_solve_mv(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
+                            const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
+                            const rk_grid_in* g, void* workspace);
+
 /* solve_sim_draws (an addition): n_draws sample paths per trajectory from one forward filter.  Runs the forward pass of
  * rk_solve_filter (cfg must carry RK_FLAG_BATCH_MINOR; out->mean_state / var_state hold the filtered moments afterwards), then
  * one backward kernel, one lane per (chunk of draws, block, trajectory), which does the work that no draw changes -- the

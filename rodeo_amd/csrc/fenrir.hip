@@ -193,6 +193,12 @@ static int launch_fenrir_smooth(rk_handle h, const rk_solve_cfg* c, const SolveA
     return RK_OK;
 }
 
+// the sweep on the lane route's n_bstate 2 .. 6 (also the last launch of rk_fenrir_grid_solve_mv, fenrir_grid.hip: declared in
+// solve_paths.hpp)
+int launch_fenrir_smooth_lanes(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* states) {
+    return launch_fenrir_smooth<2, 6>(h, c, a, states);
+}
+
 // what every route does once its arguments are accepted: the kernels' argument block, the device, and (logdens given) the
 // zeroed per-trajectory sums that the lanes of a trajectory's blocks add to
 static int fenrir_begin(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, double* logdens,

@@ -99,6 +99,20 @@ static int launch_grid_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& 
     return RK_OK;
 }
 
+// the forward pass for a built-in or a user right-hand side (also that of rk_fenrir_grid_*, fenrir_grid.hip: declared in
+// solve_paths.hpp)
+int launch_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga) {
+    if (is_user_rhs(c->rhs_id)) return user_grid(h, c, a, ga);
+    int rc = RK_ERR_UNSUPPORTED;
+    with_builtin_rhs(c->rhs_id, [&](auto rhs) {
+        using RHS = decltype(rhs);
+        rc = check_n_theta<RHS>(c, a);
+        if (rc) return;
+        rc = launch_grid_fwd<RHS>(h, c, a, ga);
+    });
+    return rc;
+}
+
 // (also the backward pass of rk_dalton_grid_solve, dalton_grid.hip: declared in solve_paths.hpp)
 int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga) {
     const LaunchGeom g = bwd_lane_geom(a.B, a.D);
@@ -137,17 +151,7 @@ int rk_solve_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, con
     SolveArgs a;
     make_args(c, in, out, a);
     const GridArgs ga{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
-    if (is_user_rhs(c->rhs_id)) {
-        rc = user_grid(h, c, a, ga);
-    } else {
-        rc = RK_ERR_UNSUPPORTED;
-        with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-            using RHS = decltype(rhs);
-            rc = check_n_theta<RHS>(c, a);
-            if (rc) return;
-            rc = launch_grid_fwd<RHS>(h, c, a, ga);
-        });
-    }
+    rc = launch_grid_forward(h, c, a, ga);
     if (rc) return rc;
     return launch_grid_bwd(h, c, a, mode, ga);
 }

@@ -32,7 +32,8 @@ static int magi_check(const rk_magi_cfg* c, const rk_magi_in* in) {
 }
 
 // The handle's grow-only device scratch (shared with the large-block operators, solve_dense_ops.hpp), at least `need` bytes.
-static int magi_scratch(rk_handle h, size_t need, double** p) {
+// (also where rk_fenrir_grid_loglik keeps its block sums, fenrir_grid.hip: declared in solve_paths.hpp)
+int lane_scratch(rk_handle h, size_t need, double** p) {
     if (h->op_scratch_bytes < need) {
         if (h->op_scratch) {
             RK_HIP(hipStreamSynchronize(h->stream));
@@ -44,6 +45,16 @@ static int magi_scratch(rk_handle h, size_t need, double** p) {
         h->op_scratch_bytes = need;
     }
     *p = (double*)h->op_scratch;
+    return RK_OK;
+}
+
+// logdens[b] = the D block sums part[blk * B + b] of trajectory b, added in block order (magi_sum_kernel; declared in
+// solve_paths.hpp like lane_scratch)
+int launch_block_sum(rk_handle h, const double* part, int B, int D, double* logdens) {
+    LaunchTimer t(h, "magi_sum_kernel");
+    hipLaunchKernelGGL(magi_sum_kernel, dim3(div_up(B, 256)), dim3(256), 0, h->stream, part, B, D, logdens);
+    t.stop();
+    RK_HIP(hipGetLastError());
     return RK_OK;
 }
 
@@ -66,7 +77,7 @@ int rk_magi_logdens(rk_handle h, const rk_magi_cfg* c, const rk_magi_in* in, dou
     if (brc) return brc;
     double* part = logdens;
     if (a.D > 1) {
-        const int src = magi_scratch(h, sizeof(double) * (size_t)a.B * (size_t)a.D, &part);
+        const int src = lane_scratch(h, sizeof(double) * (size_t)a.B * (size_t)a.D, &part);
         if (src) return src;
     }
     const dim3 grid(div_up(a.B, 64) * a.D), block(64);
@@ -93,12 +104,7 @@ int rk_magi_logdens(rk_handle h, const rk_magi_cfg* c, const rk_magi_in* in, dou
     }
     RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "magi: no kernel for n_bstate %d, n_active %d", c->n_bstate, c->n_active);
     RK_HIP(hipGetLastError());
-    if (a.D > 1) {
-        LaunchTimer t(h, "magi_sum_kernel");
-        hipLaunchKernelGGL(magi_sum_kernel, dim3(div_up(a.B, 256)), dim3(256), 0, h->stream, part, a.B, a.D, logdens);
-        t.stop();
-        RK_HIP(hipGetLastError());
-    }
+    if (a.D > 1) return launch_block_sum(h, part, a.B, a.D, logdens);
     return RK_OK;
 }
 

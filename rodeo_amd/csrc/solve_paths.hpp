@@ -87,6 +87,8 @@ int user_grid_check(const rk_solve_cfg* c);
 int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g);
 // the backward pass on the grid (grid.hip): grid_bwd_mv_kernel / grid_bwd_sim_kernel on the batch-minor filtered moments
 int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga);
+// the forward pass on the grid (grid.hip): grid_fwd_kernel for a built-in or a user right-hand side
+int launch_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga);
 // dalton_grid: the configuration against the registration and the forward launch (dalton_grid.hip)
 int user_dalton_grid_check(const rk_solve_cfg* c);
 int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
@@ -110,6 +112,15 @@ size_t sqrt_ws_doubles(const rk_solve_cfg* c, int mode);
 size_t fenrir_sqrt_item_doubles(int p);
 int fenrir_sqrt_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* obs, const double* obs_w,
                        const double* obs_v, const int32_t* obs_ind, int n_obs, int n_bobs, double* logdens, double* states);
+
+// fenrir's smoothing sweep over a stored backward filter on the lanes, n_bstate 2 .. 6 (fenrir.hip: fenrir_smooth_kernel)
+int launch_fenrir_smooth_lanes(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const double* states);
+
+// ---- per-block sums without atomics (magi.hip) ------------------------------------------------------------------------
+// the handle's grow-only device scratch, at least `need` bytes, and logdens[b] = sum over blocks of part[blk * B + b] in block
+// order (magi_sum_kernel)
+int lane_scratch(rk_handle h, size_t need, double** p);
+int launch_block_sum(rk_handle h, const double* part, int B, int D, double* logdens);
 
 // ---- MFMA-tile paths: n_bstate = 3 (solve_tile3.hip), 4 (solve_tile4.hip), blocked 4 .. 8 (solve_tilen.hip) ----------
 bool tile3_supported(const rk_solve_cfg* c, int mode);

@@ -5,7 +5,7 @@ times sit on the grid, the sub-step priors they need, and the ``rk_dalton_at_in`
 """
 import numpy as np
 from .. import _lib
-from ..solve import check_prior_at, eval_at_nodes, _device_ode, _interrogate_id, _prior_at_pair, _shape_rule
+from ..solve import cached_plan, check_prior_at, eval_at_nodes, _device_ode, _interrogate_id, _prior_at_pair, _shape_rule
 
 
 def _check_obs(obs_data, obs_weight, obs_var):
@@ -117,6 +117,24 @@ def _stack_pairs(pairs, B, force=0):
         else:
             out.append(np.ascontiguousarray(np.array(mats)))
     return tuple(out), batched
+
+
+def _grid_plan(obs_slot, ode, ode_weight, ode_init, t, slot, pairs, interrogate, kalman_type, params, obs, D, Om, node, n_bobs):
+    """
+    What the likelihoods on a non-uniform grid (``dalton_grid``, ``fenrir_grid`` and their solvers) do once nothing is left to
+    refuse: the cached batch-minor plan (its own prior pair is slot 0's) with the grid ``(t, slot, pairs)`` of ``grid._refusals``
+    staged in ``rodeo_amd.solve_mv_grid``'s slot and the observations on the nodes ``node`` in ``obs_slot``.  Returns ``(plan, g,
+    observation pointers and counts)``; the pointers are None for an empty observation set.
+    """
+    plan = cached_plan(ode, ode_weight, ode_init, t[0], t[-1], len(slot), interrogate, pairs[0], kalman_type, batch_minor=True,
+                       **params)
+    (q, r), batched = _stack_pairs(pairs, plan.B)
+    d_t, d_slot, d_q, d_r = plan.staged("grid", t, slot, q, r)
+    g = _lib.GridIn(t=d_t.ptr, slot=d_slot.ptr, q=d_q.ptr, r=d_r.ptr, q_batched=batched, r_batched=batched, n_slots=len(pairs))
+    ptrs = (None,) * 4
+    if len(node):
+        ptrs = tuple(a.ptr for a in plan.staged(obs_slot, obs, D, Om, node))
+    return plan, g, ptrs + (len(node), n_bobs)
 
 
 def _at_inputs(who, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, prior_pars, n_obs, obs_times, prior_at, params):

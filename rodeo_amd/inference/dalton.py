@@ -33,7 +33,7 @@ import os
 import numpy as np
 from .. import _lib
 from ..solve import cached_plan
-from ._obs import _at_inputs, _at_layout, _refuse_config, _served, _stack_pairs, _stage_at  # noqa: F401  (_at_layout: importable here as before)
+from ._obs import _at_inputs, _at_layout, _grid_plan, _refuse_config, _served, _stack_pairs, _stage_at  # noqa: F401  (_at_layout, _stack_pairs: importable here as before)
 from .logpost import obs_index
 
 _BMEAS = " (the dense / indep_init form is not served)"             # what dalton / dalton_at add to "n_bmeas = 1 only"
@@ -173,15 +173,8 @@ def _on_grid(who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, 
     obs, D, Om, n_bobs = _served(who, ode_weight, kalman_type, obs_data, obs_weight, obs_var, interrogate=interrogate, bmeas=_BMEAS)
     node = _obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
     ode, t, slot, pairs = grid._refusals(who, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
-    plan = cached_plan(ode, ode_weight, ode_init, t[0], t[-1], len(slot), interrogate, pairs[0], kalman_type, batch_minor=True,
-                       **params)
-    (q, r), batched = _stack_pairs(pairs, plan.B)
-    d_t, d_slot, d_q, d_r = plan.staged("grid", t, slot, q, r)
-    g = _lib.GridIn(t=d_t.ptr, slot=d_slot.ptr, q=d_q.ptr, r=d_r.ptr, q_batched=batched, r_batched=batched, n_slots=len(pairs))
-    ptrs = (None,) * 4
-    if len(node):
-        ptrs = tuple(a.ptr for a in plan.staged("dalton_grid", obs, D, Om, node))
-    return plan, g, ptrs + (len(node), n_bobs)
+    return _grid_plan("dalton_grid", ode, ode_weight, ode_init, t, slot, pairs, interrogate, kalman_type, params, obs, D, Om, node,
+                      n_bobs)
 
 
 def dalton_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,

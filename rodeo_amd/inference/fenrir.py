@@ -16,13 +16,16 @@ factor before the log-density sees it (square_root.py:343-344), so the value is 
 form for ``L L^T`` inputs (tests).  Lane-per-trajectory kernels (``fenrir_sqrt.hip``), n_bstate 2 .. 8.
 ``fenrir_at`` (an addition; imported from this module, not re-exported by ``rodeo_amd.inference``): ``fenrir`` with the
 observations at their own times, between grid nodes where they fall there (``rk_fenrir_backward_at``).
+``fenrir_grid`` / ``solve_mv_grid`` (an addition, imported from this module like ``fenrir_at``): the likelihood and the
+data-adaptive solver on a non-uniform grid shared by the batch, every observation on a node (``rk_fenrir_grid_loglik`` /
+``rk_fenrir_grid_solve_mv``).
 """
 import ctypes as C
 import os
 import numpy as np
 from .. import _lib
 from ..solve import SolvePlan, cached_plan
-from ._obs import _at_inputs, _check_obs, _served, _stage_at
+from ._obs import _at_inputs, _check_obs, _grid_plan, _served, _stage_at
 from .logpost import obs_index
 
 
@@ -121,6 +124,93 @@ def fenrir_at(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interro
     _lib.check(dev.lib.rk_fenrir_backward_at(dev.h, C.byref(plan.cfg), C.byref(plan.inp), C.byref(plan._out), d_obs.ptr, d_w.ptr,
                                              d_v.ptr, C.byref(at), int(table.shape[0]), n_bobs, ws.ptr, out.ptr))
     return plan.per_traj(out)
+
+
+# --- Fenrir on a non-uniform grid (an addition) ---------------------------------------------------
+
+def _on_grid(who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var,
+             kalman_type, params):
+    """
+    What the two grid calls do before their launch: ``_check_obs``'s shape errors, the observation times against the nodes
+    (``dalton_grid``'s rule), ``rodeo_amd.solve_mv_grid``'s refusals of the configuration, the grid and ``prior_at`` (called once
+    per slot) -- all before any device work -- then the cached batch-minor plan with the grid staged in ``solve_mv_grid``'s slot
+    and the observations in their own.  Returns ``(plan, g, observation pointers and counts)``; the pointers are None for an
+    empty observation set.
+    """
+    from .. import grid
+    from .dalton import _obs_nodes
+    obs, D, Om, n_bobs = _check_obs(obs_data, obs_weight, obs_var)
+    node = _obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
+    ode, t, slot, pairs = grid._refusals(who, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
+    d, p = (int(n) for n in (np.shape(ode_weight)[-3], np.shape(ode_weight)[-1]))
+    if D.shape[1:] != (d, n_bobs, p):
+        raise ValueError(f"obs_weight must have shape (n_obs, {d}, n_bobs, {p})")
+    return _grid_plan("fenrir_grid", ode, ode_weight, ode_init, t, slot, pairs, interrogate, kalman_type, params, obs, D, Om, node,
+                      n_bobs)
+
+
+def fenrir_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", **params):
+    """
+    ``fenrir`` on a non-uniform grid shared by the batch (an addition): log p(Y | Z), a float, or an array (B,) for batched
+    inputs.  ``t_grid`` (N+1,), ``prior_at(dt)`` (called once per slot of ``grid_slots(t_grid)``) and the batching of what it
+    returns are ``rodeo_amd.solve_mv_grid``'s; the observation arguments and n_bobs = 1 .. 3 are ``fenrir``'s.  Imported from
+    this module, not re-exported by ``rodeo_amd.inference``.
+
+    EVERY OBSERVATION TIME MUST BE A NODE, by ``dalton_grid``'s rule: time tau belongs to node k when |tau - t[k]| <=
+    ``EVAL_AT_NODE_TOL`` times the shorter adjacent step.  ``rodeo_amd.grid_with_times(t_grid, obs_times)`` returns the grid with
+    the times put in.  Unlike ``fenrir_at``, the solver then interrogates the ODE at the observation times as well, and every
+    observation has a record: ``solve_mv_grid`` smooths through it.
+
+    The forward pass is ``solve_mv_grid``'s (Fenrir's is free of data).  Backwards the carry starts at the filtered moments of
+    node N; for n = N-1 .. 0 the prediction of node n + 1 is re-evaluated from the filtered moments of node n with the prior pair
+    of step n, the Markov chain steps with that pair's transition matrix, and the step conditions on y where node n is
+    observed -- node 0 like any other (``dalton_grid`` only adds a density there).  An empty observation set gives 0.0.
+
+    Served: ``kalman_type="standard"``, n_bmeas = 1, n_bstate 2 .. 6 (2 .. 5 with three or more blocks), the four
+    interrogations (``interrogate_chkrebtii`` with an integer ``key``), built-in and plain-Python right-hand sides.  Refused
+    before any device work: what ``solve_mv_grid`` refuses (``"square-root"``: NotImplementedError, not built), the node errors
+    (ValueError) and ``fenrir``'s shape errors.  The block sums of a trajectory are added in block order: two calls give the
+    same bits.
+    """
+    plan, g, (p_obs, p_w, p_v, p_node, n_obs, n_bobs) = _on_grid(
+        "fenrir_grid", ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var,
+        kalman_type, params)
+    out = plan.dev.empty((plan.B,))
+    plan.launch(plan.dev.lib.rk_fenrir_grid_loglik, key, _lib.MODE_FILTER, p_obs, p_w, p_v, p_node, n_obs, n_bobs, C.byref(g),
+                out.ptr)
+    return plan.per_traj(out)
+
+
+def solve_mv_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                  obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", **params):
+    """
+    Fenrir's data-adaptive solver on the nodes ``t_grid`` (an addition): mean and variance of p(X | Z, Y), ``(mean (N+1, d, p),
+    var (N+1, d, p, p))`` with a leading batch axis for batched inputs -- ``fenrir_grid``'s backward filter with its moments
+    kept, then ``solve_mv``'s smoothing sweep over them (nodes 0 and 1 keep the backward filter's own estimates).  Arguments, the
+    node rule and the refusals are ``fenrir_grid``'s; with an empty observation set the backward filter never conditions and
+    the result is the posterior of ``rodeo_amd.solve_mv_grid`` reached by another recursion.  The sweep inverts the backward
+    filter's predicted variances: with ``interrogate_kramer`` / ``interrogate_schober`` (an exact measurement) these can be
+    singular, as in ``solve_mv``.
+    """
+    return _solve_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var,
+                       kalman_type, params).state_host()
+
+
+def _solve_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var,
+                kalman_type, params):
+    """``solve_mv_grid`` up to the download: the plan whose batch-minor records hold the smoothed moments."""
+    plan, g, (p_obs, p_w, p_v, p_node, n_obs, n_bobs) = _on_grid(
+        "fenrir.solve_mv_grid", ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight,
+        obs_var, kalman_type, params)
+    nbytes = C.c_size_t(0)
+    _lib.check(plan.dev.lib.rk_fenrir_workspace_bytes(C.byref(plan.cfg), C.byref(nbytes)))
+    ws = plan.dev.empty((nbytes.value // 8,))                       # the stored backward filter: released on return
+    plan.launch(plan.dev.lib.rk_fenrir_grid_solve_mv, key, _lib.MODE_MV, p_obs, p_w, p_v, p_node, n_obs, n_bobs, C.byref(g), ws.ptr)
+    if plan.layout != _lib.LAYOUT_BATCH_MINOR:
+        raise RuntimeError(f"fenrir.solve_mv_grid: the plan reports layout {plan.layout}, not the batch-minor records")
+    plan.sync()                                                     # (the sweep has read the workspace before it is released)
+    return plan
 
 
 def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
