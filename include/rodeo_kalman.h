@@ -366,6 +366,30 @@ typedef struct {
 int rk_solve_grid(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
                   const rk_grid_in* g);
 
+/* solve_evidence_grid / solve_mv_dynamic_grid / solve_sim_dynamic_grid (an addition): rk_solve_evidence and rk_solve_dynamic on
+ * rk_solve_grid's non-uniform grid, i.e. the calibration of the prior scale on the grid the solver runs on.  Step n -> n + 1
+ * takes the pair (q, r)[slot[n]] in place of in->prior_weight / prior_var and interrogates at t[n+1]; cfg->t_min / t_max are
+ * not read.
+ * rk_solve_evidence_grid: rk_solve_evidence's sums with every step's own pair -- quad_b = sum_n z^2 / s, logdet_b = sum_n log s
+ * (the plain Gaussian density, no threshold on s) and logdens = -1/2 sum_b (quad_b + logdet_b) - n_block n_steps log(2 pi) / 2.
+ * The scale law holds when every r of block b becomes c_b r.  Outputs as rk_solve_evidence's: logdens (n_traj); quad, logdet
+ * (n_block, n_traj) batch-minor.  One kernel (grid_evidence_kernel), nothing stored per step.
+ * rk_solve_dynamic_grid: rk_solve_dynamic's step with the step's own pair -- mu- = q mu, P = q Sigma q^T,
+ * c = max(z^2 / (W~ r W~^T), scale_min), Sigma- = P + c r, var_meas from this Sigma- (rodeo) -- and its backward passes with
+ * Sigma-_{n+1} re-evaluated as q_n Sigma_f[n] q_n^T + scale[n] r_n and the gain from q_n; mode, out, scale (n_steps, n_block,
+ * n_traj) and logdens (n_traj) as for rk_solve_dynamic (Philox keys as in rk_solve_sim).  scale[n] multiplies r_n, which
+ * already carries the step's length.
+ * Both: all records are RK_LAYOUT_BATCH_MINOR and cfg->flags must carry RK_FLAG_BATCH_MINOR; each output element has one
+ * writer, no atomics, no workspace.  Served: kalman_type standard, n_bmeas = 1, interrogate rodeo / schober / kramer, any
+ * built-in right-hand side or a user one with n_bmeas = 1; n_bstate 2..6 (2..5 with three or more blocks) for the evidence and
+ * 2..5 (2..4) for the dynamic solver.  What is not served is refused on cfg (and mode, scale_min) alone -- RK_ERR_INVALID (a
+ * non-positive size, another mode, a negative or non-finite scale_min, RK_FLAG_BATCH_MINOR missing) or RK_ERR_UNSUPPORTED --
+ * before the handle or any pointer is looked at.                                                                           */
+int rk_solve_evidence_grid(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_grid_in* g, double* logdens,
+                           double* quad, double* logdet);
+int rk_solve_dynamic_grid(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                          const rk_grid_in* g, double scale_min, double* scale, double* logdens);
+
 /* dalton_grid (an addition): rk_dalton_loglik / rk_dalton_solve on rk_solve_grid's non-uniform grid, every observation on a node.
  * obs / obs_weight / obs_var as for rk_dalton_loglik (n_bobs = 1..3); obs_ind (n_obs) holds the NODE of every observation,
  * strictly increasing in 0..n_steps: node 0 enters the joint density only and does not update x_0, a node above n_steps never

@@ -15,6 +15,7 @@ from .solve import solve_sim, solve_mv, solve_mv_at, SolvePlan
 from .evidence import solve_evidence, evidence_scale, evidence_at, Evidence
 from .dynamic import solve_mv_dynamic, solve_sim_dynamic, DynamicMV, DynamicSim
 from .grid import solve_mv_grid, solve_sim_grid, grid_slots, grid_with_times
+from .grid_calib import solve_evidence_grid, solve_mv_dynamic_grid, solve_sim_dynamic_grid
 from .draws import solve_sim_draws
 from .prior.ibm import ibm_init
 from .prior.indep_init import indep_init

@@ -141,6 +141,8 @@ SIGNATURES = {
     "rk_solve_evidence": (C.c_int, [_H, _P, _P, _P, _P, _P]),
     "rk_solve_dynamic": (C.c_int, [_H, _P, _P, _P, _I, _D, _P, _P]),
     "rk_solve_grid": (C.c_int, [_H, _P, _P, _P, _I, C.POINTER(GridIn)]),
+    "rk_solve_evidence_grid": (C.c_int, [_H, _P, _P, C.POINTER(GridIn), _P, _P, _P]),
+    "rk_solve_dynamic_grid": (C.c_int, [_H, _P, _P, _P, _I, C.POINTER(GridIn), _D, _P, _P]),
     "rk_dalton_grid_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _P]),
     "rk_dalton_grid_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn)]),
     "rk_fenrir_grid_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _P]),

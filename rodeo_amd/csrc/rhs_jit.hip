@@ -78,6 +78,8 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_GRID               */ {"rk::grid_fwd_kernel<rk::UserRhsT, {P}, {I}>", "grid_kernels.hpp", "grid_fwd_kernel<user>"},
     /* JIT_DALTON_GRID        */ {"rk::dalton_grid_fwd_kernel<rk::UserRhsT, {P}, {I}, {M}, false>", "dalton_grid_kernels.hpp", "dalton_grid_fwd_kernel<loglik, user>"},
     /* JIT_DALTON_GRID_STORE  */ {"rk::dalton_grid_fwd_kernel<rk::UserRhsT, {P}, {I}, {M}, true>", "dalton_grid_kernels.hpp", "dalton_grid_fwd_kernel<store, user>"},
+    /* JIT_GRID_EVIDENCE      */ {"rk::grid_evidence_kernel<rk::UserRhsT, {P}, {I}>", "grid_calib_kernels.hpp", "grid_evidence_kernel<user>"},
+    /* JIT_GRID_DYNAMIC       */ {"rk::grid_dynamic_fwd_kernel<rk::UserRhsT, {P}, {I}>", "grid_calib_kernels.hpp", "grid_dynamic_fwd_kernel<user>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -497,6 +499,37 @@ int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Grid
     SolveArgs args = a;
     void* params[] = {&args, (void*)&g};
     return launch_jit(h, jit_key(JIT_GRID, c->rhs_id, c), fwd_lane_geom(a.B), params);
+}
+
+// solve_evidence_grid / solve_mv_dynamic_grid / solve_sim_dynamic_grid around a user right-hand side (grid_calib_kernels.hpp):
+// the configuration against the registration (n_block, n_bmeas = 1; the n_bstate ranges are grid_calib.hip's) and the forward
+// launches, like grid_calib.hip's built-in instances.  The backward kernels do not depend on the right-hand side:
+// grid_calib.hip launches its own.
+int user_grid_calib_check(const rk_solve_cfg* c, const char* who) {
+    const UserRhs* u;
+    const int rc = user_rhs(c->rhs_id, &u);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
+               "%s: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", who, c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
+    return RK_OK;
+}
+
+int user_grid_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double* logdens, double* quad,
+                       double* logdet) {
+    const int rc = user_grid_calib_check(c, "evidence_grid");
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&g, &logdens, &quad, &logdet};
+    return launch_jit(h, jit_key(JIT_GRID_EVIDENCE, c->rhs_id, c), fwd_lane_geom(a.B), params);
+}
+
+int user_grid_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double scale_min, double* scale,
+                      double* logdens) {
+    const int rc = user_grid_calib_check(c, "dynamic_grid");
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&g, &scale_min, &scale, &logdens};
+    return launch_jit(h, jit_key(JIT_GRID_DYNAMIC, c->rhs_id, c), fwd_lane_geom(a.B), params);
 }
 
 // dalton_grid around a user right-hand side (dalton_grid_kernels.hpp): the configuration against the registration (n_block,

@@ -61,6 +61,8 @@ enum JitKind : int {
     JIT_GRID = 24,            // grid_fwd_kernel (solve_mv_grid / solve_sim_grid, the forward lanes)
     JIT_DALTON_GRID = 25,     // dalton_grid_fwd_kernel<.., false> (dalton_grid's log-likelihood)
     JIT_DALTON_GRID_STORE = 26,  // dalton_grid_fwd_kernel<.., true> (dalton.solve_mv_grid / solve_sim_grid, the joint filter's moments)
+    JIT_GRID_EVIDENCE = 27,   // grid_evidence_kernel (solve_evidence_grid)
+    JIT_GRID_DYNAMIC = 28,    // grid_dynamic_fwd_kernel (solve_mv_dynamic_grid / solve_sim_dynamic_grid, the forward lanes)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -89,6 +91,13 @@ int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Grid
 int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga);
 // the forward pass on the grid (grid.hip): grid_fwd_kernel for a built-in or a user right-hand side
 int launch_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga);
+// solve_evidence_grid / solve_mv_dynamic_grid / solve_sim_dynamic_grid: the configuration against the registration (`who` names
+// the entry in the message) and the forward launches (grid_calib.hip)
+int user_grid_calib_check(const rk_solve_cfg* c, const char* who);
+int user_grid_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double* logdens, double* quad,
+                       double* logdet);
+int user_grid_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double scale_min, double* scale,
+                      double* logdens);
 // dalton_grid: the configuration against the registration and the forward launch (dalton_grid.hip)
 int user_dalton_grid_check(const rk_solve_cfg* c);
 int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
