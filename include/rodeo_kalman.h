@@ -455,6 +455,28 @@ int rk_solve_sim_draws(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* 
                        const int32_t* keep, int32_t n_keep, double* x_draws);
 int rk_sim_draws_chunk(void);
 
+/* solve_sim_draws_grid / dalton.solve_sim_draws_grid (an addition): rk_solve_sim_draws on rk_solve_grid's non-uniform grid, from
+ * the solver's forward filter (p(X | Z)) or from dalton_grid's joint filter (p(X | Z, Y)).
+ * rk_solve_sim_draws_grid runs the forward pass of rk_solve_grid (grid_fwd_kernel), rk_dalton_grid_sim_draws the store form of
+ * rk_dalton_grid_solve's joint filter (obs .. n_bobs as there: obs_ind holds the NODE of every observation); out->mean_state /
+ * var_state hold the filtered moments afterwards.  Then one backward kernel (grid_bwd_sim_draws_kernel), one lane per (chunk of
+ * draws, block, trajectory): rk_solve_sim_draws's, with the pair (q, r)[slot[n]] of step n in the prediction and in the
+ * smoothing gain.  The chunk is rk_solve_sim_draws's (RK_SIM_DRAWS_CHUNK included); the draws do not depend on it.
+ * THE SEED LAW: draw s is the path that rk_solve_grid / rk_dalton_grid_solve write in RK_MODE_SIM under the seed cfg->seed + s
+ * (mod 2^64) -- Philox is keyed with (seed + s, traj_offset + trajectory, step, block, smoothing purpose).
+ * keep, n_keep and x_draws (n_draws, K, n_block, n_bstate, n_traj) are rk_solve_sim_draws's, with node indices of t in
+ * 0..n_steps: an array that breaks the rule loses rows but never writes outside x_draws.  No workspace; out->x_state is not used.
+ * Served: kalman_type standard, n_bmeas = 1, n_bstate 2..6 (2..5 with three or more blocks), interrogate rodeo / schober /
+ * kramer, n_bobs 1..3, any built-in right-hand side or a user one with n_bmeas = 1; cfg->flags must carry RK_FLAG_BATCH_MINOR.
+ * What is not served is refused on cfg (and n_bobs) alone -- RK_ERR_INVALID (a non-positive size, RK_FLAG_BATCH_MINOR missing)
+ * or RK_ERR_UNSUPPORTED -- before the handle or any pointer is looked at; then n_draws (1..65535) and n_keep (RK_ERR_INVALID). */
+int rk_solve_sim_draws_grid(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out,
+                            const rk_grid_in* g, int32_t n_draws, const int32_t* keep, int32_t n_keep, double* x_draws);
+int rk_dalton_grid_sim_draws(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out,
+                             const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
+                             int32_t n_obs, int32_t n_bobs, const rk_grid_in* g, int32_t n_draws, const int32_t* keep,
+                             int32_t n_keep, double* x_draws);
+
 /* dalton_at: rk_dalton_loglik for observations whose times need not be grid nodes (an addition: the reference places every
  * observation by searchsorted on the grid).  obs / obs_weight / obs_var as for rk_dalton_loglik, in time order.  The device
  * array `table` (n_obs, 4) holds per observation: node, off-grid flag, pre slot, post slot or -1.  With the flag clear the

@@ -17,6 +17,7 @@ from .dynamic import solve_mv_dynamic, solve_sim_dynamic, DynamicMV, DynamicSim
 from .grid import solve_mv_grid, solve_sim_grid, grid_slots, grid_with_times
 from .grid_calib import solve_evidence_grid, solve_mv_dynamic_grid, solve_sim_dynamic_grid
 from .draws import solve_sim_draws
+from .grid_draws import solve_sim_draws_grid
 from .prior.ibm import ibm_init
 from .prior.indep_init import indep_init
 from .device import Device, DeviceArray, default_device

@@ -149,6 +149,8 @@ SIGNATURES = {
     "rk_fenrir_grid_solve_mv": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _P]),
     "rk_solve_sim_draws":(C.c_int, [_H, _P, _P, _P, _I, _P, _I, _P]),
     "rk_sim_draws_chunk": (C.c_int, []),
+    "rk_solve_sim_draws_grid": (C.c_int, [_H, _P, _P, _P, C.POINTER(GridIn), _I, _P, _I, _P]),
+    "rk_dalton_grid_sim_draws": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _I, _P, _I, _P]),
     "rk_magi_logdens": (C.c_int, [_H, C.POINTER(MagiCfg), C.POINTER(MagiIn), _P]),
     "rk_fd_stencil": (C.c_int, [_H, _I, _I, _P, _P, _P]),
     "rk_fd_grad_hess": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P]),

@@ -24,7 +24,8 @@ constexpr bool dalton_grid_ships() {
     return !(std::is_same<RHS, FitzHughNagumo>::value && P == 4 && MO == 3 && !STORE);
 #endif
 }
-static bool dalton_grid_left_out(const rk_solve_cfg* c, int n_bobs, bool store) {
+// (also asked by rk_dalton_grid_sim_draws, grid_draws.hip: declared in solve_paths.hpp)
+bool dalton_grid_left_out(const rk_solve_cfg* c, int n_bobs, bool store) {
     bool out = false;
     with_builtin_rhs(c->rhs_id, [&](auto rhs) {
         dispatch_int<2, 6>(c->n_bstate, [&](auto P) {
@@ -107,10 +108,17 @@ static int dalton_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveAr
     return rc;
 }
 
+// the store form's forward pass (also that of rk_dalton_grid_sim_draws, grid_draws.hip: declared in solve_paths.hpp)
+int dalton_grid_store_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
+                              int n_bobs) {
+    return dalton_grid_forward<true>(h, c, a, o, ga, n_bobs, nullptr);
+}
+
 // the pointers of a served call: the grid (rk_solve_grid's rule), the solver inputs and the observations (dalton_inputs' rule)
-static int dalton_grid_inputs(const char* who, const rk_solve_cfg* c, const rk_solve_in* in, const double* obs,
-                              const double* obs_weight, const double* obs_var, const int32_t* obs_ind, int n_obs, const rk_grid_in* g,
-                              DaltonObs& o, GridArgs& ga) {
+// (also those of rk_dalton_grid_sim_draws, grid_draws.hip: declared in solve_paths.hpp)
+int dalton_grid_inputs(const char* who, const rk_solve_cfg* c, const rk_solve_in* in, const double* obs,
+                       const double* obs_weight, const double* obs_var, const int32_t* obs_ind, int n_obs, const rk_grid_in* g,
+                       DaltonObs& o, GridArgs& ga) {
     RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
                "%s: grid needs t, slot, q, r and n_slots >= 1 (got %d)", who, g->n_slots);
     const int rc = check_cfg(c, in);
@@ -165,7 +173,7 @@ int rk_dalton_grid_solve(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* 
     if (rc) return rc;
     SolveArgs a;
     make_args(c, in, out, a);
-    rc = dalton_grid_forward<true>(h, c, a, o, ga, n_bobs, nullptr);
+    rc = dalton_grid_store_forward(h, c, a, o, ga, n_bobs);
     if (rc) return rc;
     return launch_grid_bwd(h, c, a, mode, ga);
 }

@@ -7,7 +7,6 @@
 // (seed + s, trajectory, step, block, PURPOSE_SMOOTH), bwd_sim_kernel's key.  Standard form, n_bstate 2..6, any n_block,
 // interrogate rodeo / schober / kramer.  Nothing but out->mean_state / var_state (the filtered moments) and x_draws is
 // written; there is no workspace.
-#include <cstdlib>
 #include <string>
 #include "common.hpp"
 #include "kalman_small.hpp"
@@ -19,9 +18,8 @@
 
 namespace rk {
 
-// most draws a lane carries down the chain: C * P doubles of carry on top of bwd_sim_kernel's registers (instances: C = 1, 2
-// and this; sim_draws_chunk picks one per call)
-constexpr int SIM_DRAWS_CHUNK = 4;
+// (SIM_DRAWS_CHUNK, the most draws a lane carries, and sim_draws_chunk, the rule that picks 1, 2 or that per call, are in
+// solve_paths.hpp: grid_draws.hip shares them)
 constexpr int SIM_DRAWS_PMIN = 2, SIM_DRAWS_PMAX = 6;
 
 // Mirrors lane_backward.hpp (BwdLane, bwd_walk under StaticPrior, store_path, load_path_init), written out: through them <3, 1>
@@ -146,21 +144,6 @@ static int sim_draws_check(const rk_solve_cfg* c) {
     RK_REQUIRE(c->flags & RK_FLAG_BATCH_MINOR, RK_ERR_INVALID,
                "sim_draws: the backward kernel reads batch-minor filtered records (set RK_FLAG_BATCH_MINOR)");
     return RK_OK;
-}
-
-// Draws per lane of this call: 1, 2 or SIM_DRAWS_CHUNK.  The chain of n_steps dependent steps bounds the kernel's time from
-// below, and a draw more per lane lengthens every step, so sharing the gain work pays only once the waves no longer fit the
-// machine side by side: the smallest chunk whose waves fit one per SIMD (four SIMDs per CU), else the largest.
-// RK_SIM_DRAWS_CHUNK = 1, 2 or 4 (read per call) fixes it, for tests and measurements; the draws do not depend on it.
-static int sim_draws_chunk(rk_handle h, const rk_solve_cfg* c, int n_draws) {
-    if (const char* fixed = getenv("RK_SIM_DRAWS_CHUNK")) {
-        const int v = atoi(fixed);
-        if (v == 1 || v == 2 || v == SIM_DRAWS_CHUNK) return v;
-    }
-    const long lanes_waves = div_up(c->n_traj * c->n_block, 64), simds = 4L * h->prop.multiProcessorCount;
-    for (int chunk = 1; chunk < SIM_DRAWS_CHUNK; chunk *= 2)
-        if (lanes_waves * div_up(n_draws, chunk) <= simds) return chunk;
-    return SIM_DRAWS_CHUNK;
 }
 
 template <int C>

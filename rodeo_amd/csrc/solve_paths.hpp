@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include <cstdlib>
 #include <type_traits>
 #include <utility>
 #include "common.hpp"
@@ -98,6 +99,13 @@ int user_grid_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, c
                        double* logdet);
 int user_grid_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double scale_min, double* scale,
                       double* logdens);
+// dalton_grid's store form for rk_dalton_grid_sim_draws (grid_draws.hip; all three in dalton_grid.hip): is the instance of
+// this configuration left out, the pointers of a served call, and the joint filter's batch-minor records into a.mean / a.var
+bool dalton_grid_left_out(const rk_solve_cfg* c, int n_bobs, bool store);
+int dalton_grid_inputs(const char* who, const rk_solve_cfg* c, const rk_solve_in* in, const double* obs, const double* obs_weight,
+                       const double* obs_var, const int32_t* obs_ind, int n_obs, const rk_grid_in* g, DaltonObs& o, GridArgs& ga);
+int dalton_grid_store_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
+                              int n_bobs);
 // dalton_grid: the configuration against the registration and the forward launch (dalton_grid.hip)
 int user_dalton_grid_check(const rk_solve_cfg* c);
 int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
@@ -210,6 +218,26 @@ inline LaunchGeom dalton_lane_geom(int B, bool pair) { return {dim3(div_up(B, pa
 // dalton_fwd_tile3_kernel, dalton_fwd_at_tile3_kernel (n_block <= 4): 2 B (pair) or B filter instances of D tiles
 inline LaunchGeom dalton_tile_geom(int B, int D, bool pair) {
     return {dim3(div_up((pair ? 2 * B : B) * D, tiles_per_wave(D))), dim3(64)};
+}
+
+// ---- draws per lane of the many-draws backward kernels (sim_draws.hip, grid_draws.hip) -------------------------------------
+// most draws a lane carries down the chain: C * P doubles of carry on top of the one-draw kernel's registers (instances: C = 1,
+// 2 and this; sim_draws_chunk picks one per call)
+constexpr int SIM_DRAWS_CHUNK = 4;
+
+// Draws per lane of this call: 1, 2 or SIM_DRAWS_CHUNK.  The chain of n_steps dependent steps bounds the kernel's time from
+// below, and a draw more per lane lengthens every step, so sharing the gain work pays only once the waves no longer fit the
+// machine side by side: the smallest chunk whose waves fit one per SIMD (four SIMDs per CU), else the largest.
+// RK_SIM_DRAWS_CHUNK = 1, 2 or 4 (read per call) fixes it, for tests and measurements; the draws do not depend on it.
+inline int sim_draws_chunk(rk_handle h, const rk_solve_cfg* c, int n_draws) {
+    if (const char* fixed = getenv("RK_SIM_DRAWS_CHUNK")) {
+        const int v = atoi(fixed);
+        if (v == 1 || v == 2 || v == SIM_DRAWS_CHUNK) return v;
+    }
+    const long lanes_waves = div_up(c->n_traj * c->n_block, 64), simds = 4L * h->prop.multiProcessorCount;
+    for (int chunk = 1; chunk < SIM_DRAWS_CHUNK; chunk *= 2)
+        if (lanes_waves * div_up(n_draws, chunk) <= simds) return chunk;
+    return SIM_DRAWS_CHUNK;
 }
 
 // ---- what the built-in instances of several families share ---------------------------------------------------------------

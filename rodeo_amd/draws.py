@@ -21,7 +21,8 @@ dependent steps bounds the time from below, so sharing pays only once the device
 All of it runs on the device (``rk_solve_sim_draws``).
 
 Not built: the square-root form, interrogate_chkrebtii, the p = 3 tile route, the dense route (n_bmeas > 1), draws of
-``dalton.solve_sim`` and off-grid times.
+``dalton.solve_sim`` on the uniform grid (``rodeo_amd.inference.dalton.solve_sim_draws_grid`` gives draws from p(X | Z, Y) on any
+grid, a uniform one included) and off-grid times (``solve_sim_draws_grid``, grid_draws.py, takes a grid that has them as nodes).
 """
 import numpy as np
 from . import _lib
@@ -41,20 +42,32 @@ def draw_seed(key, s):
     return (_seed(key) + int(s)) & 0xFFFFFFFFFFFFFFFF
 
 
-def _keep_rule(keep, n_steps):
-    """``keep`` as an int32 array of grid indices, or None for every node; ValueError for what the contract rules out."""
+def _keep_rule(keep, n_steps, name="solve_sim_draws"):
+    """``keep`` as an int32 array of grid indices, or None for every node; ValueError for what the contract rules out (``name``:
+    the function the message names)."""
     if keep is None:
         return None
     k = np.asarray(keep)
     if k.ndim != 1 or not np.issubdtype(k.dtype, np.integer):
-        raise ValueError(f"solve_sim_draws: keep must be a 1-D integer array of grid indices, got shape {k.shape}, dtype {k.dtype}")
+        raise ValueError(f"{name}: keep must be a 1-D integer array of grid indices, got shape {k.shape}, dtype {k.dtype}")
     if k.size == 0:
-        raise ValueError("solve_sim_draws: keep is empty")
+        raise ValueError(f"{name}: keep is empty")
     if k.min() < 0 or k.max() > n_steps:
-        raise ValueError(f"solve_sim_draws: keep must lie in 0 .. n_steps = {n_steps}, got {int(k.min())} .. {int(k.max())}")
+        raise ValueError(f"{name}: keep must lie in 0 .. n_steps = {n_steps}, got {int(k.min())} .. {int(k.max())}")
     if np.any(np.diff(k.astype(np.int64)) <= 0):
-        raise ValueError("solve_sim_draws: keep must be strictly increasing")
+        raise ValueError(f"{name}: keep must be strictly increasing")
     return k.astype(np.int32)
+
+
+def _draw_rules(name, interrogate, n_draws, keep, n_steps):
+    """What is refused for the draws themselves, for ``solve_sim_draws`` and for ``solve_sim_draws_grid`` (grid_draws.py):
+    interrogate_chkrebtii, ``n_draws`` and ``keep``; returns (n_draws, keep or None)."""
+    if _interrogate_id(interrogate)[0] == _lib.INTERROGATE_CHKREBTII:
+        raise NotImplementedError(f"{name}: interrogate_chkrebtii is not served: its forward pass depends on the key, "
+                                  "so the draws cannot share one filter (rodeo, schober, kramer)")
+    if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or not 1 <= n_draws <= N_DRAWS_MAX:
+        raise ValueError(f"{name}: n_draws must be an integer in 1 .. {N_DRAWS_MAX}, got {n_draws!r}")
+    return int(n_draws), _keep_rule(keep, int(n_steps), name)
 
 
 def _refusals(ode_fun, ode_weight, ode_init, n_steps, interrogate, prior_pars, kalman_type, n_draws, keep, params):
@@ -63,12 +76,7 @@ def _refusals(ode_fun, ode_weight, ode_init, n_steps, interrogate, prior_pars, k
         raise NotImplementedError(f"solve_sim_draws: unknown kalman_type {kalman_type!r}")
     if kalman_type != "standard":
         raise NotImplementedError("solve_sim_draws: kalman_type='square-root' is not built")
-    if _interrogate_id(interrogate)[0] == _lib.INTERROGATE_CHKREBTII:
-        raise NotImplementedError("solve_sim_draws: interrogate_chkrebtii is not served: its forward pass depends on the key, "
-                                  "so the draws cannot share one filter (rodeo, schober, kramer)")
-    if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or not 1 <= n_draws <= N_DRAWS_MAX:
-        raise ValueError(f"solve_sim_draws: n_draws must be an integer in 1 .. {N_DRAWS_MAX}, got {n_draws!r}")
-    keep = _keep_rule(keep, int(n_steps))
+    n_draws, keep = _draw_rules("solve_sim_draws", interrogate, n_draws, keep, n_steps)
     W = np.shape(ode_weight)
     if len(W) not in (3, 4):
         raise ValueError("ode_weight must have shape (n_block, n_bmeas, n_bstate) [+ a leading batch axis]")
@@ -81,7 +89,22 @@ def _refusals(ode_fun, ode_weight, ode_init, n_steps, interrogate, prior_pars, k
     if (ode.n_block, ode.n_bmeas) != (d, m):
         raise ValueError(f"ODE '{ode.name}' has (n_block, n_bmeas) = ({ode.n_block}, {ode.n_bmeas}) but ode_weight has ({d}, {m})")
     _shape_rule(ode, ode_weight, ode_init, prior_pars, params)      # ValueError: ranks, mismatched shapes, batch sizes
-    return ode, int(n_draws), keep
+    return ode, n_draws, keep
+
+
+def _launch_draws(name, plan, key, fn, n_draws, keep, *front):
+    """One launch of a many-draws entry ``fn(handle, cfg, in, out, *front, n_draws, keep, K, x_draws)`` on the batch-minor
+    ``plan`` and the download: ``x`` (n_draws, K, d, p) or (B, n_draws, K, d, p).  ``solve_sim_draws``'s, and with the grid (and
+    the observations) in ``front`` that of the two ``solve_sim_draws_grid`` (grid_draws.py, inference/dalton.py)."""
+    dev = plan.dev
+    K = plan.N + 1 if keep is None else int(keep.size)
+    keep_dev = plan.staged("sim_draws_keep", keep)[0] if keep is not None else None
+    x = dev.empty((n_draws, K, plan.d, plan.p, plan.B))
+    plan.launch(fn, key, _lib.MODE_FILTER, *front, n_draws, keep_dev.ptr if keep_dev is not None else None, K, x.ptr)
+    if plan.layout != _lib.LAYOUT_BATCH_MINOR:                       # (batch_minor=True: the records the backward kernel reads)
+        raise RuntimeError(f"{name}: the plan reports layout {plan.layout}, not the batch-minor records")
+    xs = x.batch_first()                                             # (B, n_draws, K, d, p): a view of the download
+    return xs if plan.batched else xs[0]
 
 
 def solve_sim_draws(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
@@ -108,12 +131,4 @@ def solve_sim_draws(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, i
                                    params)
     plan = cached_plan(ode, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars, kalman_type,
                        batch_minor=True, **params)
-    dev = plan.dev
-    K = plan.N + 1 if keep is None else int(keep.size)
-    keep_dev = plan.staged("sim_draws_keep", keep)[0] if keep is not None else None
-    x = dev.empty((n_draws, K, plan.d, plan.p, plan.B))
-    plan.launch(dev.lib.rk_solve_sim_draws, key, _lib.MODE_FILTER, n_draws, keep_dev.ptr if keep_dev is not None else None, K, x.ptr)
-    if plan.layout != _lib.LAYOUT_BATCH_MINOR:                       # (batch_minor=True: the records the backward kernel reads)
-        raise RuntimeError(f"solve_sim_draws: the plan reports layout {plan.layout}, not the batch-minor records")
-    xs = x.batch_first()                                             # (B, n_draws, K, d, p): a view of the download
-    return xs if plan.batched else xs[0]
+    return _launch_draws("solve_sim_draws", plan, key, plan.dev.lib.rk_solve_sim_draws, n_draws, keep)

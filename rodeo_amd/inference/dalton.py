@@ -250,6 +250,28 @@ def solve_sim_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prio
                        obs_data, obs_times, obs_weight, obs_var, kalman_type, params).x_host()
 
 
+def solve_sim_draws_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                         obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", n_draws=1, keep=None, **params):
+    """``n_draws`` draws from p(X | Z, Y) on the nodes ``t_grid`` from one joint filter (an addition):
+    ``x`` (n_draws, K, d, p), or (B, n_draws, K, d, p) for batched inputs -- ``dalton_grid``'s joint filter (its store form), then
+    ``rodeo_amd.solve_sim_draws_grid``'s backward kernel.  Arguments, the node rule and the refusals are ``dalton_grid``'s;
+    ``n_draws`` and ``keep`` (node indices of ``t_grid``, ``None`` for every node) and their refusals are
+    ``rodeo_amd.solve_sim_draws``'s, raised before any device work.  The law: draw ``s`` is ``solve_sim_grid``'s path (this
+    module's) for the integer seed ``rodeo_amd.draws.draw_seed(key, s)``, restricted to ``keep``; node 0 is ``ode_init``.  With an
+    empty observation set the result is ``rodeo_amd.solve_sim_draws_grid``'s."""
+    from .. import grid
+    from ..draws import _draw_rules, _launch_draws
+    who = "dalton.solve_sim_draws_grid"
+    n_draws, keep = _draw_rules(who, interrogate, n_draws, keep, len(grid._grid(t_grid)) - 1)
+    plan, g, (p_obs, p_w, p_v, p_ind, n_obs, n_bobs) = _on_grid(
+        who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var, kalman_type,
+        params)
+    if n_obs == 0:                                                  # p(X | Z): rodeo_amd.solve_sim_draws_grid itself
+        return _launch_draws(who, plan, key, plan.dev.lib.rk_solve_sim_draws_grid, n_draws, keep, C.byref(g))
+    return _launch_draws(who, plan, key, plan.dev.lib.rk_dalton_grid_sim_draws, n_draws, keep, p_obs, p_w, p_v, p_ind, n_obs, n_bobs,
+                         C.byref(g))
+
+
 # --- non-Gaussian observations (src/rodeo/inference/dalton.py:547-1039) -------------------------------------------------
 #
 # ``daltonng`` and ``solve_mv_nn`` take an ordinary Python ``obs_loglik_i(obs_data_i, ode_data_i, ind, **params)`` written with
