@@ -544,6 +544,28 @@ int rk_daltonng_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* 
                        const int32_t* obs_ind, int32_t n_obs, void* workspace, size_t workspace_bytes, double* logdens);
 int rk_daltonng_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
                       int32_t obs_id, const double* obs, const int32_t* obs_ind, int32_t n_obs);
+/* daltonng_grid (an addition): rk_daltonng_loglik / rk_daltonng_solve on rk_solve_grid's non-uniform grid, every observation on a
+ * node.  obs_id and obs as for rk_daltonng_loglik; obs_node (n_obs) holds the NODE of every observation, strictly increasing in
+ * 0..n_steps: node 0 enters the log-likelihood term only, a node above n_steps never matches.  Step n -> n + 1 of the joint
+ * filter: the prediction with (q, r)[slot[n]], the interrogation at t[n+1], the z update, then -- if node n + 1 is observed -- the
+ * conditioning on the pseudo-observation expanded at the predicted mean (z first, yhat second, as rk_daltonng_loglik).  The two
+ * backward conditionals at node n re-evaluate the prediction and the gain from filt[n] with (q, r)[slot[n]].
+ * rk_daltonng_grid_loglik: logy_x + logx_z - logx_yhat per trajectory into logdens (B); `workspace` is rk_daltonng_workspace_bytes's,
+ * the same layout, checked before any launch.  A non-concave point yields NaN, not an error.
+ * rk_daltonng_grid_solve: the joint filter's moments into out->mean_state / var_state (mode = RK_MODE_FILTER), then rk_solve_grid's
+ * smoothing pass (RK_MODE_MV); RK_LAYOUT_BATCH_MINOR.
+ * Served: what rk_daltonng_loglik serves; cfg->flags must carry RK_FLAG_BATCH_MINOR and not RK_FLAG_STORE_PRED.  What is not served
+ * is refused on cfg, mode and the registered model alone -- RK_ERR_INVALID (a non-positive size, another mode,
+ * RK_FLAG_BATCH_MINOR missing, a model registered for another configuration) or RK_ERR_UNSUPPORTED -- before the handle or any
+ * pointer is looked at.
+ * rk_obs_grid_compile_check: compiles the two forward forms of the grid filter around obs_id for this right-hand side and
+ * interrogation without loading them (needs no GPU; RK_JIT_VERBOSE prints each build's registers, scratch and LDS).            */
+int rk_obs_grid_compile_check(int32_t obs_id, int32_t rhs_id, int32_t interrogate);
+int rk_daltonng_grid_loglik(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, int32_t obs_id, const double* obs,
+                            const int32_t* obs_node, int32_t n_obs, const rk_grid_in* g, void* workspace, size_t workspace_bytes,
+                            double* logdens);
+int rk_daltonng_grid_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
+                           int32_t obs_id, const double* obs, const int32_t* obs_node, int32_t n_obs, const rk_grid_in* g);
 /* The same on the records of the blocked-tile forward pass (kalman_type standard, n_bstate 4 .. 8, rk_solve_filter WITHOUT
  * RK_FLAG_STORE_PRED | RK_FLAG_BATCH_MINOR: out->var_state = the records): predicted moments are re-evaluated, nothing but the
  * filtered records is read; the result goes to mean_out (N+1, d, p, B) and var_out (N+1, d, p, p, B), batch-minor.

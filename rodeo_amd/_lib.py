@@ -138,6 +138,9 @@ SIGNATURES = {
     "rk_daltonng_workspace_bytes": (C.c_int, [_P, _I, C.POINTER(C.c_size_t)]),
     "rk_daltonng_loglik": (C.c_int, [_H, _P, _P, _I, _P, _P, _I, _P, C.c_size_t, _P]),
     "rk_daltonng_solve": (C.c_int, [_H, _P, _P, _P, _I, _I, _P, _P, _I]),
+    "rk_obs_grid_compile_check": (C.c_int, [_I, _I, _I]),
+    "rk_daltonng_grid_loglik": (C.c_int, [_H, _P, _P, _I, _P, _P, _I, C.POINTER(GridIn), _P, C.c_size_t, _P]),
+    "rk_daltonng_grid_solve": (C.c_int, [_H, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(GridIn)]),
     "rk_solve_evidence": (C.c_int, [_H, _P, _P, _P, _P, _P]),
     "rk_solve_dynamic": (C.c_int, [_H, _P, _P, _P, _I, _D, _P, _P]),
     "rk_solve_grid": (C.c_int, [_H, _P, _P, _P, _I, C.POINTER(GridIn)]),

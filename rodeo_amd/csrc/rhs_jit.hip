@@ -80,6 +80,8 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_DALTON_GRID_STORE  */ {"rk::dalton_grid_fwd_kernel<rk::UserRhsT, {P}, {I}, {M}, true>", "dalton_grid_kernels.hpp", "dalton_grid_fwd_kernel<store, user>"},
     /* JIT_GRID_EVIDENCE      */ {"rk::grid_evidence_kernel<rk::UserRhsT, {P}, {I}>", "grid_calib_kernels.hpp", "grid_evidence_kernel<user>"},
     /* JIT_GRID_DYNAMIC       */ {"rk::grid_dynamic_fwd_kernel<rk::UserRhsT, {P}, {I}>", "grid_calib_kernels.hpp", "grid_dynamic_fwd_kernel<user>"},
+    /* JIT_DALTONNG_GRID      */ {"rk::daltonng_grid_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, false>", "daltonng_grid_kernels.hpp", "daltonng_grid_fwd_kernel<store>"},
+    /* JIT_DALTONNG_GRID_BOTH */ {"rk::daltonng_grid_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, true>", "daltonng_grid_kernels.hpp", "daltonng_grid_fwd_kernel<both>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -227,6 +229,28 @@ struct JitCode { int rc; std::vector<char> code; std::string lowered; std::strin
 static std::map<JitKey, JitCode> g_code;                            // key.device = -1
 static std::map<JitKey, hipFunction_t> g_mod;                       // key.device = the handle's
 
+// RK_JIT_VERBOSE, at build time and without a device: the resources of the one kernel in a hiprtc code object, read from its
+// AMDGPU metadata note (msgpack: the key's string, then an unsigned integer).  What the loaded kernel reports in jit_lookup, so
+// that an instance's registers, scratch and LDS can be listed on a machine without a GPU.
+static long jit_meta_uint(const std::vector<char>& code, const char* key) {
+    const size_t n = strlen(key);
+    for (size_t at = 0; at + n + 1 <= code.size(); ++at) {
+        if (memcmp(code.data() + at, key, n) != 0) continue;
+        const unsigned char* v = (const unsigned char*)code.data() + at + n;
+        const size_t left = code.size() - (at + n);
+        if (v[0] <= 0x7f) return v[0];
+        if (v[0] == 0xcc && left >= 2) return v[1];
+        if (v[0] == 0xcd && left >= 3) return (long)v[1] << 8 | v[2];
+        if (v[0] == 0xce && left >= 5) return (long)v[1] << 24 | (long)v[2] << 16 | (long)v[3] << 8 | v[4];
+    }
+    return -1;
+}
+static void jit_report_build(const JitCode& b) {
+    fprintf(stderr, "[rk] jit build %s: %ld VGPRs + %ld AGPRs, %ld B scratch per lane, %ld B LDS\n", b.lowered.c_str(),
+            jit_meta_uint(b.code, ".vgpr_count"), jit_meta_uint(b.code, ".agpr_count"),
+            jit_meta_uint(b.code, ".private_segment_fixed_size"), jit_meta_uint(b.code, ".group_segment_fixed_size"));
+}
+
 // program text, name expression and the user's type name (for the error message) of the build behind `key`
 struct JitProgram { std::string src, expr, what; const char* role; };
 static int jit_program(const JitKey& key, JitProgram& p) {
@@ -283,6 +307,7 @@ static int jit_lookup(JitKey key, rk_handle h, hipFunction_t* fn) {
         JitCode built;
         built.rc = jit_compile_src(p.src, p.expr, p.what, built.code, built.lowered, p.role);
         if (built.rc) built.error = rk_last_error();
+        if (built.rc == RK_OK && getenv("RK_JIT_VERBOSE")) jit_report_build(built);
         std::lock_guard<std::mutex> lk(g_mu);
         c = &g_code.emplace(ckey, std::move(built)).first->second;     // (map nodes do not move: the pointer stays valid)
     }
@@ -592,6 +617,20 @@ int ng_forward(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& 
     return launch_jit(h, jit_key(both ? JIT_DALTONNG_BOTH : JIT_DALTONNG, c->rhs_id, c, 0, obs_id), dalton_lane_geom(a.B, both), params);
 }
 
+// the same on rk_solve_grid's non-uniform grid (daltonng_grid_kernels.hpp): o.obs_ind holds the node of every observation
+int ng_grid_forward(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, const GridArgs& g, bool both,
+                    double* zm, double* zv) {
+    if (is_user_rhs(c->rhs_id)) {
+        const int rc = user_rhs_check(c);
+        if (rc) return rc;
+    }
+    SolveArgs args = a;
+    NgObs obs = o;
+    void* params[] = {&args, &obs, (void*)&g, &zm, &zv};
+    return launch_jit(h, jit_key(both ? JIT_DALTONNG_GRID_BOTH : JIT_DALTONNG_GRID, c->rhs_id, c, 0, obs_id),
+                      dalton_lane_geom(a.B, both), params);
+}
+
 // logy_x on the smoothed means and the final sum into out (B)
 int ng_obs_eval(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, const double* sm,
                 const double* part, double* out) {
@@ -643,6 +682,21 @@ int rk_obs_compile_check(int32_t obs_id, int32_t rhs_id, int32_t interrogate) {
     c.n_bstate = info.n_bstate;
     c.interrogate = interrogate;
     const JitKind kinds[] = {JIT_DALTONNG_BOTH, JIT_DALTONNG, JIT_DALTONNG_OBS};
+    for (JitKind k : kinds) {
+        rc = jit_lookup(jit_key(k, rhs_id, &c, 0, obs_id), nullptr, nullptr);
+        if (rc) return rc;
+    }
+    return RK_OK;
+}
+
+int rk_obs_grid_compile_check(int32_t obs_id, int32_t rhs_id, int32_t interrogate) {
+    NgObsInfo info;
+    int rc = ng_obs_info(obs_id, &info);
+    if (rc) return rc;
+    rk_solve_cfg c{};
+    c.n_bstate = info.n_bstate;
+    c.interrogate = interrogate;
+    const JitKind kinds[] = {JIT_DALTONNG_GRID_BOTH, JIT_DALTONNG_GRID};
     for (JitKind k : kinds) {
         rc = jit_lookup(jit_key(k, rhs_id, &c, 0, obs_id), nullptr, nullptr);
         if (rc) return rc;

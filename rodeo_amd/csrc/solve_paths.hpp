@@ -64,6 +64,8 @@ enum JitKind : int {
     JIT_DALTON_GRID_STORE = 26,  // dalton_grid_fwd_kernel<.., true> (dalton.solve_mv_grid / solve_sim_grid, the joint filter's moments)
     JIT_GRID_EVIDENCE = 27,   // grid_evidence_kernel (solve_evidence_grid)
     JIT_GRID_DYNAMIC = 28,    // grid_dynamic_fwd_kernel (solve_mv_dynamic_grid / solve_sim_dynamic_grid, the forward lanes)
+    JIT_DALTONNG_GRID = 29,   // daltonng_grid_fwd_kernel<.., false> (solve_mv_nn_grid, the joint filter's moments)
+    JIT_DALTONNG_GRID_BOTH = 30,  // daltonng_grid_fwd_kernel<.., true> (daltonng_grid, the joint filter and the filter on Z alone)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -120,6 +122,16 @@ int ng_forward(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& 
                double* zv);
 int ng_obs_eval(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, const double* sm,
                 const double* part, double* out);
+// the same forward filter(s) on rk_solve_grid's non-uniform grid (daltonng_grid_kernels.hpp): o.obs_ind holds nodes
+int ng_grid_forward(rk_handle h, const rk_solve_cfg* c, int obs_id, const SolveArgs& a, const NgObs& o, const GridArgs& g, bool both,
+                    double* zm, double* zv);
+// what rk_daltonng_grid_* (daltonng_grid.hip) share with rk_daltonng_* (all three in daltonng.hip; `who` names the entry in the
+// messages): is the configuration served and the observation model registered for it, the workspace of
+// rk_daltonng_workspace_bytes carved into its parts (checked against workspace_bytes), and the launch of daltonng_chain_kernel
+struct NgWs;
+int ng_check(const char* who, const rk_solve_cfg* c, int obs_id);
+int ng_workspace(const char* who, const rk_solve_cfg* c, int n_obs, void* workspace, size_t workspace_bytes, NgWs& w);
+int ng_chain(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const NgWs& w, const NgObs& o);
 bool user_dense_wanted(const rk_solve_cfg* c);
 int user_dense_interrogate(rk_handle h, const rk_solve_cfg* c, const DenseItgArgs& a);
 

@@ -9,6 +9,8 @@
     addition; imported from this module, not re-exported by ``rodeo_amd.inference``).
   * ``dalton_grid`` / ``solve_mv_grid`` / ``solve_sim_grid``: the three on a non-uniform grid shared by the batch, every observation
     on a node (an addition, imported from this module like ``dalton_at``; ``rk_dalton_grid_loglik`` / ``rk_dalton_grid_solve``).
+  * ``daltonng`` / ``solve_mv_nn`` for non-Gaussian observations (:547-1039) and ``daltonng_grid`` / ``solve_mv_nn_grid``, the two
+    on that non-uniform grid (an addition; ``rk_daltonng_grid_loglik`` / ``rk_daltonng_grid_solve``); imported from this module.
 All of it runs on the device (``rk_dalton_loglik`` / ``rk_dalton_loglik_at`` / ``rk_dalton_solve``): both filters of every parameter set in one
 kernel launch for ``dalton`` (only B doubles come back), the joint filter's moments and the solver's own backward kernels
 for ``solve_mv`` / ``solve_sim``.  At n_bstate = 3 with one observation per block and up to four blocks the filters run
@@ -300,28 +302,48 @@ def _ng_param_spec(ode_fun, params):
     return tuple(spec)
 
 
-def _ng_refusals(ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_times, obs_loglik_i, t_min, t_max, n_steps,
-                 params):
-    """Everything this build does not serve, raised before any device work; returns (obs, obs_ind, traced model)."""
-    from ..trace import trace_obs_source
-    _refuse_config("daltonng", ode_weight, kalman_type, interrogate=interrogate, bmeas="")
+def _ng_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_loglik_i):
+    """The configurations ``who`` (daltonng, or daltonng_grid) does not serve and the shapes of its observation arguments, raised
+    before any device work; returns obs (n_obs, d, n_ycols) as contiguous float64."""
+    _refuse_config(who, ode_weight, kalman_type, interrogate=interrogate, bmeas="")
     d, p = int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1])
     if d >= 3 and p > 5:                                            # (daltonng.hip ng_check: the lane kernel spills)
-        raise NotImplementedError("daltonng on the device: n_bstate up to 5 with three or more blocks")
+        raise NotImplementedError(f"{who} on the device: n_bstate up to 5 with three or more blocks")
     rid = getattr(ode_fun, "rhs_id", None)
     if rid is not None and rid < _lib.RHS_USER_BASE:                # a built-in right-hand side: the hiprtc unit has to name it
         if rid not in (_lib.RHS_FITZHUGH_NAGUMO, _lib.RHS_LORENZ63, _lib.RHS_HIGHER_ORDER):
-            raise NotImplementedError(f"daltonng on the device: the built-in right-hand side {getattr(ode_fun, 'name', rid)!r} "
+            raise NotImplementedError(f"{who} on the device: the built-in right-hand side {getattr(ode_fun, 'name', rid)!r} "
                                       "has no lane-per-trajectory form (fitzhugh_nagumo, lorenz63, higher_order, or a "
                                       "Python / from_source right-hand side)")
         if getattr(ode_fun, "n_block", d) != d:
-            raise NotImplementedError(f"daltonng on the device: the right-hand side {ode_fun.name!r} has {ode_fun.n_block} "
+            raise NotImplementedError(f"{who} on the device: the right-hand side {ode_fun.name!r} has {ode_fun.n_block} "
                                       f"blocks, ode_weight has {d}")
     obs = np.ascontiguousarray(obs_data, dtype=np.float64)
     if obs.ndim != 3 or obs.shape[1] != d:
         raise ValueError(f"obs_data must have shape (n_obs, {d}, n_ycols), got {obs.shape}")
     if not callable(obs_loglik_i):
         raise TypeError("obs_loglik_i must be a Python function obs_loglik_i(obs_data_i, ode_data_i, ind, **params)")
+    return obs
+
+
+def _ng_model(ode_fun, ode_weight, obs, obs_loglik_i, params):
+    """The traced model of ``obs_loglik_i`` (the one run on symbols), kept by the hash of its generated source."""
+    from ..trace import trace_obs_source
+    d, p = int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1])
+    spec = _ng_param_spec(ode_fun, params)
+    probe, active = trace_obs_source(obs_loglik_i, d, p, obs.shape[2], spec, _NG_PLACEHOLDER)
+    key = hashlib.sha1(repr((probe, d, p, obs.shape[2], spec)).encode()).hexdigest()
+    if key not in _obs_models:
+        struct = "TracedObs_" + key[:10]
+        _obs_models[key] = dict(source=probe.replace(_NG_PLACEHOLDER, struct), struct=struct, active=active,
+                                n_theta=sum(s for _, s in spec), obs_id=None)
+    return _obs_models[key]
+
+
+def _ng_refusals(ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_times, obs_loglik_i, t_min, t_max, n_steps,
+                 params):
+    """Everything this build does not serve, raised before any device work; returns (obs, obs_ind, traced model)."""
+    obs = _ng_config("daltonng", ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_loglik_i)
     times = np.asarray(obs_times, dtype=np.float64)
     if times.shape != (obs.shape[0],):
         raise ValueError(f"obs_times must have shape ({obs.shape[0]},), got {times.shape}")
@@ -331,14 +353,7 @@ def _ng_refusals(ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_ti
     if np.any(np.diff(ind) <= 0):
         raise ValueError("daltonng: the observations' grid indices must be strictly increasing (one observation per grid "
                          "point, in time order)")
-    spec = _ng_param_spec(ode_fun, params)
-    probe, active = trace_obs_source(obs_loglik_i, d, p, obs.shape[2], spec, _NG_PLACEHOLDER)       # the one run on symbols
-    key = hashlib.sha1(repr((probe, d, p, obs.shape[2], spec)).encode()).hexdigest()
-    if key not in _obs_models:
-        struct = "TracedObs_" + key[:10]
-        _obs_models[key] = dict(source=probe.replace(_NG_PLACEHOLDER, struct), struct=struct, active=active,
-                                n_theta=sum(s for _, s in spec), obs_id=None)
-    return obs, ind, _obs_models[key]
+    return obs, ind, _ng_model(ode_fun, ode_weight, obs, obs_loglik_i, params)
 
 
 def _ng_obs_id(model, d, p, n_ycols):
@@ -383,6 +398,88 @@ def solve_mv_nn(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, inter
     oid = _ng_obs_id(model, plan.d, plan.p, obs.shape[2])
     d_obs, d_ind = plan.staged("daltonng", obs, ind)
     plan.launch(plan.dev.lib.rk_daltonng_solve, key, _lib.MODE_MV, _lib.MODE_MV, oid, d_obs.ptr, d_ind.ptr, int(ind.shape[0]))
+    return plan.state_host()
+
+
+# --- non-Gaussian observations on a non-uniform grid (an addition) -------------------------------
+
+def _ng_on_grid(who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_loglik_i, kalman_type,
+                params):
+    """
+    What the two grid calls do before their launch: ``daltonng``'s refusals of the configuration (``_ng_config``), the observation
+    times against the nodes (``_obs_nodes``, ``dalton_grid``'s rule), ``rodeo_amd.solve_mv_grid``'s refusals of the grid and
+    ``prior_at`` (called once per slot) and the trace of ``obs_loglik_i`` -- all before any device work -- then the cached
+    batch-minor plan with the grid and the observations staged on it.  Returns ``(plan, g, obs_id, p_obs, p_node, n_obs)``; the
+    pointers are None for an empty observation set.
+    """
+    from .. import grid
+    obs = _ng_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_data, obs_loglik_i)
+    node = _obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
+    ode, t, slot, pairs = grid._refusals(who, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
+    model = _ng_model(ode_fun, ode_weight, obs, obs_loglik_i, params)
+    plan = cached_plan(ode, ode_weight, ode_init, t[0], t[-1], len(slot), interrogate, pairs[0], kalman_type, batch_minor=True,
+                       **params)
+    (q, r), batched = _stack_pairs(pairs, plan.B)
+    d_t, d_slot, d_q, d_r = plan.staged("grid", t, slot, q, r)
+    g = _lib.GridIn(t=d_t.ptr, slot=d_slot.ptr, q=d_q.ptr, r=d_r.ptr, q_batched=batched, r_batched=batched, n_slots=len(pairs))
+    oid = _ng_obs_id(model, plan.d, plan.p, obs.shape[2])
+    p_obs = p_node = None
+    if len(node):
+        p_obs, p_node = (a.ptr for a in plan.staged("daltonng_grid", obs, node))
+    return plan, g, oid, p_obs, p_node, len(node)
+
+
+def daltonng_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                  obs_data, obs_times, obs_loglik_i, kalman_type="standard", **params):
+    """
+    ``daltonng`` on a non-uniform grid shared by the batch (an addition): logy_x + logx_z - logx_yhat, a float, or an array (B,)
+    for batched inputs.  ``t_grid`` (N+1,), ``prior_at(dt)`` (called once per slot of ``grid_slots(t_grid)``) and the batching of
+    what it returns are ``rodeo_amd.solve_mv_grid``'s; ``obs_data`` (n_obs, d, n_ycols), ``obs_loglik_i(obs_data_i, ode_data_i, ind,
+    **params)`` -- ``ind`` is the observation's index i --, its tracing, the model cache and what is served (kalman_type
+    "standard", n_bmeas = 1, n_bstate 2 .. 6, 2 .. 5 with three or more blocks, rodeo / schober / kramer, 1 .. 3 active components
+    per block) are ``daltonng``'s.
+
+    EVERY OBSERVATION TIME MUST BE A NODE (``dalton_grid``'s rule): time tau belongs to node k when |tau - t[k]| <=
+    ``EVAL_AT_NODE_TOL`` times the shorter adjacent step, and ``rodeo_amd.grid_with_times(t_grid, obs_times)`` returns the grid with
+    the times put in.  ValueError before any device work: a time that is no node, times not strictly increasing, two times on one
+    node, a non-finite time, a time outside [t[0], t[-1]], and what ``solve_mv_grid`` and ``daltonng`` refuse.
+
+    Step n -> n + 1 of the joint filter predicts with the step's own prior pair, interrogates at t[n+1], updates on z and, if node
+    n + 1 is observed, conditions on the pseudo-observation yhat = mu-[A_b] + V g_A, V = (-H_AA)^{-1}, expanded at the predicted
+    mean (z first, yhat second, like ``daltonng``).  An observation on node 0 does not enter the filter; it enters logy_x at
+    ``ode_init``.  The two backward conditionals at node n re-evaluate the prediction and the gain from the filtered moments of
+    node n with the pair of step n.  A point where the log-likelihood is not concave gives NaN, never an error.  With NO
+    OBSERVATIONS the call does what ``daltonng`` does with none: both filters run on the device and the value is
+    logx_z - logx_yhat of two equal filters.  The workspace (``rk_daltonng_workspace_bytes``) lives for the call only.
+    """
+    plan, g, oid, p_obs, p_node, n_obs = _ng_on_grid("daltonng_grid", ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                                                     obs_data, obs_times, obs_loglik_i, kalman_type, params)
+    need = C.c_size_t(0)
+    _lib.check(plan.dev.lib.rk_daltonng_workspace_bytes(C.byref(plan.cfg), n_obs, C.byref(need)))
+    ws = plan.dev.empty((need.value // 8,))                         # two stored filters + the gain records: released on return
+    plan.set_seed(key)
+    out = plan.dev.empty((plan.B,))
+    _lib.check(plan.dev.lib.rk_daltonng_grid_loglik(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), oid, p_obs, p_node, n_obs,
+                                                    C.byref(g), ws.ptr, ws.nbytes, out.ptr))
+    return plan.per_traj(out)
+
+
+def solve_mv_nn_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                     obs_data, obs_times, obs_loglik_i, kalman_type="standard", **params):
+    """Mean and variance of p(X | Z, Yhat) on the nodes ``t_grid`` for non-Gaussian observations (an addition): ``(mean (N+1, d,
+    p), var (N+1, d, p, p))`` with a leading batch axis for batched inputs -- ``daltonng_grid``'s joint filter, then
+    ``rodeo_amd.solve_mv_grid``'s smoothing pass with every step's own prior pair.  Arguments, the node rule and the refusals are
+    ``daltonng_grid``'s; with an empty observation set the result is ``rodeo_amd.solve_mv_grid``'s (the rule of
+    ``dalton.solve_mv_grid``)."""
+    who = "daltonng_grid (solve_mv_nn_grid)"
+    plan, g, oid, p_obs, p_node, n_obs = _ng_on_grid(who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data,
+                                                     obs_times, obs_loglik_i, kalman_type, params)
+    if n_obs == 0:                                                  # p(X | Z): rodeo_amd.solve_mv_grid itself
+        plan.launch(plan.dev.lib.rk_solve_grid, key, _lib.MODE_MV, _lib.MODE_MV, C.byref(g))
+    else:
+        plan.launch(plan.dev.lib.rk_daltonng_grid_solve, key, _lib.MODE_MV, _lib.MODE_MV, oid, p_obs, p_node, n_obs, C.byref(g))
+    if plan.layout != _lib.LAYOUT_BATCH_MINOR:
+        raise RuntimeError(f"{who}: the plan reports layout {plan.layout}, not the batch-minor records")
     return plan.state_host()
 
 
