@@ -411,6 +411,26 @@ int rk_dalton_grid_solve(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in
                          const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_ind,
                          int32_t n_obs, int32_t n_bobs, const rk_grid_in* g);
 
+/* dalton_grid_jvp (an addition): rk_dalton_grid_loglik's value and its directional derivatives, forward mode, with respect to
+ * the ODE parameters and the initial state.  The first ten arguments are rk_dalton_grid_loglik's.  n_dir >= 1 directions:
+ * dtheta (n_dir, n_theta), or (n_dir, n_theta, n_traj) batch-minor with dtheta_batched; dinit (n_dir, n_block, n_bstate), or
+ * (n_dir, n_block, n_bstate, n_traj) with dinit_batched; a NULL array is a zero direction in that argument.
+ * value (n_traj) = joint - marginal; dvalue (n_traj, n_dir), trajectory-major: dvalue[b n_dir + k] is the derivative of value[b]
+ * along direction k.  Both are overwritten, one writer per element, no atomics: two calls give the same bits.  It is the exact
+ * derivative of the filters' formulas as computed; a forecast term the value drops (|s| <= 1e-8) contributes nothing.
+ * One kernel (dalton_grid_jvp_kernel, dalton_grad_kernels.hpp): a (trajectory, direction) pair per lane pair; no workspace.
+ * Served: kalman_type standard, n_bmeas = 1, n_bobs = 1, interrogate rodeo / schober / kramer, fitzhugh_nagumo and lorenz63 at
+ * n_bstate 2..3, and a user right-hand side of the gradient kind (hiprtc, JIT_DALTON_GRAD) with n_block n_bstate^2 <= 27; cfg->flags must carry RK_FLAG_BATCH_MINOR.  What is not served is refused on cfg, n_bobs and n_dir
+ * alone -- RK_ERR_INVALID (a non-positive size, n_dir < 1, RK_FLAG_BATCH_MINOR missing) or RK_ERR_UNSUPPORTED ("not built") --
+ * before the handle or any pointer is looked at.                                                                          */
+int rk_dalton_grid_jvp(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const double* obs, const double* obs_weight,
+                       const double* obs_var, const int32_t* obs_ind, int32_t n_obs, int32_t n_bobs, const rk_grid_in* g,
+                       int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit, int32_t dinit_batched,
+                       double* value, double* dvalue);
+/* Build rk_dalton_grid_jvp's kernel for a registered right-hand side of the gradient kind (rodeo_amd.trace.trace_grad_source,
+ * registered as AutoJacG<struct>) without a device; RK_ERR_INVALID with the compiler's log otherwise.                    */
+int rk_dalton_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate);
+
 /* fenrir_grid (an addition): rk_fenrir_backward / rk_fenrir_solve_mv on rk_solve_grid's non-uniform grid, every observation on a
  * node.  Both entries run the forward pass of rk_solve_grid themselves (grid_fwd_kernel: out->mean_state / var_state receive
  * the batch-minor filtered moments; Fenrir's forward pass is free of data), then the backward Markov-chain filter with every

@@ -148,6 +148,8 @@ SIGNATURES = {
     "rk_solve_dynamic_grid": (C.c_int, [_H, _P, _P, _P, _I, C.POINTER(GridIn), _D, _P, _P]),
     "rk_dalton_grid_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _P]),
     "rk_dalton_grid_solve": (C.c_int, [_H, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn)]),
+    "rk_dalton_grid_jvp": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _I, _P, _I, _P, _I, _P, _P]),
+    "rk_dalton_grad_compile_check": (C.c_int, [_I, _I, _I]),
     "rk_fenrir_grid_loglik": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _P]),
     "rk_fenrir_grid_solve_mv": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _P]),
     "rk_solve_sim_draws":(C.c_int, [_H, _P, _P, _P, _I, _P, _I, _P]),

@@ -47,6 +47,14 @@ struct FitzHughNagumo {
         J[0][0] = th[2] * (1.0 - V * V);
         J[1][0] = -th[1] / th[2];
     }
+    // The same function on a generic scalar, parameters included (tangent.hpp): what the gradient kernels differentiate
+    // (dalton_grad_kernels.hpp); V^3 / 3 is a plain division there.  Nothing else instantiates it.
+    template <class T, class TH, int P>
+    __device__ __forceinline__ static void rhs_generic(const T (&X)[D][P], double, const TH (&th)[NTHETA], T (&out)[D]) {
+        const T V = X[0][0], R = X[1][0];
+        out[0] = th[2] * (V - V * V * V / 3.0 + R);
+        out[1] = -1.0 / th[2] * (V - th[0] + th[1] * R);
+    }
     // Optional "tile form" used by the MFMA-tile forward kernel (one (trajectory, block) per 16 lanes): every lane
     // evaluates only ITS block's f_b and J_b0 from own = X[b][0] and oth = X[1-b][0] through per-lane coefficients,
     //     f_b = k0 own + k1 own^3 + k2 oth + k3 ,   d f_b / d X[b][0] = k4 + k5 own^2 ,
@@ -93,6 +101,14 @@ struct Lorenz63 {
         J[0][0] = -th[1];
         J[1][0] = -1.0;
         J[2][0] = -th[2];
+    }
+    // the same function on a generic scalar, parameters included (tangent.hpp; FitzHughNagumo::rhs_generic)
+    template <class T, class TH, int P>
+    __device__ __forceinline__ static void rhs_generic(const T (&X)[D][P], double, const TH (&th)[NTHETA], T (&out)[D]) {
+        const T x = X[0][0], y = X[1][0], z = X[2][0];
+        out[0] = th[1] * y - th[1] * x;
+        out[1] = th[0] * x - y - x * z;
+        out[2] = x * y - th[2] * z;
     }
     static constexpr bool HAS_TILE_FORM = false;
     // Optional three-block "tile form" used by the p = 4 MFMA-tile forward kernel: every lane evaluates only ITS block's

@@ -82,6 +82,7 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_GRID_DYNAMIC       */ {"rk::grid_dynamic_fwd_kernel<rk::UserRhsT, {P}, {I}>", "grid_calib_kernels.hpp", "grid_dynamic_fwd_kernel<user>"},
     /* JIT_DALTONNG_GRID      */ {"rk::daltonng_grid_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, false>", "daltonng_grid_kernels.hpp", "daltonng_grid_fwd_kernel<store>"},
     /* JIT_DALTONNG_GRID_BOTH */ {"rk::daltonng_grid_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, true>", "daltonng_grid_kernels.hpp", "daltonng_grid_fwd_kernel<both>"},
+    /* JIT_DALTON_GRAD        */ {"rk::dalton_grid_jvp_kernel<rk::UserRhsT, {P}, {I}>", "dalton_grad_kernels.hpp", "dalton_grid_jvp_kernel<user>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -580,6 +581,30 @@ int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, con
                       params);
 }
 
+// dalton_grid_jvp around a user right-hand side of the gradient kind (dalton_grad_kernels.hpp): the configuration against the
+// registration (n_block, n_bmeas = 1) and the size limit of the built-in instances that ship (n_bstate 2 .. 3, n_block n_bstate^2
+// <= 27: DESIGN.md section 7 (21)), then the launch, one (trajectory, direction) item per lane pair like dalton_grad.hip's.
+int user_dalton_grad_check(const rk_solve_cfg* c) {
+    const UserRhs* u;
+    const int rc = user_rhs(c->rhs_id, &u);
+    if (rc) return rc;
+    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
+               "dalton_grid_jvp: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
+    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 3 && c->n_block * c->n_bstate * c->n_bstate <= 27, RK_ERR_UNSUPPORTED,
+               "dalton_grid_jvp: not built: user rhs %d with %d blocks at n_bstate %d (n_bstate 2..3, n_block n_bstate^2 <= 27)",
+               c->rhs_id, c->n_block, c->n_bstate);
+    return RK_OK;
+}
+
+int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, const JvpDirs& dir,
+                     int n_items, double* value, double* dvalue) {
+    const int rc = user_dalton_grad_check(c);
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&o, (void*)&g, (void*)&dir, &value, &dvalue};
+    return launch_jit(h, jit_key(JIT_DALTON_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, true), params);
+}
+
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm) {
     const int rc = user_rhs_check(c);
@@ -715,6 +740,17 @@ int rk_rhs_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) 
     rc = jit_lookup(jit_key(dense ? JIT_DENSE_ITG : (u->n_bmeas > 1 ? JIT_FWD_M : JIT_FWD), rhs_id, &c), nullptr, nullptr);
     if (rc == RK_OK && !dense && u->n_bmeas > 1) rc = jit_lookup(jit_key(JIT_ITG_M, rhs_id, &c), nullptr, nullptr);     // + the standalone interrogation
     return rc;
+}
+
+// the gradient kind's build for a registered right-hand side, without a device (what rk_rhs_compile_check is for the solver)
+int rk_dalton_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
+    const UserRhs* u;
+    const int rc = user_rhs(rhs_id, &u);
+    if (rc) return rc;
+    rk_solve_cfg c{};
+    c.n_bstate = n_bstate;
+    c.interrogate = interrogate;
+    return jit_lookup(jit_key(JIT_DALTON_GRAD, rhs_id, &c), nullptr, nullptr);
 }
 
 }  // extern "C"

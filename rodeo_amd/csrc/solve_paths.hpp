@@ -66,6 +66,7 @@ enum JitKind : int {
     JIT_GRID_DYNAMIC = 28,    // grid_dynamic_fwd_kernel (solve_mv_dynamic_grid / solve_sim_dynamic_grid, the forward lanes)
     JIT_DALTONNG_GRID = 29,   // daltonng_grid_fwd_kernel<.., false> (solve_mv_nn_grid, the joint filter's moments)
     JIT_DALTONNG_GRID_BOTH = 30,  // daltonng_grid_fwd_kernel<.., true> (daltonng_grid, the joint filter and the filter on Z alone)
+    JIT_DALTON_GRAD = 31,     // dalton_grid_jvp_kernel (dalton_grid_jvp: value and directional derivatives; a gradient-kind source)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -112,6 +113,12 @@ int dalton_grid_store_forward(rk_handle h, const rk_solve_cfg* c, const SolveArg
 int user_dalton_grid_check(const rk_solve_cfg* c);
 int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
                      bool store, double* out);
+// dalton_grid_jvp: the configuration against the registration and the launch (dalton_grad.hip); the right-hand side must be of
+// the gradient kind (AutoJacG around a struct with rhs_generic: rodeo_amd.trace.trace_grad_source), else the build fails
+struct JvpDirs;
+int user_dalton_grad_check(const rk_solve_cfg* c);
+int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, const JvpDirs& dir,
+                     int n_items, double* value, double* dvalue);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them

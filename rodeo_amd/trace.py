@@ -169,6 +169,62 @@ struct {struct_name} {{
     return src, ndep, n_bmeas
 
 
+def trace_grad_source(fun, n_vars, n_deriv_used, param_spec, struct_name):
+    """The second emitter, for the gradient kind (``rodeo_amd.inference.dalton.dalton_grid_jvp``): run ``fun`` on symbols like
+    ``trace_source`` and return (source, ndep) of a struct whose one member ``rhs_generic<T, TH, P>`` is generic in the parameters
+    as well (``const TH (&th)[NTHETA]``), so that forward-mode scalars (csrc/tangent.hpp) carry a direction in theta through
+    it; ``rk::AutoJacG`` (csrc/dalton_grad_kernels.hpp) makes a complete right-hand side of it.  n_bmeas = 1 only (ValueError).
+    What ``trace_source`` emits is not touched: its sources, and the cache keys made from them, stay what they are."""
+    X = _symbols((n_vars, n_deriv_used), lambda b, j: f"X[{b}][{j}]")
+    params, off = {}, 0
+    for name, size in param_spec:
+        params[name] = _symbols((size,), lambda k, off=off: f"th[{off + k}]")
+        off += size
+    out = np.asarray(fun(X, Sym("t"), **params), dtype=object)
+    if out.shape == (n_vars,):
+        out = out[:, None]
+    if out.shape != (n_vars, 1):
+        raise ValueError(f"the gradient kind needs an ode_fun that returns shape ({n_vars}, 1) (n_bmeas = 1), got {out.shape}")
+    body = "\n".join(f"        out[{b}] = {Sym._c(out[b, 0])};" for b in range(n_vars))
+    used = [j for b in range(n_vars) for j in range(n_deriv_used) if f"X[{b}][{j}]" in body]
+    ndep = max(used) + 1 if used else 1
+    src = f"""
+// generated by rodeo_amd.trace (gradient kind) from the Python function {getattr(fun, '__name__', 'ode_fun')!r}
+struct {struct_name} {{
+    static constexpr int D = {n_vars};
+    static constexpr int NTHETA = {max(off, 1)};
+    static constexpr int NDEP = {ndep};
+    template <class T, class TH, int P>
+    __device__ __forceinline__ static void rhs_generic(const T (&X)[D][P], double t, const TH (&th)[NTHETA], T (&out)[D]) {{
+        static_assert(P >= NDEP, "the right-hand side reads more derivatives than the prior carries");
+{body}
+    }}
+}};
+"""
+    return src, ndep
+
+
+_grad_cache = {}
+
+
+def grad_from_python(fun, n_vars, n_deriv_used=2, name=None, **param_sizes):
+    """``DeviceODE`` of the gradient kind from an ordinary Python right-hand side (``from_python``'s arguments): registered as
+    ``AutoJacG<struct>``, it serves ``dalton_grid_jvp`` / ``dalton_grid_grad`` / ``dalton_grad`` and nothing else."""
+    from . import ode
+    spec = tuple((k, int(v)) for k, v in param_sizes.items())
+    key = (fun, int(n_vars), int(n_deriv_used), spec)
+    if key in _grad_cache:
+        return _grad_cache[key]
+    probe_src, _ = trace_grad_source(fun, n_vars, n_deriv_used, spec, "TracedGradOde")
+    struct = f"TracedGrad_{hashlib.sha1(probe_src.encode()).hexdigest()[:10]}"
+    src, ndep = trace_grad_source(fun, n_vars, n_deriv_used, spec, struct)
+    dev = ode.from_source(f"AutoJacG<{struct}>", src, n_vars, spec, _host_twin(fun, n_vars, 1),
+                          name=name or getattr(fun, "__name__", struct))
+    dev.source, dev.ndep, dev.grad_kind = src, ndep, True
+    _grad_cache[key] = dev
+    return dev
+
+
 def gammaln(x):
     """log Gamma(x) for floats and for traced symbols (device ``lgamma``), e.g. the ``log y!`` of a Poisson log-pmf.  A symbol
     that depends on the state is refused: the device has no digamma / trigamma to differentiate it with."""
@@ -275,5 +331,6 @@ def from_python(fun, n_vars, n_deriv_used=2, name=None, **param_sizes):
     dev = ode.from_source(f"{wrapper}<{struct}>", src, n_vars, spec, _host_twin(fun, n_vars, n_bmeas),
                           name=name or getattr(fun, "__name__", struct), n_bmeas=n_bmeas)
     dev.source, dev.ndep = src, ndep
+    dev.traced_from = (fun, int(n_vars), int(n_deriv_used), spec)      # what grad_from_python needs to trace it again
     _cache[key] = dev
     return dev
