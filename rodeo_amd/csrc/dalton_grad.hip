@@ -2,11 +2,13 @@
 // directional derivatives of rk_dalton_grid_loglik's value with respect to the ODE parameters and the initial state.  One
 // route: dalton_grid_jvp_kernel (dalton_grad_kernels.hpp), one (trajectory, direction) item per lane pair, 32 items per wave.
 // Standard form, n_bmeas = 1, n_bobs = 1, built-in FitzHugh-Nagumo and Lorenz63, or a user right-hand side of the gradient kind
-// (hiprtc, rhs_jit.hip's JIT_DALTON_GRAD).  No workspace.
+// (hiprtc, rhs_jit.hip's JIT_DALTON_GRAD).  No workspace.  The sizes test, the grid's staging (through dalton_grid_inputs) and
+// the launch patterns are grid_entry.hpp's; the rest of the configuration check is worded for this entry alone ("not built: ...").
 #include "common.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "dalton_grad_kernels.hpp"
 
 namespace rk {
@@ -29,9 +31,8 @@ constexpr bool dalton_grad_has_rhs() { return std::is_same<RHS, FitzHughNagumo>:
 
 // Is this call served?  Decided on the configuration, n_bobs and n_dir alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
 static int dalton_grad_check(const rk_solve_cfg* c, int n_bobs, int n_dir) {
-    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
-               "dalton_grid_jvp: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", c->n_traj,
-               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
+    const int rc = grid_sizes_check("dalton_grid_jvp", c);               // (grid_entry.hpp; from here on the wording is this entry's own)
+    if (rc) return rc;
     RK_REQUIRE(n_dir >= 1, RK_ERR_INVALID, "dalton_grid_jvp: n_dir must be at least 1, got %d", n_dir);
     RK_REQUIRE((long long)c->n_traj * n_dir <= 0x7fffffffLL, RK_ERR_INVALID, "dalton_grid_jvp: n_traj * n_dir = %lld exceeds 2^31 - 1",
                (long long)c->n_traj * n_dir);
@@ -61,23 +62,21 @@ static int dalton_grad_check(const rk_solve_cfg* c, int n_bobs, int n_dir) {
     return RK_OK;
 }
 
-template <class RHS>
-static int launch_dalton_grid_jvp(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
+static int dalton_grid_jvp_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
                                   const JvpDirs& dir, double* value, double* dvalue) {
-    const LaunchGeom g = dalton_lane_geom(a.B * dir.K, true);               // 32 (trajectory, direction) items per wave
-    bool ok = false;
-    dispatch_int<2, dalton_grad_pmax<RHS>()>(c->n_bstate, [&](auto P) {
-        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
-            LaunchTimer t(h, "dalton_grid_jvp_kernel");
-            hipLaunchKernelGGL((dalton_grid_jvp_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, o, ga, dir, value, dvalue);
-            t.stop();
-            ok = true;
-        });
+    return launch_by_rhs(c, a, [&] { return user_dalton_grad(h, c, a, o, ga, dir, a.B * dir.K, value, dvalue); }, [&](auto rhs) {
+        using RHS = decltype(rhs);
+        if constexpr (dalton_grad_has_rhs<RHS>()) {
+            const LaunchGeom g = dalton_lane_geom(a.B * dir.K, true);       // 32 (trajectory, direction) items per wave
+            // (one writer per element: nothing to clear)
+            return launch_fwd_instance<2, dalton_grad_pmax<RHS>(), RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
+                h, c, "dalton_grid_jvp_kernel", "dalton_grid_jvp", [&](auto P, auto I) {
+                    hipLaunchKernelGGL((dalton_grid_jvp_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, o, ga, dir, value, dvalue);
+                });
+        } else {
+            return (int)RK_ERR_UNSUPPORTED;                                 // (dalton_grad_check has refused it)
+        }
     });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dalton_grid_jvp: no kernel for rhs %d, n_bstate %d, interrogate %d", c->rhs_id, c->n_bstate,
-               c->interrogate);
-    RK_HIP(hipGetLastError());
-    return RK_OK;
 }
 
 }  // namespace rk
@@ -103,17 +102,7 @@ int rk_dalton_grid_jvp(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
     SolveArgs a;
     make_args(c, in, nullptr, a);
     const JvpDirs dir{dtheta, dinit, dtheta_batched != 0, dinit_batched != 0, n_dir};
-    if (is_user_rhs(c->rhs_id)) return user_dalton_grad(h, c, a, o, ga, dir, a.B * n_dir, value, dvalue);
-    rc = RK_ERR_UNSUPPORTED;
-    with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-        using RHS = decltype(rhs);
-        if constexpr (dalton_grad_has_rhs<RHS>()) {
-            rc = check_n_theta<RHS>(c, a);
-            if (rc) return;
-            rc = launch_dalton_grid_jvp<RHS>(h, c, a, o, ga, dir, value, dvalue);   // (one writer per element: nothing to clear)
-        }
-    });
-    return rc;
+    return dalton_grid_jvp_launch(h, c, a, o, ga, dir, value, dvalue);
 }
 
 }  // extern "C"

@@ -3,10 +3,13 @@
 // observation on a node.  One route: the lanes on batch-minor records -- dalton_grid_fwd_kernel (dalton_grid_kernels.hpp), two
 // filters per trajectory in the halves of a wave for the log-likelihood, one lane per trajectory for the store form, then
 // grid.hip's own backward launch (grid_bwd_mv_kernel / grid_bwd_sim_kernel).  Standard form, n_bmeas = 1.  No workspace.
+// The pieces of the configuration check, the grid's staging and the right-hand-side switch are grid_entry.hpp's; the forward
+// launch stays written out here: it dispatches on n_bobs as well and decides per instance whether there is a kernel at all.
 #include "common.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "dalton_grid_kernels.hpp"
 
 namespace rk {
@@ -24,11 +27,16 @@ constexpr bool dalton_grid_ships() {
     return !(std::is_same<RHS, FitzHughNagumo>::value && P == 4 && MO == 3 && !STORE);
 #endif
 }
+// n_bstate served: dalton's lane range (dalton_pmax<RHS>() of solve_paths.hpp is the built-in instances' upper end)
+constexpr int DALTON_GRID_PMIN = 2, DALTON_GRID_PMAX = 6, DALTON_GRID_PMAX_THREE_BLOCKS = 5;
+static_assert(dalton_pmax<FitzHughNagumo>() == DALTON_GRID_PMAX && dalton_pmax<Lorenz63>() == DALTON_GRID_PMAX_THREE_BLOCKS,
+              "the check's limits are the instances'");
+
 // (also asked by rk_dalton_grid_sim_draws, grid_draws.hip: declared in solve_paths.hpp)
 bool dalton_grid_left_out(const rk_solve_cfg* c, int n_bobs, bool store) {
     bool out = false;
     with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-        dispatch_int<2, 6>(c->n_bstate, [&](auto P) {
+        dispatch_int<DALTON_GRID_PMIN, DALTON_GRID_PMAX>(c->n_bstate, [&](auto P) {
             dispatch_int<1, 3>(n_bobs, [&](auto M) {
                 out = store ? !dalton_grid_ships<decltype(rhs), P, M, true>() : !dalton_grid_ships<decltype(rhs), P, M, false>();
             });
@@ -38,31 +46,20 @@ bool dalton_grid_left_out(const rk_solve_cfg* c, int n_bobs, bool store) {
 }
 
 // Is this call served?  Decided on the configuration, the mode and n_bobs alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
-// grid_check's pattern (grid.hip) joined with dalton_check's limits (dalton.hip).  mode < 0: the log-likelihood, which has none.
+// grid_check's pattern (grid.hip; the pieces are grid_entry.hpp's) joined with dalton_check's limits (dalton.hip).  mode < 0: the
+// log-likelihood, which has none.
 static int dalton_grid_check(const rk_solve_cfg* c, int mode, int n_bobs) {
-    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
-               "dalton_grid: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", c->n_traj,
-               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
+    int rc = grid_sizes_check("dalton_grid", c);
+    if (rc) return rc;
     RK_REQUIRE(mode < 0 || mode == RK_MODE_MV || mode == RK_MODE_SIM, RK_ERR_INVALID,
                "dalton_grid: mode must be RK_MODE_MV or RK_MODE_SIM, got %d", mode);
-    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "dalton_grid: cfg->flags must carry RK_FLAG_BATCH_MINOR (the "
-               "records are the batch-minor ones)");
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "dalton_grid: RK_FLAG_STORE_PRED is not served");
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
-               "dalton_grid: unknown kalman_type %d", c->kalman_type);
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "dalton_grid: kalman_type square-root is not built");
-    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_KRAMER, RK_ERR_UNSUPPORTED,
-               "dalton_grid: interrogate id %d is not supported (rodeo, schober, kramer)", c->interrogate);
-    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "dalton_grid: n_bmeas = 1 only (the dense / indep_init form is not served), "
-               "got %d", c->n_bmeas);
-    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 6, RK_ERR_UNSUPPORTED, "dalton_grid: n_bstate in 2..6, got %d", c->n_bstate);
-    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= 5, RK_ERR_UNSUPPORTED,
-               "dalton_grid: n_bstate up to 5 with three or more blocks, got %d", c->n_bstate);
+    rc = grid_served_check({"dalton_grid", GRID_RECORDS, RK_INTERROGATE_KRAMER, nullptr, DALTON_GRID_PMIN, DALTON_GRID_PMAX,
+                            DALTON_GRID_PMAX_THREE_BLOCKS}, c);
+    if (rc) return rc;
     RK_REQUIRE(n_bobs >= 1 && n_bobs <= 3, RK_ERR_UNSUPPORTED, "dalton_grid: n_bobs in 1..3, got %d", n_bobs);
-    if (is_user_rhs(c->rhs_id)) return user_dalton_grid_check(c);
-    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "dalton_grid: unknown rhs_id %d", c->rhs_id);
-    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "dalton_grid: rhs %d needs another n_block than %d",
-               c->rhs_id, c->n_block);
+    rc = grid_rhs_check("dalton_grid", c);
+    if (rc) return rc;
+    // (never so for a user right-hand side: it has no instance to leave out)
     RK_REQUIRE(!dalton_grid_left_out(c, n_bobs, mode >= 0), RK_ERR_UNSUPPORTED,
                "dalton_grid: the %s form of rhs %d at n_bstate %d with n_bobs %d is left out (it needs more scratch than dalton's "
                "and the grid solver's kernels at the same parameters)", mode >= 0 ? "store" : "log-likelihood", c->rhs_id,
@@ -76,7 +73,7 @@ static int launch_dalton_grid_rhs(rk_handle h, const rk_solve_cfg* c, const Solv
                                   int n_bobs, double* logdens) {
     const LaunchGeom g = dalton_lane_geom(a.B, !STORE);
     bool ok = false;
-    dispatch_int<2, dalton_pmax<RHS>()>(c->n_bstate, [&](auto P) {
+    dispatch_int<DALTON_GRID_PMIN, dalton_pmax<RHS>()>(c->n_bstate, [&](auto P) {
         dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
             dispatch_int<1, 3>(n_bobs, [&](auto M) {
                 if constexpr (dalton_grid_ships<RHS, P, M, STORE>()) {
@@ -97,15 +94,9 @@ static int launch_dalton_grid_rhs(rk_handle h, const rk_solve_cfg* c, const Solv
 template <bool STORE>
 static int dalton_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
                                int n_bobs, double* logdens) {
-    if (is_user_rhs(c->rhs_id)) return user_dalton_grid(h, c, a, o, ga, n_bobs, STORE, logdens);
-    int rc = RK_ERR_UNSUPPORTED;
-    with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-        using RHS = decltype(rhs);
-        rc = check_n_theta<RHS>(c, a);
-        if (rc) return;
-        rc = launch_dalton_grid_rhs<RHS, STORE>(h, c, a, o, ga, n_bobs, logdens);
+    return launch_by_rhs(c, a, [&] { return user_dalton_grid(h, c, a, o, ga, n_bobs, STORE, logdens); }, [&](auto rhs) {
+        return launch_dalton_grid_rhs<decltype(rhs), STORE>(h, c, a, o, ga, n_bobs, logdens);
     });
-    return rc;
 }
 
 // the store form's forward pass (also that of rk_dalton_grid_sim_draws, grid_draws.hip: declared in solve_paths.hpp)
@@ -119,14 +110,13 @@ int dalton_grid_store_forward(rk_handle h, const rk_solve_cfg* c, const SolveArg
 int dalton_grid_inputs(const char* who, const rk_solve_cfg* c, const rk_solve_in* in, const double* obs,
                        const double* obs_weight, const double* obs_var, const int32_t* obs_ind, int n_obs, const rk_grid_in* g,
                        DaltonObs& o, GridArgs& ga) {
-    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
-               "%s: grid needs t, slot, q, r and n_slots >= 1 (got %d)", who, g->n_slots);
-    const int rc = check_cfg(c, in);
+    int rc = grid_args(who, g, ga);
+    if (rc) return rc;
+    rc = check_cfg(c, in);
     if (rc) return rc;
     RK_REQUIRE(n_obs >= 0 && (n_obs == 0 || (obs && obs_weight && obs_var && obs_ind)), RK_ERR_INVALID,
                "%s: null observation array or n_obs < 0", who);
     o.obs = obs; o.obs_w = obs_weight; o.obs_v = obs_var; o.obs_ind = obs_ind; o.n_obs = n_obs;
-    ga = GridArgs{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
     return RK_OK;
 }
 
@@ -166,9 +156,8 @@ int rk_dalton_grid_solve(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* 
     GridArgs ga;
     rc = dalton_grid_inputs("rk_dalton_grid_solve", c, in, obs, obs_weight, obs_var, obs_ind, n_obs, g, o, ga);
     if (rc) return rc;
-    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID,
-               "rk_dalton_grid_solve: out->mean_state / var_state must not be NULL");
-    RK_REQUIRE(mode != RK_MODE_SIM || out->x_state, RK_ERR_INVALID, "rk_dalton_grid_solve: RK_MODE_SIM needs out->x_state");
+    rc = grid_out_check("rk_dalton_grid_solve", out, mode);
+    if (rc) return rc;
     rc = begin_solve(h);
     if (rc) return rc;
     SolveArgs a;

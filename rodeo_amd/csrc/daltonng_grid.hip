@@ -4,10 +4,13 @@
 // daltonng_grid_kernels.hpp); the gain kernel of the two backward log-density passes is built here, with every step's own prior
 // pair; the chain and observation kernels are rk_daltonng_loglik's own, which read records and never the prior, and
 // rk_daltonng_grid_solve ends in rk_solve_grid's smoothing pass.  The workspace is rk_daltonng_workspace_bytes's.
+// The pieces of the configuration check ahead of ng_check, the grid's staging and the test of the output pointers are
+// grid_entry.hpp's.
 #include "common.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "grid_kernels.hpp"
 #include "daltonng_kernels.hpp"
 
@@ -58,33 +61,29 @@ __global__ void __launch_bounds__(64) daltonng_grid_gain_kernel(SolveArgs a, NgW
 }
 
 // Is this call served?  Decided on the configuration, the mode and the registered model alone: RK_OK, RK_ERR_INVALID or
-// RK_ERR_UNSUPPORTED.  dalton_grid_check's pattern (dalton_grid.hip) joined with rk_daltonng_*'s limits (ng_check).
+// RK_ERR_UNSUPPORTED.  dalton_grid_check's pattern (dalton_grid.hip; the pieces are grid_entry.hpp's) joined with rk_daltonng_*'s
+// limits (ng_check).
 // mode < 0: the log-likelihood, which has none.
 static int ng_grid_check(const rk_solve_cfg* c, int mode, int obs_id) {
     const char* who = "daltonng_grid";
-    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
-               "%s: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", who, c->n_traj, c->n_steps,
-               c->n_block, c->n_bstate, c->n_bmeas);
+    int rc = grid_sizes_check(who, c);
+    if (rc) return rc;
     RK_REQUIRE(mode < 0 || mode == RK_MODE_FILTER || mode == RK_MODE_MV, RK_ERR_INVALID,
                "%s: mode must be RK_MODE_FILTER or RK_MODE_MV (the uniform-grid form has no sampler either), got %d", who, mode);
-    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "%s: cfg->flags must carry RK_FLAG_BATCH_MINOR (the records "
-               "are the batch-minor ones)", who);
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "%s: RK_FLAG_STORE_PRED is not served", who);
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
-               "%s: unknown kalman_type %d", who, c->kalman_type);
+    rc = grid_flags_check(who, GRID_RECORDS, c);
+    if (rc) return rc;
     return ng_check(who, c, obs_id);
 }
 
 // the pointers of a served call: the grid (rk_solve_grid's rule), the solver inputs and the observations
 static int ng_grid_inputs(const char* who, const rk_solve_cfg* c, const rk_solve_in* in, const double* obs, const int32_t* obs_node,
                           int n_obs, const rk_grid_in* g, NgObs& o, GridArgs& ga) {
-    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
-               "%s: grid needs t, slot, q, r and n_slots >= 1 (got %d)", who, g->n_slots);
-    const int rc = check_cfg(c, in);
+    int rc = grid_args(who, g, ga);
+    if (rc) return rc;
+    rc = check_cfg(c, in);
     if (rc) return rc;
     RK_REQUIRE(n_obs >= 0 && (n_obs == 0 || (obs && obs_node)), RK_ERR_INVALID, "%s: null observation array or n_obs < 0", who);
     o.y = obs; o.obs_ind = obs_node; o.n_obs = n_obs;
-    ga = GridArgs{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
     return RK_OK;
 }
 
@@ -143,8 +142,8 @@ int rk_daltonng_grid_solve(rk_handle h, const rk_solve_cfg* c, const rk_solve_in
     GridArgs ga;
     rc = ng_grid_inputs("rk_daltonng_grid_solve", c, in, obs, obs_node, n_obs, g, o, ga);
     if (rc) return rc;
-    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID,
-               "rk_daltonng_grid_solve: out->mean_state / var_state must not be NULL");
+    rc = grid_out_check("rk_daltonng_grid_solve", out, mode);        // (FILTER or MV: no sampler)
+    if (rc) return rc;
     rc = begin_solve(h);
     if (rc) return rc;
     SolveArgs a;

@@ -9,6 +9,7 @@
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "dynamic_kernels.hpp"
 #include "lane_backward.hpp"
 
@@ -76,44 +77,36 @@ static int dynamic_check(const rk_solve_cfg* c, int mode, double scale_min) {
     RK_REQUIRE(c->n_block < 3 || c->n_bstate <= DYNAMIC_PMAX_THREE_BLOCKS, RK_ERR_UNSUPPORTED,
                "dynamic: n_bstate up to %d with three or more blocks (the lane kernel spills more than solve_evidence's), got %d",
                DYNAMIC_PMAX_THREE_BLOCKS, c->n_bstate);
-    if (is_user_rhs(c->rhs_id)) return user_dynamic_check(c);
+    if (is_user_rhs(c->rhs_id)) return user_lane_check(c, "dynamic");
     RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "dynamic: unknown rhs_id %d", c->rhs_id);
     RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "dynamic: rhs %d needs another n_block than %d",
                c->rhs_id, c->n_block);
     return RK_OK;
 }
 
-template <class RHS>
-static int launch_dynamic_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double scale_min, double* scale,
-                              double* logdens) {
-    const LaunchGeom g = fwd_lane_geom(a.B);
-    bool ok = false;
-    dispatch_int<DYNAMIC_PMIN, dynamic_pmax<RHS>()>(c->n_bstate, [&](auto P) {
-        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
-            LaunchTimer t(h, "dynamic_fwd_kernel");
-            hipLaunchKernelGGL((dynamic_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, scale_min, scale, logdens);
-            t.stop();
-            ok = true;
-        });
-    });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dynamic: no kernel for rhs %d, n_bstate %d, interrogate %d", c->rhs_id, c->n_bstate,
-               c->interrogate);
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
+// ---- launches (grid_entry.hpp's patterns) -------------------------------------------------------------------------------
+// The backward launch stands first: a kernel is emitted where its launch is first seen, and the code object keeps the order it
+// has had -- the backward kernels, then dynamic_fwd_kernel's instances.
 static int launch_dynamic_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const double* scale) {
     const LaunchGeom g = bwd_lane_geom(a.B, a.D);
-    const bool sim = mode == RK_MODE_SIM;
-    LaunchTimer t(h, sim ? "dynamic_bwd_sim_kernel" : "dynamic_bwd_mv_kernel");
-    const bool ok = dispatch_int<DYNAMIC_PMIN, DYNAMIC_PMAX>(c->n_bstate, [&](auto P) {
+    return launch_bwd_instance<DYNAMIC_PMIN, DYNAMIC_PMAX>(h, c, mode, "dynamic_bwd_mv_kernel", "dynamic_bwd_sim_kernel", "dynamic",
+                                                           [&](auto P, bool sim) {
         if (sim) hipLaunchKernelGGL((dynamic_bwd_sim_kernel<P>), g.grid, g.block, 0, h->stream, a, scale);
         else hipLaunchKernelGGL((dynamic_bwd_mv_kernel<P>), g.grid, g.block, 0, h->stream, a, scale);
     });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dynamic: no backward kernel for n_bstate %d", c->n_bstate);
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
+}
+
+// the forward pass for a built-in or a user right-hand side
+static int dynamic_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double scale_min, double* scale,
+                           double* logdens) {
+    return launch_by_rhs(c, a, [&] { return user_dynamic(h, c, a, scale_min, scale, logdens); }, [&](auto rhs) {
+        using RHS = decltype(rhs);
+        const LaunchGeom g = fwd_lane_geom(a.B);
+        return launch_fwd_instance<DYNAMIC_PMIN, dynamic_pmax<RHS>(), RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
+            h, c, "dynamic_fwd_kernel", "dynamic", [&](auto P, auto I) {
+                hipLaunchKernelGGL((dynamic_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, scale_min, scale, logdens);
+            });
+    });
 }
 
 }  // namespace rk
@@ -136,17 +129,7 @@ int rk_solve_dynamic(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, 
     if (rc) return rc;
     SolveArgs a;
     make_args(c, in, out, a);
-    if (is_user_rhs(c->rhs_id)) {
-        rc = user_dynamic(h, c, a, scale_min, scale, logdens);
-    } else {
-        rc = RK_ERR_UNSUPPORTED;
-        with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-            using RHS = decltype(rhs);
-            rc = check_n_theta<RHS>(c, a);
-            if (rc) return;
-            rc = launch_dynamic_fwd<RHS>(h, c, a, scale_min, scale, logdens);
-        });
-    }
+    rc = dynamic_forward(h, c, a, scale_min, scale, logdens);
     if (rc) return rc;
     return launch_dynamic_bwd(h, c, a, mode, scale);
 }

@@ -35,7 +35,7 @@ static int evidence_check(const rk_solve_cfg* c) {
     RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= hi, RK_ERR_UNSUPPORTED, "evidence: n_bstate in 2..%d (%s form), got %d", hi,
                sq ? "square-root" : "standard", c->n_bstate);
     if (is_user_rhs(c->rhs_id)) {
-        const int rc = user_evidence_check(c);                      // (n_block / n_bmeas of the registration; the range is the one above)
+        const int rc = user_lane_check(c, "evidence");               // (n_block / n_bmeas of the registration; the range is the one above)
         if (rc) return rc;
         RK_REQUIRE(sq || c->n_block < 3 || c->n_bstate <= 5, RK_ERR_UNSUPPORTED,
                    "evidence: n_bstate up to 5 with three or more blocks (the lane kernel spills), got %d", c->n_bstate);

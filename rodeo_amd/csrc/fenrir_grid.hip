@@ -4,12 +4,13 @@
 // (grid_fwd_kernel, one lane per trajectory; Fenrir's forward pass is free of data), then fenrir_grid_bwd_kernel, one lane per
 // (block, trajectory), and for the solver fenrir.hip's own smoothing sweep (fenrir_smooth_kernel), which reads only the stored
 // backward filter and knows nothing of step lengths.  Standard form, n_bmeas = 1.  Ahead-of-time code only: the backward pass
-// has no right-hand side.
-#include <string>
+// has no right-hand side.  The pieces of the configuration check, the grid's staging and the test of the output pointers are
+// grid_entry.hpp's.
 #include "common.hpp"
 #include "kalman_small.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "grid_kernels.hpp"
 #include "fenrir_kernels.hpp"
 #include "records.hpp"
@@ -118,38 +119,18 @@ __global__ void __launch_bounds__(64) fenrir_grid_bwd_kernel(SolveArgs a, Dalton
 // to the two (scripts/fenrir_grid_code_objects.py): all 30 keep the rule -- none up to n_bstate 4 uses scratch, at 5 and 6 they
 // need less than grid_bwd_mv_kernel, which holds the same two pairs and two records -- so none is left out.
 
+constexpr int FENRIR_GRID_PMIN = 2, FENRIR_GRID_PMAX = 6, FENRIR_GRID_PMAX_THREE_BLOCKS = 5;
+
 // Is this call served?  Decided on the configuration and n_bobs alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
-// grid_check's pattern (grid.hip) with fenrir's n_bobs.
+// grid_check's pattern (grid.hip; the pieces are grid_entry.hpp's) with fenrir's n_bobs.
 static int fenrir_grid_check(const rk_solve_cfg* c, int n_bobs) {
-    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
-               "fenrir_grid: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", c->n_traj,
-               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
-    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "fenrir_grid: cfg->flags must carry RK_FLAG_BATCH_MINOR (the "
-               "records are the batch-minor ones)");
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "fenrir_grid: RK_FLAG_STORE_PRED is not served");
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
-               "fenrir_grid: unknown kalman_type %d", c->kalman_type);
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "fenrir_grid: kalman_type square-root is not built");
-    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_CHKREBTII, RK_ERR_UNSUPPORTED,
-               "fenrir_grid: interrogate id %d is not supported (rodeo, schober, kramer, chkrebtii)", c->interrogate);
-    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "fenrir_grid: n_bmeas = 1 only (the dense / indep_init form is not served), "
-               "got %d", c->n_bmeas);
-    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 6, RK_ERR_UNSUPPORTED, "fenrir_grid: n_bstate in 2..6, got %d", c->n_bstate);
-    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= 5, RK_ERR_UNSUPPORTED,
-               "fenrir_grid: n_bstate up to 5 with three or more blocks, got %d", c->n_bstate);
+    int rc = grid_sizes_check("fenrir_grid", c);
+    if (rc) return rc;
+    rc = grid_served_check({"fenrir_grid", GRID_RECORDS, RK_INTERROGATE_CHKREBTII, nullptr, FENRIR_GRID_PMIN, FENRIR_GRID_PMAX,
+                            FENRIR_GRID_PMAX_THREE_BLOCKS}, c);
+    if (rc) return rc;
     RK_REQUIRE(n_bobs >= 1 && n_bobs <= 3, RK_ERR_UNSUPPORTED, "fenrir_grid: n_bobs in 1..3, got %d", n_bobs);
-    if (is_user_rhs(c->rhs_id)) {
-        const int rc = user_grid_check(c);                          // (the forward pass is the grid solver's: its rule, our name)
-        if (rc) {
-            const std::string why = rk_last_error();
-            set_error("fenrir_grid: %s", why.c_str());
-        }
-        return rc;
-    }
-    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "fenrir_grid: unknown rhs_id %d", c->rhs_id);
-    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "fenrir_grid: rhs %d needs another n_block than %d",
-               c->rhs_id, c->n_block);
-    return RK_OK;
+    return grid_rhs_check("fenrir_grid", c, "grid");                // (the forward pass is the grid solver's: its rule, our name)
 }
 
 template <bool STORE>
@@ -158,7 +139,7 @@ static int launch_fenrir_grid_bwd(rk_handle h, const rk_solve_cfg* c, const Solv
     const LaunchGeom g = bwd_lane_geom(a.B, a.D);
     bool ok = false;
     LaunchTimer t(h, "fenrir_grid_bwd_kernel");
-    dispatch_int<2, 6>(c->n_bstate, [&](auto P) {
+    dispatch_int<FENRIR_GRID_PMIN, FENRIR_GRID_PMAX>(c->n_bstate, [&](auto P) {
         dispatch_int<1, 3>(n_bobs, [&](auto M) {
             hipLaunchKernelGGL((fenrir_grid_bwd_kernel<P, STORE, M>), g.grid, g.block, 0, h->stream, a, o, ga, part, states);
             ok = true;
@@ -175,18 +156,18 @@ static int launch_fenrir_grid_bwd(rk_handle h, const rk_solve_cfg* c, const Solv
 static int fenrir_grid_forward(const char* who, rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out,
                                const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_node, int n_obs,
                                const rk_grid_in* g, SolveArgs& a, DaltonObs& o, GridArgs& ga) {
-    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
-               "%s (fenrir_grid): grid needs t, slot, q, r and n_slots >= 1 (got %d)", who, g->n_slots);
-    int rc = check_cfg(c, in);
+    int rc = grid_args(who, g, ga);
+    if (rc) return rc;
+    rc = check_cfg(c, in);
     if (rc) return rc;
     RK_REQUIRE(n_obs >= 0 && (n_obs == 0 || (obs && obs_weight && obs_var && obs_node)), RK_ERR_INVALID,
-               "%s (fenrir_grid): null observation array or n_obs < 0", who);
-    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID, "%s (fenrir_grid): out->mean_state / var_state must not be NULL", who);
+               "%s: null observation array or n_obs < 0", who);
+    rc = grid_out_check(who, out, RK_MODE_MV);
+    if (rc) return rc;
     rc = begin_solve(h);
     if (rc) return rc;
     make_args(c, in, out, a);
     o = DaltonObs{obs, obs_weight, obs_var, obs_node, n_obs};
-    ga = GridArgs{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
     return launch_grid_forward(h, c, a, ga);
 }
 
@@ -206,7 +187,7 @@ int rk_fenrir_grid_loglik(rk_handle h, const rk_solve_cfg* c, const rk_solve_in*
     SolveArgs a;
     DaltonObs o;
     GridArgs ga;
-    rc = fenrir_grid_forward("rk_fenrir_grid_loglik", h, c, in, out, obs, obs_weight, obs_var, obs_node, n_obs, g, a, o, ga);
+    rc = fenrir_grid_forward("rk_fenrir_grid_loglik (fenrir_grid)", h, c, in, out, obs, obs_weight, obs_var, obs_node, n_obs, g, a, o, ga);
     if (rc) return rc;
     double* part = logdens;                                         // one block: the lanes write logdens themselves
     if (a.D > 1) {
@@ -228,7 +209,7 @@ int rk_fenrir_grid_solve_mv(rk_handle h, const rk_solve_cfg* c, const rk_solve_i
     SolveArgs a;
     DaltonObs o;
     GridArgs ga;
-    rc = fenrir_grid_forward("rk_fenrir_grid_solve_mv", h, c, in, out, obs, obs_weight, obs_var, obs_node, n_obs, g, a, o, ga);
+    rc = fenrir_grid_forward("rk_fenrir_grid_solve_mv (fenrir_grid)", h, c, in, out, obs, obs_weight, obs_var, obs_node, n_obs, g, a, o, ga);
     if (rc) return rc;
     rc = launch_fenrir_grid_bwd<true>(h, c, a, o, ga, n_bobs, nullptr, (double*)workspace);
     if (rc) return rc;

@@ -4,11 +4,14 @@
 // lane per trajectory, then grid_bwd_mv_kernel or grid_bwd_sim_kernel, one lane per (trajectory, block): the passes of
 // bwd_mv_kernel / bwd_sim_kernel (lane_backward.hpp: bwd_smooth_lane / bwd_sample_lane over bwd_walk) under the prediction
 // policy SlotPrior, Q_n Sigma_f[n] Q_n^T + R_n with the gain from Q_n.  Standard form, n_bmeas = 1.  No workspace.
+// Also here: the bodies of what every entry on the grid shares (grid_entry.hpp) -- the pieces of the configuration check, the
+// staging of rk_grid_in and the test of the output pointers.
 #include <cmath>
 #include "common.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "grid_kernels.hpp"
 #include "lane_backward.hpp"
 
@@ -53,79 +56,96 @@ constexpr int GRID_PMAX_THREE_BLOCKS = 5;
 template <class RHS>
 constexpr int grid_pmax() { return RHS::D >= 3 ? GRID_PMAX_THREE_BLOCKS : GRID_PMAX; }
 
-// Is this call served?  Decided on the configuration and the mode alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
-static int grid_check(const rk_solve_cfg* c, int mode) {
-    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
-               "grid: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", c->n_traj,
-               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
-    RK_REQUIRE(mode == RK_MODE_MV || mode == RK_MODE_SIM, RK_ERR_INVALID, "grid: mode must be RK_MODE_MV or RK_MODE_SIM, got %d",
-               mode);
-    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "grid: cfg->flags must carry RK_FLAG_BATCH_MINOR (the records "
-               "are the batch-minor ones)");
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "grid: RK_FLAG_STORE_PRED is not served");
+// ---- what the grid entries share (grid_entry.hpp; the sizes piece is written out there) ------------------------------
+int grid_flags_check(const char* who, const char* records, const rk_solve_cfg* c) {
+    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "%s: cfg->flags must carry RK_FLAG_BATCH_MINOR (%s)", who,
+               records);
+    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "%s: RK_FLAG_STORE_PRED is not served", who);
     RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
-               "grid: unknown kalman_type %d", c->kalman_type);
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "grid: kalman_type square-root is not built");
-    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_CHKREBTII, RK_ERR_UNSUPPORTED,
-               "grid: interrogate id %d is not supported (rodeo, schober, kramer, chkrebtii)", c->interrogate);
-    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "grid: n_bmeas = 1 only (the dense / indep_init form is not served), got %d",
-               c->n_bmeas);
-    RK_REQUIRE(c->n_bstate >= GRID_PMIN && c->n_bstate <= GRID_PMAX, RK_ERR_UNSUPPORTED, "grid: n_bstate in %d..%d, got %d",
-               GRID_PMIN, GRID_PMAX, c->n_bstate);
-    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= GRID_PMAX_THREE_BLOCKS, RK_ERR_UNSUPPORTED,
-               "grid: n_bstate up to %d with three or more blocks, got %d", GRID_PMAX_THREE_BLOCKS, c->n_bstate);
-    if (is_user_rhs(c->rhs_id)) return user_grid_check(c);
-    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "grid: unknown rhs_id %d", c->rhs_id);
-    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "grid: rhs %d needs another n_block than %d",
+               "%s: unknown kalman_type %d", who, c->kalman_type);
+    return RK_OK;
+}
+
+int grid_served_check(const GridServed& s, const rk_solve_cfg* c) {
+    const int rc = grid_flags_check(s.who, s.records, c);
+    if (rc) return rc;
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "%s: kalman_type square-root is not built", s.who);
+    RK_REQUIRE(!s.no_chkrebtii || c->interrogate != RK_INTERROGATE_CHKREBTII, RK_ERR_UNSUPPORTED,
+               "%s: interrogate_chkrebtii is not served (%s)", s.who, s.no_chkrebtii);
+    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= s.itg_last, RK_ERR_UNSUPPORTED,
+               "%s: interrogate id %d is not supported (rodeo, schober, kramer%s)", s.who, c->interrogate,
+               s.itg_last == RK_INTERROGATE_CHKREBTII ? ", chkrebtii" : "");
+    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "%s: n_bmeas = 1 only (the dense / indep_init form is not served), got %d",
+               s.who, c->n_bmeas);
+    RK_REQUIRE(c->n_bstate >= s.pmin && c->n_bstate <= s.pmax, RK_ERR_UNSUPPORTED, "%s: n_bstate in %d..%d, got %d", s.who, s.pmin,
+               s.pmax, c->n_bstate);
+    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= s.pmax3, RK_ERR_UNSUPPORTED,
+               "%s: n_bstate up to %d with three or more blocks, got %d", s.who, s.pmax3, c->n_bstate);
+    return RK_OK;
+}
+
+int grid_rhs_check(const char* who, const rk_solve_cfg* c, const char* rule) {
+    if (is_user_rhs(c->rhs_id)) {
+        const int rc = user_lane_check(c, rule ? rule : who);
+        if (rc && rule) {
+            const std::string why = rk_last_error();
+            set_error("%s: %s", who, why.c_str());
+        }
+        return rc;
+    }
+    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "%s: unknown rhs_id %d", who, c->rhs_id);
+    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "%s: rhs %d needs another n_block than %d", who,
                c->rhs_id, c->n_block);
     return RK_OK;
 }
 
-template <class RHS>
-static int launch_grid_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga) {
-    const LaunchGeom g = fwd_lane_geom(a.B);
-    bool ok = false;
-    dispatch_int<GRID_PMIN, grid_pmax<RHS>()>(c->n_bstate, [&](auto P) {
-        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(c->interrogate, [&](auto I) {
-            LaunchTimer t(h, "grid_fwd_kernel");
-            hipLaunchKernelGGL((grid_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga);
-            t.stop();
-            ok = true;
-        });
-    });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "grid: no kernel for rhs %d, n_bstate %d, interrogate %d", c->rhs_id, c->n_bstate,
-               c->interrogate);
-    RK_HIP(hipGetLastError());
+int grid_args(const char* who, const rk_grid_in* g, GridArgs& ga) {
+    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
+               "%s: grid needs t, slot, q, r and n_slots >= 1 (got %d)", who, g->n_slots);
+    ga = GridArgs{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
     return RK_OK;
 }
 
-// the forward pass for a built-in or a user right-hand side (also that of rk_fenrir_grid_*, fenrir_grid.hip: declared in
-// solve_paths.hpp)
-int launch_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga) {
-    if (is_user_rhs(c->rhs_id)) return user_grid(h, c, a, ga);
-    int rc = RK_ERR_UNSUPPORTED;
-    with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-        using RHS = decltype(rhs);
-        rc = check_n_theta<RHS>(c, a);
-        if (rc) return;
-        rc = launch_grid_fwd<RHS>(h, c, a, ga);
-    });
-    return rc;
+int grid_out_check(const char* who, const rk_solve_out* out, int mode) {
+    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID, "%s: out->mean_state / var_state must not be NULL", who);
+    RK_REQUIRE(mode != RK_MODE_SIM || out->x_state, RK_ERR_INVALID, "%s: RK_MODE_SIM needs out->x_state", who);
+    return RK_OK;
 }
 
-// (also the backward pass of rk_dalton_grid_solve, dalton_grid.hip: declared in solve_paths.hpp)
+// ---- rk_solve_grid ----------------------------------------------------------------------------------------------
+// Is this call served?  Decided on the configuration and the mode alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
+static int grid_check(const rk_solve_cfg* c, int mode) {
+    int rc = grid_sizes_check("grid", c);
+    if (rc) return rc;
+    RK_REQUIRE(mode == RK_MODE_MV || mode == RK_MODE_SIM, RK_ERR_INVALID, "grid: mode must be RK_MODE_MV or RK_MODE_SIM, got %d",
+               mode);
+    rc = grid_served_check({"grid", GRID_RECORDS, RK_INTERROGATE_CHKREBTII, nullptr, GRID_PMIN, GRID_PMAX, GRID_PMAX_THREE_BLOCKS}, c);
+    if (rc) return rc;
+    return grid_rhs_check("grid", c);
+}
+
+// the forward pass for a built-in or a user right-hand side (also that of rk_fenrir_grid_*, fenrir_grid.hip, and of
+// rk_solve_sim_draws_grid, grid_draws.hip: declared in solve_paths.hpp)
+int launch_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga) {
+    return launch_by_rhs(c, a, [&] { return user_grid(h, c, a, ga); }, [&](auto rhs) {
+        using RHS = decltype(rhs);
+        const LaunchGeom g = fwd_lane_geom(a.B);
+        return launch_fwd_instance<GRID_PMIN, grid_pmax<RHS>(), RK_INTERROGATE_RODEO, RK_INTERROGATE_CHKREBTII>(
+            h, c, "grid_fwd_kernel", "grid", [&](auto P, auto I) {
+                hipLaunchKernelGGL((grid_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga);
+            });
+    });
+}
+
+// (also the backward pass of rk_dalton_grid_solve, dalton_grid.hip, and of rk_daltonng_grid_solve, daltonng_grid.hip: declared in
+// solve_paths.hpp)
 int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga) {
     const LaunchGeom g = bwd_lane_geom(a.B, a.D);
-    const bool sim = mode == RK_MODE_SIM;
-    LaunchTimer t(h, sim ? "grid_bwd_sim_kernel" : "grid_bwd_mv_kernel");
-    const bool ok = dispatch_int<GRID_PMIN, GRID_PMAX>(c->n_bstate, [&](auto P) {
+    return launch_bwd_instance<GRID_PMIN, GRID_PMAX>(h, c, mode, "grid_bwd_mv_kernel", "grid_bwd_sim_kernel", "grid",
+                                                     [&](auto P, bool sim) {
         if (sim) hipLaunchKernelGGL((grid_bwd_sim_kernel<P>), g.grid, g.block, 0, h->stream, a, ga);
         else hipLaunchKernelGGL((grid_bwd_mv_kernel<P>), g.grid, g.block, 0, h->stream, a, ga);
     });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "grid: no backward kernel for n_bstate %d", c->n_bstate);
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
 }
 
 }  // namespace rk
@@ -140,17 +160,17 @@ int rk_solve_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, con
     int rc = grid_check(c, mode);                                   // (the configuration alone, before anything else is looked at)
     if (rc) return rc;
     RK_REQUIRE(h && out && g, RK_ERR_INVALID, "rk_solve_grid: null argument");
-    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
-               "rk_solve_grid: grid needs t, slot, q, r and n_slots >= 1 (got %d)", g->n_slots);
+    GridArgs ga;
+    rc = grid_args("rk_solve_grid", g, ga);
+    if (rc) return rc;
     rc = check_cfg(c, in);
     if (rc) return rc;
-    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID, "rk_solve_grid: out->mean_state / var_state must not be NULL");
-    RK_REQUIRE(mode != RK_MODE_SIM || out->x_state, RK_ERR_INVALID, "rk_solve_grid: RK_MODE_SIM needs out->x_state");
+    rc = grid_out_check("rk_solve_grid", out, mode);
+    if (rc) return rc;
     rc = begin_solve(h);
     if (rc) return rc;
     SolveArgs a;
     make_args(c, in, out, a);
-    const GridArgs ga{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
     rc = launch_grid_forward(h, c, a, ga);
     if (rc) return rc;
     return launch_grid_bwd(h, c, a, mode, ga);

@@ -5,11 +5,13 @@
 // grid_dynamic_bwd_mv_kernel or grid_dynamic_bwd_sim_kernel, one lane per (trajectory, block): the passes of bwd_mv_kernel /
 // bwd_sim_kernel (lane_backward.hpp: bwd_smooth_lane / bwd_sample_lane over bwd_walk) under the prediction policy
 // ScaledSlotPrior, Q_n Sigma_f[n] Q_n^T + scale[n] R_n with the gain from Q_n.  Standard form, n_bmeas = 1.  No workspace.
+// The pieces of the configuration check, the grid's staging and the launch patterns are grid_entry.hpp's.
 #include <cmath>
 #include "common.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "grid_calib_kernels.hpp"
 #include "lane_backward.hpp"
 
@@ -61,33 +63,15 @@ constexpr int grid_evidence_pmax() { return RHS::D >= 3 ? GRID_EVIDENCE_PMAX_THR
 template <class RHS>
 constexpr int grid_dynamic_pmax() { return RHS::D >= 3 ? GRID_DYNAMIC_PMAX_THREE_BLOCKS : GRID_DYNAMIC_PMAX; }
 
-// what both entries refuse, on the configuration alone; `who` names the entry in the message
+// what both entries refuse, on the configuration alone (grid_entry.hpp's pieces); `who` names the entry in the message
 static int grid_calib_check(const rk_solve_cfg* c, const char* who, int pmin, int pmax, int pmax3) {
-    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
-               "%s: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", who, c->n_traj,
-               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
-    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "%s: cfg->flags must carry RK_FLAG_BATCH_MINOR (the "
-               "records are the batch-minor ones)", who);
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "%s: RK_FLAG_STORE_PRED is not served", who);
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
-               "%s: unknown kalman_type %d", who, c->kalman_type);
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "%s: kalman_type square-root is not built", who);
-    RK_REQUIRE(c->interrogate != RK_INTERROGATE_CHKREBTII, RK_ERR_UNSUPPORTED,
-               "%s: interrogate_chkrebtii is not served (it draws its point from the predicted variance: no scale law, and a "
-               "variance that depends on the point through the scale)", who);
-    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_KRAMER, RK_ERR_UNSUPPORTED,
-               "%s: interrogate id %d is not supported (rodeo, schober, kramer)", who, c->interrogate);
-    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "%s: n_bmeas = 1 only (the dense / indep_init form is not served), got %d",
-               who, c->n_bmeas);
-    RK_REQUIRE(c->n_bstate >= pmin && c->n_bstate <= pmax, RK_ERR_UNSUPPORTED, "%s: n_bstate in %d..%d, got %d", who, pmin, pmax,
-               c->n_bstate);
-    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= pmax3, RK_ERR_UNSUPPORTED,
-               "%s: n_bstate up to %d with three or more blocks, got %d", who, pmax3, c->n_bstate);
-    if (is_user_rhs(c->rhs_id)) return user_grid_calib_check(c, who);
-    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "%s: unknown rhs_id %d", who, c->rhs_id);
-    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "%s: rhs %d needs another n_block than %d", who,
-               c->rhs_id, c->n_block);
-    return RK_OK;
+    int rc = grid_sizes_check(who, c);
+    if (rc) return rc;
+    rc = grid_served_check({who, GRID_RECORDS, RK_INTERROGATE_KRAMER,
+                            "it draws its point from the predicted variance: no scale law, and a variance that depends on the point "
+                            "through the scale", pmin, pmax, pmax3}, c);
+    if (rc) return rc;
+    return grid_rhs_check(who, c);
 }
 
 static int evidence_grid_check(const rk_solve_cfg* c) {
@@ -103,65 +87,44 @@ static int dynamic_grid_check(const rk_solve_cfg* c, int mode, double scale_min)
     return grid_calib_check(c, "dynamic_grid", GRID_DYNAMIC_PMIN, GRID_DYNAMIC_PMAX, GRID_DYNAMIC_PMAX_THREE_BLOCKS);
 }
 
-static int grid_in_check(const rk_grid_in* g, const char* who) {
-    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
-               "%s: grid needs t, slot, q, r and n_slots >= 1 (got %d)", who, g->n_slots);
-    return RK_OK;
-}
-
-// ---- launches ---------------------------------------------------------------------------------------------------
-template <class RHS>
-static int launch_grid_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga, double* logdens,
-                                double* quad, double* logdet) {
-    const LaunchGeom g = fwd_lane_geom(a.B);
-    bool ok = false;
-    dispatch_int<GRID_EVIDENCE_PMIN, grid_evidence_pmax<RHS>()>(c->n_bstate, [&](auto P) {
-        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
-            LaunchTimer t(h, "grid_evidence_kernel");
-            hipLaunchKernelGGL((grid_evidence_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga, logdens, quad, logdet);
-            t.stop();
-            ok = true;
-        });
-    });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "evidence_grid: no kernel for rhs %d, n_bstate %d, interrogate %d", c->rhs_id, c->n_bstate,
-               c->interrogate);
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
-template <class RHS>
-static int launch_grid_dynamic_fwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga, double scale_min,
-                                   double* scale, double* logdens) {
-    const LaunchGeom g = fwd_lane_geom(a.B);
-    bool ok = false;
-    dispatch_int<GRID_DYNAMIC_PMIN, grid_dynamic_pmax<RHS>()>(c->n_bstate, [&](auto P) {
-        dispatch_int<RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(c->interrogate, [&](auto I) {
-            LaunchTimer t(h, "grid_dynamic_fwd_kernel");
-            hipLaunchKernelGGL((grid_dynamic_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga, scale_min, scale,
-                               logdens);
-            t.stop();
-            ok = true;
-        });
-    });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dynamic_grid: no kernel for rhs %d, n_bstate %d, interrogate %d", c->rhs_id, c->n_bstate,
-               c->interrogate);
-    RK_HIP(hipGetLastError());
-    return RK_OK;
-}
-
+// ---- launches (grid_entry.hpp's patterns) -------------------------------------------------------------------------------
+// The backward launch stands first: a kernel is emitted where its launch is first seen, and the code object keeps the order it
+// has had -- the backward kernels, then grid_evidence_kernel's instances, then grid_dynamic_fwd_kernel's.
 static int launch_grid_dynamic_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga,
                                    const double* scale) {
     const LaunchGeom g = bwd_lane_geom(a.B, a.D);
-    const bool sim = mode == RK_MODE_SIM;
-    LaunchTimer t(h, sim ? "grid_dynamic_bwd_sim_kernel" : "grid_dynamic_bwd_mv_kernel");
-    const bool ok = dispatch_int<GRID_DYNAMIC_PMIN, GRID_DYNAMIC_PMAX>(c->n_bstate, [&](auto P) {
+    return launch_bwd_instance<GRID_DYNAMIC_PMIN, GRID_DYNAMIC_PMAX>(h, c, mode, "grid_dynamic_bwd_mv_kernel",
+                                                                     "grid_dynamic_bwd_sim_kernel", "dynamic_grid",
+                                                                     [&](auto P, bool sim) {
         if (sim) hipLaunchKernelGGL((grid_dynamic_bwd_sim_kernel<P>), g.grid, g.block, 0, h->stream, a, ga, scale);
         else hipLaunchKernelGGL((grid_dynamic_bwd_mv_kernel<P>), g.grid, g.block, 0, h->stream, a, ga, scale);
     });
-    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "dynamic_grid: no backward kernel for n_bstate %d", c->n_bstate);
-    t.stop();
-    RK_HIP(hipGetLastError());
-    return RK_OK;
+}
+
+// the forward passes, for a built-in or a user right-hand side
+static int grid_evidence_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga, double* logdens,
+                                 double* quad, double* logdet) {
+    return launch_by_rhs(c, a, [&] { return user_grid_evidence(h, c, a, ga, logdens, quad, logdet); }, [&](auto rhs) {
+        using RHS = decltype(rhs);
+        const LaunchGeom g = fwd_lane_geom(a.B);
+        return launch_fwd_instance<GRID_EVIDENCE_PMIN, grid_evidence_pmax<RHS>(), RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
+            h, c, "grid_evidence_kernel", "evidence_grid", [&](auto P, auto I) {
+                hipLaunchKernelGGL((grid_evidence_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga, logdens, quad, logdet);
+            });
+    });
+}
+
+static int grid_dynamic_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga, double scale_min,
+                                double* scale, double* logdens) {
+    return launch_by_rhs(c, a, [&] { return user_grid_dynamic(h, c, a, ga, scale_min, scale, logdens); }, [&](auto rhs) {
+        using RHS = decltype(rhs);
+        const LaunchGeom g = fwd_lane_geom(a.B);
+        return launch_fwd_instance<GRID_DYNAMIC_PMIN, grid_dynamic_pmax<RHS>(), RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
+            h, c, "grid_dynamic_fwd_kernel", "dynamic_grid", [&](auto P, auto I) {
+                hipLaunchKernelGGL((grid_dynamic_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga, scale_min, scale,
+                                   logdens);
+            });
+    });
 }
 
 }  // namespace rk
@@ -176,7 +139,8 @@ int rk_solve_evidence_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_in
     int rc = evidence_grid_check(c);                                // (the configuration alone, before anything else is looked at)
     if (rc) return rc;
     RK_REQUIRE(h && g && logdens && quad && logdet, RK_ERR_INVALID, "rk_solve_evidence_grid: null argument");
-    rc = grid_in_check(g, "rk_solve_evidence_grid");
+    GridArgs ga;
+    rc = grid_args("rk_solve_evidence_grid", g, ga);
     if (rc) return rc;
     rc = check_cfg(c, in);
     if (rc) return rc;
@@ -184,16 +148,7 @@ int rk_solve_evidence_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_in
     if (rc) return rc;
     SolveArgs a;
     make_args(c, in, nullptr, a);
-    const GridArgs ga{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
-    if (is_user_rhs(c->rhs_id)) return user_grid_evidence(h, c, a, ga, logdens, quad, logdet);
-    rc = RK_ERR_UNSUPPORTED;
-    with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-        using RHS = decltype(rhs);
-        rc = check_n_theta<RHS>(c, a);
-        if (rc) return;
-        rc = launch_grid_evidence<RHS>(h, c, a, ga, logdens, quad, logdet);
-    });
-    return rc;
+    return grid_evidence_forward(h, c, a, ga, logdens, quad, logdet);
 }
 
 int rk_solve_dynamic_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, int32_t mode,
@@ -202,29 +157,18 @@ int rk_solve_dynamic_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_in*
     int rc = dynamic_grid_check(c, mode, scale_min);                // (cfg, mode and scale_min alone, before anything else is looked at)
     if (rc) return rc;
     RK_REQUIRE(h && out && g && scale && logdens, RK_ERR_INVALID, "rk_solve_dynamic_grid: null argument");
-    rc = grid_in_check(g, "rk_solve_dynamic_grid");
+    GridArgs ga;
+    rc = grid_args("rk_solve_dynamic_grid", g, ga);
     if (rc) return rc;
     rc = check_cfg(c, in);
     if (rc) return rc;
-    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID,
-               "rk_solve_dynamic_grid: out->mean_state / var_state must not be NULL");
-    RK_REQUIRE(mode != RK_MODE_SIM || out->x_state, RK_ERR_INVALID, "rk_solve_dynamic_grid: RK_MODE_SIM needs out->x_state");
+    rc = grid_out_check("rk_solve_dynamic_grid", out, mode);
+    if (rc) return rc;
     rc = begin_solve(h);
     if (rc) return rc;
     SolveArgs a;
     make_args(c, in, out, a);
-    const GridArgs ga{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
-    if (is_user_rhs(c->rhs_id)) {
-        rc = user_grid_dynamic(h, c, a, ga, scale_min, scale, logdens);
-    } else {
-        rc = RK_ERR_UNSUPPORTED;
-        with_builtin_rhs(c->rhs_id, [&](auto rhs) {
-            using RHS = decltype(rhs);
-            rc = check_n_theta<RHS>(c, a);
-            if (rc) return;
-            rc = launch_grid_dynamic_fwd<RHS>(h, c, a, ga, scale_min, scale, logdens);
-        });
-    }
+    rc = grid_dynamic_forward(h, c, a, ga, scale_min, scale, logdens);
     if (rc) return rc;
     return launch_grid_dynamic_bwd(h, c, a, mode, ga, scale);
 }

@@ -7,14 +7,15 @@
 // THE SEED LAW: draw s is rk_solve_grid's (rk_dalton_grid_solve's) RK_MODE_SIM path under the seed cfg->seed + s (mod 2^64) --
 // Philox is keyed with (seed + s, trajectory, step, block, PURPOSE_SMOOTH), grid_bwd_sim_kernel's key.  Standard form, n_bstate
 // 2..6 (2..5 with three or more blocks), interrogate rodeo / schober / kramer.  Nothing but out->mean_state / var_state (the
-// filtered moments) and x_draws is written; there is no workspace.
-#include <string>
+// filtered moments) and x_draws is written; there is no workspace.  The pieces of the configuration check, the grid's staging
+// and the test of the output pointers are grid_entry.hpp's.
 #include "common.hpp"
 #include "kalman_small.hpp"
 #include "philox.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
+#include "grid_entry.hpp"
 #include "records.hpp"
 #include "grid_kernels.hpp"
 #include "dalton_kernels.hpp"
@@ -133,41 +134,18 @@ __global__ void __launch_bounds__(64) grid_bwd_sim_draws_kernel(SolveArgs a, Gri
 
 // Is this configuration served?  Decided on the configuration (and, for DALTON, n_bobs; < 0: the plain form) alone: RK_OK,
 // RK_ERR_INVALID (sizes, the layout flag) or RK_ERR_UNSUPPORTED.  grid_check's / dalton_grid_check's limits (grid.hip,
-// dalton_grid.hip) joined with sim_draws_check's (sim_draws.hip).
+// dalton_grid.hip) joined with sim_draws_check's (sim_draws.hip), on grid_entry.hpp's pieces.
 static int grid_draws_check(const rk_solve_cfg* c, int n_bobs) {
     const bool dalton = n_bobs >= 0;
-    RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && c->n_bstate >= 1 && c->n_bmeas >= 1, RK_ERR_INVALID,
-               "grid_draws: non-positive dimension (n_traj=%d n_steps=%d n_block=%d n_bstate=%d n_bmeas=%d)", c->n_traj,
-               c->n_steps, c->n_block, c->n_bstate, c->n_bmeas);
-    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "grid_draws: cfg->flags must carry RK_FLAG_BATCH_MINOR (the "
-               "backward kernel reads batch-minor filtered records)");
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "grid_draws: RK_FLAG_STORE_PRED is not served");
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD || c->kalman_type == RK_KALMAN_SQRT, RK_ERR_UNSUPPORTED,
-               "grid_draws: unknown kalman_type %d", c->kalman_type);
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "grid_draws: kalman_type square-root is not built");
-    RK_REQUIRE(c->interrogate != RK_INTERROGATE_CHKREBTII, RK_ERR_UNSUPPORTED,
-               "grid_draws: interrogate_chkrebtii is not served (its forward pass depends on the key, so the draws cannot share "
-               "one filter)");
-    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_KRAMER, RK_ERR_UNSUPPORTED,
-               "grid_draws: interrogate id %d is not supported (rodeo, schober, kramer)", c->interrogate);
-    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "grid_draws: n_bmeas = 1 only (the dense / indep_init form is not served), "
-               "got %d", c->n_bmeas);
-    RK_REQUIRE(c->n_bstate >= GRID_DRAWS_PMIN && c->n_bstate <= GRID_DRAWS_PMAX, RK_ERR_UNSUPPORTED,
-               "grid_draws: n_bstate in %d..%d, got %d", GRID_DRAWS_PMIN, GRID_DRAWS_PMAX, c->n_bstate);
-    RK_REQUIRE(c->n_block < 3 || c->n_bstate <= GRID_DRAWS_PMAX_THREE_BLOCKS, RK_ERR_UNSUPPORTED,
-               "grid_draws: n_bstate up to %d with three or more blocks, got %d", GRID_DRAWS_PMAX_THREE_BLOCKS, c->n_bstate);
+    int rc = grid_sizes_check("grid_draws", c);
+    if (rc) return rc;
+    rc = grid_served_check({"grid_draws", "the backward kernel reads batch-minor filtered records", RK_INTERROGATE_KRAMER,
+                            "its forward pass depends on the key, so the draws cannot share one filter", GRID_DRAWS_PMIN,
+                            GRID_DRAWS_PMAX, GRID_DRAWS_PMAX_THREE_BLOCKS}, c);
+    if (rc) return rc;
     RK_REQUIRE(!dalton || (n_bobs >= 1 && n_bobs <= 3), RK_ERR_UNSUPPORTED, "grid_draws: n_bobs in 1..3, got %d", n_bobs);
-    if (is_user_rhs(c->rhs_id)) {
-        const int rc = dalton ? user_dalton_grid_check(c) : user_grid_check(c);
-        if (rc) {
-            const std::string why = rk_last_error();
-            set_error("grid_draws: %s", why.c_str());
-        }
-        return rc;
-    }
-    RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "grid_draws: unknown rhs_id %d", c->rhs_id);
-    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "grid_draws: rhs %d needs another n_block than %d",
-               c->rhs_id, c->n_block);
+    rc = grid_rhs_check("grid_draws", c, dalton ? "dalton_grid" : "grid");  // (the forward pass is theirs: their rule, our name)
+    if (rc) return rc;
     RK_REQUIRE(!dalton || !dalton_grid_left_out(c, n_bobs, true), RK_ERR_UNSUPPORTED,
                "grid_draws: the store form of dalton_grid's filter for rhs %d at n_bstate %d with n_bobs %d is left out", c->rhs_id,
                c->n_bstate, n_bobs);
@@ -221,17 +199,17 @@ int rk_solve_sim_draws_grid(rk_handle h, const rk_solve_cfg* c, const rk_solve_i
     rc = grid_draws_counts(c, n_draws, keep, n_keep);
     if (rc) return rc;
     RK_REQUIRE(h && out && g && x_draws, RK_ERR_INVALID, "rk_solve_sim_draws_grid: null argument");
-    RK_REQUIRE(g->t && g->slot && g->q && g->r && g->n_slots >= 1, RK_ERR_INVALID,
-               "rk_solve_sim_draws_grid: grid needs t, slot, q, r and n_slots >= 1 (got %d)", g->n_slots);
+    GridArgs ga;
+    rc = grid_args("rk_solve_sim_draws_grid", g, ga);
+    if (rc) return rc;
     rc = check_cfg(c, in);
     if (rc) return rc;
-    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID,
-               "rk_solve_sim_draws_grid: out->mean_state / var_state must not be NULL");
+    rc = grid_out_check("rk_solve_sim_draws_grid", out, RK_MODE_MV);    // (the draws go to x_draws)
+    if (rc) return rc;
     rc = begin_solve(h);
     if (rc) return rc;
     SolveArgs a;
     make_args(c, in, out, a);
-    const GridArgs ga{g->t, g->slot, g->q, g->r, g->q_batched != 0, g->r_batched != 0, g->n_slots};
     rc = launch_grid_forward(h, c, a, ga);                          // grid.hip's forward pass, built-in or hiprtc
     if (rc) return rc;
     return launch_grid_draws(h, c, a, ga, n_draws, keep, n_keep, x_draws);
@@ -252,8 +230,8 @@ int rk_dalton_grid_sim_draws(rk_handle h, const rk_solve_cfg* c, const rk_solve_
     GridArgs ga;
     rc = dalton_grid_inputs("rk_dalton_grid_sim_draws", c, in, obs, obs_weight, obs_var, obs_ind, n_obs, g, o, ga);
     if (rc) return rc;
-    RK_REQUIRE(out->mean_state && out->var_state, RK_ERR_INVALID,
-               "rk_dalton_grid_sim_draws: out->mean_state / var_state must not be NULL");
+    rc = grid_out_check("rk_dalton_grid_sim_draws", out, RK_MODE_MV);
+    if (rc) return rc;
     rc = begin_solve(h);
     if (rc) return rc;
     SolveArgs a;

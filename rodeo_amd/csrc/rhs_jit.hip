@@ -372,12 +372,8 @@ int user_forward_tile(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, do
 }
 
 int user_forward_sqrt(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a) {
-    const UserRhs* u;
-    const int rc = user_rhs(c->rhs_id, &u);
+    const int rc = user_lane_check(c, "square-root solver");
     if (rc) return rc;
-    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
-               "square-root solver: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block,
-               c->n_bmeas);
     SolveArgs args = a;
     void* params[] = {&args};
     return launch_jit(h, jit_key(JIT_SQRT, c->rhs_id, c), fwd_sqrt_geom(a.B, c->n_block), params);
@@ -453,22 +449,24 @@ int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const
                       tile ? dalton_tile_geom(a.B, c->n_block, true) : dalton_lane_geom(a.B, true), params);
 }
 
-// solve_evidence around a user right-hand side (evidence_tile3_kernels.hpp / evidence_kernels.hpp).  Its own check of the
-// configuration against the registration: n_block and n_bmeas = 1 only -- the n_bstate range is evidence.hip's, per Kalman
-// form (user_rhs_check's bound of 6 is the standard lane kernels'; the square-root lanes serve 2..8, like user_forward_sqrt).
-int user_evidence_check(const rk_solve_cfg* c) {
+// The configuration against the registration for the lane families that keep their own n_bstate range (the square-root solver,
+// solve_evidence, solve_mv_dynamic and every entry on the non-uniform grid): n_block and n_bmeas = 1 only.  `who` names the entry in the message.
+// (user_rhs_check's bound of 6 is the standard lane kernels'; evidence's square-root lanes serve 2..8, like user_forward_sqrt.)
+int user_lane_check(const rk_solve_cfg* c, const char* who) {
     const UserRhs* u;
     const int rc = user_rhs(c->rhs_id, &u);
     if (rc) return rc;
     RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
-               "evidence: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
+               "%s: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", who, c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
     return RK_OK;
 }
 
+// solve_evidence around a user right-hand side (evidence_tile3_kernels.hpp / evidence_kernels.hpp): the n_bstate range is
+// evidence.hip's, per Kalman form.
 // Does evidence_tile3_kernel exist for this user right-hand side (n_bstate = 3, standard form, up to four blocks, NDEP == 1)?
 // Decided by building that kernel itself once (cached): the build that answers is the one the launch uses.
 bool user_evidence_tile_available(const rk_solve_cfg* c) {
-    if (user_evidence_check(c) || c->kalman_type != RK_KALMAN_STANDARD || c->n_bstate != 3 || c->n_block > 4) return false;
+    if (user_lane_check(c, "evidence") || c->kalman_type != RK_KALMAN_STANDARD || c->n_bstate != 3 || c->n_block > 4) return false;
     const int rc = jit_lookup(jit_key(JIT_EVIDENCE_TILE3, c->rhs_id, c), nullptr, nullptr);
     if (rc && getenv("RK_JIT_VERBOSE")) fprintf(stderr, "[rk] evidence tile kernel not available for user rhs %d: %s\n", c->rhs_id, rk_last_error());
     return rc == RK_OK;
@@ -477,7 +475,7 @@ bool user_evidence_tile_available(const rk_solve_cfg* c) {
 // the launch, like the built-in instances of evidence.hip; route: 0 tiles, 1 lanes, 2 square-root lanes
 int user_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int route, double* logdens, double* quad,
                   double* logdet) {
-    const int rc = user_evidence_check(c);
+    const int rc = user_lane_check(c, "evidence");
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args, &logdens, &quad, &logdet};
@@ -490,17 +488,8 @@ int user_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int ro
 // solve_mv_dynamic / solve_sim_dynamic around a user right-hand side (dynamic_kernels.hpp): the configuration against the
 // registration (n_block, n_bmeas = 1; the n_bstate range is dynamic.hip's) and the forward launch, like dynamic.hip's built-in
 // instances.  The backward kernels do not depend on the right-hand side: dynamic.hip launches its own.
-int user_dynamic_check(const rk_solve_cfg* c) {
-    const UserRhs* u;
-    const int rc = user_rhs(c->rhs_id, &u);
-    if (rc) return rc;
-    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
-               "dynamic: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
-    return RK_OK;
-}
-
 int user_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double scale_min, double* scale, double* logdens) {
-    const int rc = user_dynamic_check(c);
+    const int rc = user_lane_check(c, "dynamic");
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args, &scale_min, &scale, &logdens};
@@ -510,17 +499,8 @@ int user_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double 
 // solve_mv_grid / solve_sim_grid around a user right-hand side (grid_kernels.hpp): the configuration against the registration
 // (n_block, n_bmeas = 1; the n_bstate range is grid.hip's) and the forward launch, like grid.hip's built-in instances.  The
 // backward kernels do not depend on the right-hand side: grid.hip launches its own.
-int user_grid_check(const rk_solve_cfg* c) {
-    const UserRhs* u;
-    const int rc = user_rhs(c->rhs_id, &u);
-    if (rc) return rc;
-    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
-               "grid: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
-    return RK_OK;
-}
-
 int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g) {
-    const int rc = user_grid_check(c);
+    const int rc = user_lane_check(c, "grid");
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args, (void*)&g};
@@ -531,18 +511,9 @@ int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Grid
 // the configuration against the registration (n_block, n_bmeas = 1; the n_bstate ranges are grid_calib.hip's) and the forward
 // launches, like grid_calib.hip's built-in instances.  The backward kernels do not depend on the right-hand side:
 // grid_calib.hip launches its own.
-int user_grid_calib_check(const rk_solve_cfg* c, const char* who) {
-    const UserRhs* u;
-    const int rc = user_rhs(c->rhs_id, &u);
-    if (rc) return rc;
-    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
-               "%s: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", who, c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
-    return RK_OK;
-}
-
 int user_grid_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double* logdens, double* quad,
                        double* logdet) {
-    const int rc = user_grid_calib_check(c, "evidence_grid");
+    const int rc = user_lane_check(c, "evidence_grid");
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args, (void*)&g, &logdens, &quad, &logdet};
@@ -551,7 +522,7 @@ int user_grid_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, c
 
 int user_grid_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double scale_min, double* scale,
                       double* logdens) {
-    const int rc = user_grid_calib_check(c, "dynamic_grid");
+    const int rc = user_lane_check(c, "dynamic_grid");
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args, (void*)&g, &scale_min, &scale, &logdens};
@@ -562,18 +533,9 @@ int user_grid_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, co
 // n_bmeas = 1; the n_bstate range is dalton_grid.hip's) and the forward launch, like dalton_grid.hip's built-in instances: the
 // log-likelihood form (joint and marginal filter in the two halves of a wave) or the joint filter's store form.  The backward
 // kernels do not depend on the right-hand side: grid.hip launches its own.
-int user_dalton_grid_check(const rk_solve_cfg* c) {
-    const UserRhs* u;
-    const int rc = user_rhs(c->rhs_id, &u);
-    if (rc) return rc;
-    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
-               "dalton_grid: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
-    return RK_OK;
-}
-
 int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
                      bool store, double* out) {
-    const int rc = user_dalton_grid_check(c);
+    const int rc = user_lane_check(c, "dalton_grid");
     if (rc) return rc;
     SolveArgs args = a;
     void* params[] = {&args, (void*)&o, (void*)&g, &out};
@@ -585,11 +547,8 @@ int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, con
 // registration (n_block, n_bmeas = 1) and the size limit of the built-in instances that ship (n_bstate 2 .. 3, n_block n_bstate^2
 // <= 27: DESIGN.md section 7 (21)), then the launch, one (trajectory, direction) item per lane pair like dalton_grad.hip's.
 int user_dalton_grad_check(const rk_solve_cfg* c) {
-    const UserRhs* u;
-    const int rc = user_rhs(c->rhs_id, &u);
+    const int rc = user_lane_check(c, "dalton_grid_jvp");
     if (rc) return rc;
-    RK_REQUIRE(c->n_block == u->n_block && c->n_bmeas == 1 && u->n_bmeas == 1, RK_ERR_UNSUPPORTED,
-               "dalton_grid_jvp: user rhs %d needs n_block=%d, n_bmeas=1 (got %d, %d)", c->rhs_id, u->n_block, c->n_block, c->n_bmeas);
     RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 3 && c->n_block * c->n_bstate * c->n_bstate <= 27, RK_ERR_UNSUPPORTED,
                "dalton_grid_jvp: not built: user rhs %d with %d blocks at n_bstate %d (n_bstate 2..3, n_block n_bstate^2 <= 27)",
                c->rhs_id, c->n_block, c->n_bstate);

@@ -1,6 +1,7 @@
 // Host-side solver API shared by the translation units of librodeo_kalman.so (host code only, not part of the hiprtc set):
 // the functions one .hip file calls in another, the one rule that picks a configuration's device path, and the helpers
-// that turn run-time sizes / ids into template instances at the launch sites.
+// that turn run-time sizes / ids into template instances at the launch sites.  What the entries on the non-uniform grid share on
+// top of it -- the pieces of their configuration checks, the grid's staging, the launch patterns -- is in grid_entry.hpp.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -79,25 +80,23 @@ int user_dalton(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const Da
                 bool tile, double* out);
 int user_dalton_at(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const DaltonAt& s, int n_bobs,
                    bool tile, double* out);
-// solve_evidence: the configuration against the registration, whether the tile kernel builds, and the launch; route: 0 tiles,
-// 1 lanes, 2 square-root lanes (evidence.hip's EvRoute)
-int user_evidence_check(const rk_solve_cfg* c);
+// the configuration against the registration of the lane families with an n_bstate range of their own (the square-root solver,
+// solve_evidence, solve_mv_dynamic, the entries on the non-uniform grid): n_block, and n_bmeas = 1 on both sides; `who` names the entry
+int user_lane_check(const rk_solve_cfg* c, const char* who);
+// solve_evidence: whether the tile kernel builds, and the launch; route: 0 tiles, 1 lanes, 2 square-root lanes (evidence.hip's
+// EvRoute)
 bool user_evidence_tile_available(const rk_solve_cfg* c);
 int user_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int route, double* logdens, double* quad,
                   double* logdet);
-// solve_mv_dynamic / solve_sim_dynamic: the configuration against the registration and the forward launch (dynamic.hip)
-int user_dynamic_check(const rk_solve_cfg* c);
+// solve_mv_dynamic / solve_sim_dynamic: the forward launch (dynamic.hip)
 int user_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double scale_min, double* scale, double* logdens);
-// solve_mv_grid / solve_sim_grid: the configuration against the registration and the forward launch (grid.hip)
-int user_grid_check(const rk_solve_cfg* c);
+// solve_mv_grid / solve_sim_grid: the forward launch (grid.hip)
 int user_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g);
 // the backward pass on the grid (grid.hip): grid_bwd_mv_kernel / grid_bwd_sim_kernel on the batch-minor filtered moments
 int launch_grid_bwd(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, int mode, const GridArgs& ga);
 // the forward pass on the grid (grid.hip): grid_fwd_kernel for a built-in or a user right-hand side
 int launch_grid_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga);
-// solve_evidence_grid / solve_mv_dynamic_grid / solve_sim_dynamic_grid: the configuration against the registration (`who` names
-// the entry in the message) and the forward launches (grid_calib.hip)
-int user_grid_calib_check(const rk_solve_cfg* c, const char* who);
+// solve_evidence_grid / solve_mv_dynamic_grid / solve_sim_dynamic_grid: the forward launches (grid_calib.hip)
 int user_grid_evidence(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double* logdens, double* quad,
                        double* logdet);
 int user_grid_dynamic(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, double scale_min, double* scale,
@@ -109,8 +108,7 @@ int dalton_grid_inputs(const char* who, const rk_solve_cfg* c, const rk_solve_in
                        const double* obs_var, const int32_t* obs_ind, int n_obs, const rk_grid_in* g, DaltonObs& o, GridArgs& ga);
 int dalton_grid_store_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
                               int n_bobs);
-// dalton_grid: the configuration against the registration and the forward launch (dalton_grid.hip)
-int user_dalton_grid_check(const rk_solve_cfg* c);
+// dalton_grid: the forward launch (dalton_grid.hip)
 int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, int n_bobs,
                      bool store, double* out);
 // dalton_grid_jvp: the configuration against the registration and the launch (dalton_grad.hip); the right-hand side must be of
