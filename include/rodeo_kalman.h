@@ -65,6 +65,9 @@ extern "C" {
 /* flags for rk_solve_cfg.flags */
 #define RK_FLAG_STORE_PRED   1    /* also write the predicted moments (solve.py:93-96 state_pred)            */
 #define RK_FLAG_BATCH_MINOR  2    /* force the batch-minor kernels/layout even where the tile path exists    */
+#define RK_FLAG_TILE3_PACKED_MV 4 /* rk_solve_mv may leave its smoothed n_bstate = 3 tile records packed
+                                     (RK_LAYOUT_TILE3_PACKED); read by rk_solve_mv / rk_solve_layout(RK_MODE_MV)
+                                     alone, ignored by every other entry and route.  Unset: today's bytes.      */
 
 /* which call a layout query refers to */
 #define RK_MODE_FILTER  0
@@ -75,6 +78,24 @@ extern "C" {
 #define RK_LAYOUT_BATCH_MINOR  0  /* mean_state (N+1, d, p, B), var_state (N+1, d, p, p, B)                  */
 #define RK_LAYOUT_TILE3        1  /* n_bstate = 3 only: var_state holds (N+1, B, d, 3, 4) doubles, row i of a
                                      block = [Sigma[i][0..2], mu[i]]; mean_state is not used (may be NULL)  */
+#define RK_LAYOUT_TILE3_PACKED 5  /* RK_LAYOUT_TILE3 with the smoothed records of the time rows 1 .. N-1 packed in place:
+                                     same buffer, same size (rk_solve_sizes), rows 0 and N natural.  Tiles come in
+                                     tile-waves of four (tile = b * d + block; tile-wave tw = tile / 4 owns the 384-byte
+                                     stripe at byte 384 tw of every time row).  With n_tiles = B * d and
+                                     rk_tile3_packed_waves(N, n_tiles) = W, the records of steps 1 .. N-1 of the tiles
+                                     < 4 W are 9 doubles [S00 S01 S02 S11 S12 S22 | mu0 mu1 mu2] (Sigma's upper triangle
+                                     row-major, then the mean; Sigma is symmetric): the records of the steps 4k .. 4k+3
+                                     of a tile-wave are 4 x 4 x 72 = 1152 contiguous bytes (step-major, then tile) laid
+                                     over its stripe in the time rows 3k+1, 3k+2, 3k+3, i.e. slot s of (step n, tile)
+                                     is byte ((n & 3) * 288 + (tile & 3) * 72 + 8 s) of group k = n / 4, byte x of a
+                                     group being byte x % 384 of the stripe in time row 3k + 1 + x / 384.  Every other
+                                     record (W = 0: N < 16 or an array of 2 GiB and more; the tiles of a ragged last
+                                     tile-wave) is the natural RK_LAYOUT_TILE3 tile.  Bytes of the stripe rows that
+                                     hold no record of a step 1 .. N-1 are unspecified.  Reported by rk_solve_layout for
+                                     RK_MODE_MV only, with RK_FLAG_TILE3_PACKED_MV set, on the route that packs: a
+                                     built-in right-hand side in tile form at n_block = 2, kalman_type standard, not
+                                     chkrebtii, and the environment switch RK_TILE3_PACK not "0".  rk_solve_filter on
+                                     the same buffer rewrites every row in the natural layout.                       */
 #define RK_LAYOUT_TILE4        3  /* n_bstate = 4 only: var_state holds (N+1, B, d, 20) doubles per block:
                                      [Sigma row-major (16) | mu (4)]; mean_state is not used (may be NULL)   */
 #define RK_LAYOUT_TILEP        4  /* blocked tile path, n_bstate = 5 .. 8: var_state holds (N+1, B, d, p*p + p) doubles per
@@ -186,6 +207,10 @@ int rk_solve_layout(const rk_solve_cfg* cfg, int32_t mode, int32_t* layout);
  * have this size: behind the tiles sits a scratch tail (64 doubles per wave) that lanes without an output slot use.
  * RK_LAYOUT_TILE4 likewise (20 doubles per tile + 128 per wave); always size tile buffers with this function.   */
 int rk_solve_sizes(const rk_solve_cfg* cfg, int32_t layout, size_t* mean_bytes, size_t* var_bytes);
+/* RK_LAYOUT_TILE3_PACKED: the number W of leading tile-waves (four tiles each) whose records of the steps 1 .. N-1 are packed,
+ * for n_steps = N and n_tiles = B * d: n_tiles / 4 when N >= 16 and the tile array (N+1) * n_tiles * 96 bytes stays below
+ * 0x7fff0000, else 0.  The one size rule of the kernels that write and read the layout; needs no handle and no GPU.   */
+int rk_tile3_packed_waves(int32_t n_steps, int32_t n_tiles);
 
 /* bytes of device scratch (rk_solve_out.workspace) the configuration needs; 0 for the standard small-block kernels.  Dense path
  * with RK_KALMAN_SQRT and mode != RK_MODE_FILTER: per-trajectory scratch PLUS the predicted factors of every step,
@@ -206,7 +231,9 @@ int rk_solve_sim(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, co
 
 /* The solver's posterior at arbitrary times (an addition: the reference returns its posterior on the grid only).  `filt`
  * holds the records of rk_solve_filter and `smooth` those of rk_solve_mv for the SAME cfg / in / seed, both in `layout` =
- * rk_solve_layout(cfg, RK_MODE_FILTER) = rk_solve_layout(cfg, RK_MODE_MV) (two buffers: rk_solve_mv smooths in place).  Only
+ * rk_solve_layout(cfg, RK_MODE_FILTER) = rk_solve_layout(cfg, RK_MODE_MV) (two buffers: rk_solve_mv smooths in place) -- or
+ * `layout` = RK_LAYOUT_TILE3_PACKED, where that is what rk_solve_layout(cfg, RK_MODE_MV) reported for `smooth` (`filt` is then
+ * RK_LAYOUT_TILE3).  Smoothed n_bstate = 3 tile records are read with Sigma's lower triangle taken from the upper one.  Only
  * var_state (and mean_state in RK_LAYOUT_BATCH_MINOR) of the two are read.  Per query k the device array `query` (T, 3) holds
  * the node n, an on-node flag and the slot of its prior quadruple: with the flag set the smoothed record n is copied (the
  * bits of rk_solve_mv); without it the time lies in (t_n, t_{n+1}), n < N, and by the prior's Markov property
@@ -232,7 +259,8 @@ int rk_eval_at(rk_handle h, const rk_solve_cfg* cfg, int32_t layout, const rk_so
  * per trajectory: the tail of the user log-posterior of docs/examples/parameter.md:188-210,331-354 (and of
  * src/rodeo/inference/basic.py:47-62 with a Gaussian obs_loglik).
  *   state: the solver output holding the path -- layout RK_LAYOUT_BATCH_MINOR: x_state / mean_state (N+1, d, p, B);
- *          layout RK_LAYOUT_TILE3 / RK_LAYOUT_TILE4: the tile buffer (the mean is column 3 / entries 16..19);
+ *          layout RK_LAYOUT_TILE3 / RK_LAYOUT_TILE3_PACKED / RK_LAYOUT_TILE4: the tile buffer (the mean is column 3 / slots
+ *          6..8 of a packed record / entries 16..19);
  *   obs (n_obs, d) row-major on device; obs_ind (n_obs) int32 on device (clamped to [0, N]), any order; with
  *   n_obs = 0 (prior only, or zeros without upars) neither is read and both may be NULL -- here and below;
  *   upars (n_prior, B) batch-minor or NULL (no prior term); out logpost (B).                              */

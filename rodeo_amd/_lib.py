@@ -20,8 +20,9 @@ RHS_FITZHUGH_NAGUMO, RHS_LORENZ63, RHS_HIGHER_ORDER, RHS_LINEAR_DENSE = 1, 2, 3,
 RHS_USER_BASE = 1000
 FLAG_STORE_PRED = 1
 FLAG_BATCH_MINOR = 2
+FLAG_TILE3_PACKED_MV = 4
 MODE_FILTER, MODE_MV, MODE_SIM = 0, 1, 2
-LAYOUT_BATCH_MINOR, LAYOUT_TILE3, LAYOUT_TRAJ_MAJOR, LAYOUT_TILE4, LAYOUT_TILEP = 0, 1, 2, 3, 4
+LAYOUT_BATCH_MINOR, LAYOUT_TILE3, LAYOUT_TRAJ_MAJOR, LAYOUT_TILE4, LAYOUT_TILEP, LAYOUT_TILE3_PACKED = 0, 1, 2, 3, 4, 5
 COMM_UID_BYTES = 128
 
 
@@ -115,6 +116,7 @@ SIGNATURES = {
     "rk_rhs_compile_check": (C.c_int, [_I, _I, _I]),
     "rk_solve_layout": (C.c_int, [C.POINTER(SolveCfg), _I, C.POINTER(_I)]),
     "rk_solve_sizes": (C.c_int, [C.POINTER(SolveCfg), _I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rk_tile3_packed_waves": (C.c_int, [_I, _I]),
     "rk_solve_workspace_bytes": (C.c_int, [C.POINTER(SolveCfg), _I, C.POINTER(C.c_size_t)]),
     "rk_solve_filter": (C.c_int, [_H, C.POINTER(SolveCfg), C.POINTER(SolveIn), C.POINTER(SolveOut)]),
     "rk_solve_mv": (C.c_int, [_H, C.POINTER(SolveCfg), C.POINTER(SolveIn), C.POINTER(SolveOut)]),

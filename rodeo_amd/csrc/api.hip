@@ -243,7 +243,8 @@ int rk_eval_at(rk_handle h, const rk_solve_cfg* c, int32_t layout, const rk_solv
     RK_REQUIRE(c->n_bstate >= EVAL_AT_PMIN && c->n_bstate <= EVAL_AT_PMAX, RK_ERR_UNSUPPORTED,
                "eval_at: n_bstate in %d..%d (2 by padding to 3; beyond, the lane kernel spills), got %d", EVAL_AT_PMIN,
                EVAL_AT_PMAX, c->n_bstate);
-    const bool fits = layout == RK_LAYOUT_BATCH_MINOR || (layout == RK_LAYOUT_TILE3 && c->n_bstate == 3) ||
+    const bool fits = layout == RK_LAYOUT_BATCH_MINOR ||
+                      ((layout == RK_LAYOUT_TILE3 || layout == RK_LAYOUT_TILE3_PACKED) && c->n_bstate == 3) ||
                       (layout == RK_LAYOUT_TILE4 && c->n_bstate == 4) || (layout == RK_LAYOUT_TILEP && c->n_bstate >= 5);
     RK_REQUIRE(fits, RK_ERR_INVALID, "eval_at: layout %d does not hold n_bstate = %d records", layout, c->n_bstate);
     RK_REQUIRE(c->n_traj >= 1 && c->n_steps >= 1 && c->n_block >= 1 && q->n_query >= 1 && q->n_quad >= 1, RK_ERR_INVALID,

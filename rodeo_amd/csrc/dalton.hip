@@ -172,7 +172,9 @@ int rk_dalton_solve(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, c
     int rc = dalton_inputs(c, in, obs, obs_weight, obs_var, obs_ind, n_obs, n_bobs, o);
     if (rc) return rc;
     int32_t lay = 0, want = 0;
-    rc = rk_solve_layout(c, mode, &lay);
+    rk_solve_cfg natural = *c;                     // (the DALTON kernels write natural rows whatever the caller asked of rk_solve_mv)
+    natural.flags &= ~RK_FLAG_TILE3_PACKED_MV;
+    rc = rk_solve_layout(&natural, mode, &lay);
     if (rc) return rc;
     rc = rk_dalton_layout(c, mode, n_bobs, &want);
     if (rc) return rc;

@@ -7,10 +7,10 @@
 
 namespace rk {
 
-template <int P, int LAYOUT>
+template <int P, int LAYOUT, int SLAYOUT = LAYOUT>
 static void eval_at_go(rk_handle h, const EvalAtArgs& a, dim3 grid) {
     LaunchTimer t(h, "eval_at_kernel");
-    hipLaunchKernelGGL((eval_at_kernel<P, LAYOUT>), grid, dim3(64), 0, h->stream, a);
+    hipLaunchKernelGGL((eval_at_kernel<P, LAYOUT, SLAYOUT>), grid, dim3(64), 0, h->stream, a);
     t.stop();
 }
 
@@ -31,6 +31,10 @@ int eval_at_launch(rk_handle h, const rk_solve_cfg* c, int layout, const rk_solv
     switch (layout) {
         case RK_LAYOUT_TILE3:
             eval_at_go<3, RK_LAYOUT_TILE3>(h, a, grid);
+            ok = true;
+            break;
+        case RK_LAYOUT_TILE3_PACKED:           // the smoother's records; the filter's are natural
+            eval_at_go<3, RK_LAYOUT_TILE3, RK_LAYOUT_TILE3_PACKED>(h, a, grid);
             ok = true;
             break;
         case RK_LAYOUT_TILE4:

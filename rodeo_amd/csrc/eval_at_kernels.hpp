@@ -40,8 +40,11 @@ __device__ __forceinline__ void eval_at_prior(const EvalAtArgs& a, int slot, int
 
 // grid (T ceil(B D / 64)), block 64: workgroup g serves query g / ceil(B D / 64), so the query's node, flag and slot are the
 // same in every lane of a wave and the on-node branch does not diverge.  The indices are clamped to the buffers.
-template <int P, int LAYOUT>
+// LAYOUT: the filter's records; SLAYOUT: the smoother's -- the same but for RK_LAYOUT_TILE3_PACKED, which only rk_solve_mv writes.
+// Smoothed p = 3 tile records are read with Sigma mirrored from its upper triangle (records.hpp) in both layouts.
+template <int P, int LAYOUT, int SLAYOUT = LAYOUT>
 __global__ void __launch_bounds__(64) eval_at_kernel(EvalAtArgs a) {
+    constexpr bool SYM = LAYOUT == RK_LAYOUT_TILE3;
     const int nbx = (a.B * a.D + 63) >> 6;
     const int q = blockIdx.x / nbx;
     const int l = (blockIdx.x - q * nbx) * 64 + threadIdx.x;
@@ -54,7 +57,7 @@ __global__ void __launch_bounds__(64) eval_at_kernel(EvalAtArgs a) {
 
     double mu[P], S[P][P];
     if (on) {
-        load_moments<P, LAYOUT>(a.smean, a.svar, a.B, a.D, n, blk, b, mu, S);
+        load_moments<P, SLAYOUT, SYM>(a.smean, a.svar, a.B, a.D, n, blk, b, mu, S, a.N);
     } else {
         // Three stages, each with its own loads.  The scheduler would issue every load up front and hold 4 P^2 + 2 P (prior) +
         // 2 (P^2 + P) (records) doubles under the whole computation (P = 6 spilled): the barriers keep Q1, R1 and the filtered
@@ -75,7 +78,7 @@ __global__ void __launch_bounds__(64) eval_at_kernel(EvalAtArgs a) {
             smooth_gain<P>(Q2, St, Sp, Tm, G);
         }
         __builtin_amdgcn_sched_barrier(0);
-        load_moments<P, LAYOUT>(a.smean, a.svar, a.B, a.D, n + 1, blk, b, mu, S);
+        load_moments<P, SLAYOUT, SYM>(a.smean, a.svar, a.B, a.D, n + 1, blk, b, mu, S, a.N);
         smooth_mv_block<P>(G, mt, St, mp, Sp, mu, S);
     }
     double* mo = a.mean_out + ((((size_t)b * a.T + q) * a.D + blk) * P);

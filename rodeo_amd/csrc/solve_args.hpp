@@ -16,6 +16,9 @@ struct SolveArgs {
     // p = 3 tile path, solve_mv: the filtered rows 1 .. N-1 are packed in place (tile3_pack.hpp).  Set by tile3_solve
     // alone; zero for every other caller and in the hiprtc builds.
     int pack = 0;
+    // ... and, with RK_FLAG_TILE3_PACKED_MV, the smoothed rows leave packed as well, over the filtered records (pack_out
+    // implies pack; bwd_mv_tile3_kernel)
+    int pack_out = 0;
     double *mean, *var, *mean_pred, *var_pred, *x;
 };
 

@@ -158,6 +158,7 @@ int launch_block_sum(rk_handle h, const double* part, int B, int D, double* logd
 
 // ---- MFMA-tile paths: n_bstate = 3 (solve_tile3.hip), 4 (solve_tile4.hip), blocked 4 .. 8 (solve_tilen.hip) ----------
 bool tile3_supported(const rk_solve_cfg* c, int mode);
+bool tile3_pack_route(const rk_solve_cfg* c, int mode);     // the tile3 route that packs its rows (solve_tile3.hip, tile3_pack.hpp)
 int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp = nullptr);
 int tile3_backward(rk_handle h, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp = nullptr);
 bool tile3_sim_logpost_supported(const rk_solve_cfg* c, int n_obs);
@@ -196,11 +197,13 @@ inline SolvePath solve_path(const rk_solve_cfg* c, int mode) {
     return c->kalman_type == RK_KALMAN_SQRT ? SolvePath::Sqrt : SolvePath::Small;
 }
 
-// RK_LAYOUT_* of a path's outputs.  The blocked tiles at n_bstate = 4 write the RK_LAYOUT_TILE4 records.
-inline int path_layout(SolvePath p, const rk_solve_cfg* c) {
+// RK_LAYOUT_* of a path's outputs.  The blocked tiles at n_bstate = 4 write the RK_LAYOUT_TILE4 records; the p = 3 tiles pack
+// the smoothed rows only where the caller asked for it (RK_FLAG_TILE3_PACKED_MV) and the route packs at all.
+inline int path_layout(SolvePath p, const rk_solve_cfg* c, int mode) {
     switch (p) {
         case SolvePath::Dense: return RK_LAYOUT_TRAJ_MAJOR;
-        case SolvePath::Tile3: return RK_LAYOUT_TILE3;
+        case SolvePath::Tile3:
+            return (c->flags & RK_FLAG_TILE3_PACKED_MV) && tile3_pack_route(c, mode) ? RK_LAYOUT_TILE3_PACKED : RK_LAYOUT_TILE3;
         case SolvePath::Tile4: return RK_LAYOUT_TILE4;
         case SolvePath::TileN: return c->n_bstate == 4 ? RK_LAYOUT_TILE4 : RK_LAYOUT_TILEP;
         default: return RK_LAYOUT_BATCH_MINOR;

@@ -18,6 +18,7 @@
 #include "solve_args.hpp"
 #include "solve_paths.hpp"
 #include "solve_small_kernels.hpp"
+#include "tile3_pack.hpp"
 #include "lane_backward.hpp"
 
 namespace rk {
@@ -39,7 +40,8 @@ __global__ void __launch_bounds__(64) bwd_sim_kernel(SolveArgs a) {
 // One wave per trajectory: the n_obs x n_block observation terms are spread over the 64 lanes (a fixed stride-64 assignment
 // and a fixed xor tree, so the value does not depend on the launch), where one lane per trajectory walked its 82 strided
 // loads one after the other on 16 waves in all (C4: 36 us of a 306 us evaluation; now 6).
-__global__ void __launch_bounds__(64) gauss_logpost_kernel(int B, int n_steps, int D, int P, int tile, int tile_off, const double* x,
+// (`packed`: RK_LAYOUT_TILE3_PACKED -- the mean of a packed record is its slot 6, tile3_pack.hpp)
+__global__ void __launch_bounds__(64) gauss_logpost_kernel(int B, int n_steps, int D, int P, int tile, int tile_off, bool packed, const double* x,
                                                            const double* obs, const int32_t* obs_ind, int n_obs, double noise_sd,
                                                            const double* upars, int n_prior, double prior_sd, double* out) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -51,8 +53,11 @@ __global__ void __launch_bounds__(64) gauss_logpost_kernel(int B, int n_steps, i
         int ni = obs_ind[k];
         ni = ni < 0 ? 0 : (ni > n_steps ? n_steps : ni);     // never index outside the (N+1)-long path
         const size_t n = (size_t)ni;
-        const double xv = tile ? x[((n * B + b) * D + blk) * tile + tile_off]      // mu_0 inside the tile
-                               : x[((n * D + blk) * P + 0) * (size_t)B + b];
+        const long long n_tiles = (long long)B * D, tau = (long long)b * D + blk;
+        const double xv = packed && tile3_pack_record(n_steps, n_tiles, ni, tau)
+                              ? x[tile3_pack_index(n_tiles, ni, tau, tile3_pack_slot(0, 3))]
+                              : tile ? x[((n * B + b) * D + blk) * tile + tile_off]      // mu_0 inside the tile
+                                     : x[((n * D + blk) * P + 0) * (size_t)B + b];
         const double zz = (obs[e] - xv) / noise_sd;
         acc += -0.5 * zz * zz - lsd - LOG_SQRT_2PI;           // scipy.stats.norm.logpdf
     }
@@ -180,9 +185,11 @@ extern "C" {
 int rk_solve_layout(const rk_solve_cfg* c, int32_t mode, int32_t* layout) {
     RK_REQUIRE(c && layout, RK_ERR_INVALID, "rk_solve_layout: null argument");
     RK_REQUIRE(mode >= RK_MODE_FILTER && mode <= RK_MODE_SIM, RK_ERR_INVALID, "rk_solve_layout: bad mode %d", mode);
-    *layout = path_layout(solve_path(c, mode), c);
+    *layout = path_layout(solve_path(c, mode), c, mode);
     return RK_OK;
 }
+
+int rk_tile3_packed_waves(int32_t n_steps, int32_t n_tiles) { return tile3_pack_waves(n_steps, n_tiles); }
 
 int rk_solve_workspace_bytes(const rk_solve_cfg* c, int32_t mode, size_t* bytes) {
     RK_REQUIRE(c && bytes, RK_ERR_INVALID, "rk_solve_workspace_bytes: null argument");
@@ -198,7 +205,7 @@ int rk_solve_workspace_bytes(const rk_solve_cfg* c, int32_t mode, size_t* bytes)
 int rk_solve_sizes(const rk_solve_cfg* c, int32_t layout, size_t* mean_bytes, size_t* var_bytes) {
     RK_REQUIRE(c, RK_ERR_INVALID, "rk_solve_sizes: null cfg");
     const size_t m = (size_t)(c->n_steps + 1) * c->n_block * c->n_bstate * (size_t)c->n_traj * sizeof(double);
-    if (layout == RK_LAYOUT_TILE3) {
+    if (layout == RK_LAYOUT_TILE3 || layout == RK_LAYOUT_TILE3_PACKED) {            // one size: the packed records lie in place
         RK_REQUIRE(c->n_bstate == 3, RK_ERR_INVALID, "RK_LAYOUT_TILE3 needs n_bstate = 3");
         if (mean_bytes) *mean_bytes = 0;
         if (var_bytes) {
@@ -334,7 +341,8 @@ int rk_gauss_obs_logpost(rk_handle h, int32_t n_traj, int32_t n_steps, int32_t n
                          int32_t n_obs, double noise_sd, const double* upars, int32_t n_prior, double prior_sd,
                          double* logpost) {
     RK_REQUIRE(h && x_state && logpost && (n_obs <= 0 || (obs && obs_ind)), RK_ERR_INVALID, "rk_gauss_obs_logpost: null argument");
-    RK_REQUIRE(layout == RK_LAYOUT_BATCH_MINOR || (layout == RK_LAYOUT_TILE3 && n_bstate == 3) ||
+    const bool tile3 = layout == RK_LAYOUT_TILE3 || layout == RK_LAYOUT_TILE3_PACKED;
+    RK_REQUIRE(layout == RK_LAYOUT_BATCH_MINOR || (tile3 && n_bstate == 3) ||
                    (layout == RK_LAYOUT_TILE4 && n_bstate == 4) || (layout == RK_LAYOUT_TILEP && n_bstate >= 4), RK_ERR_INVALID,
                "rk_gauss_obs_logpost: bad layout %d for n_bstate %d", layout, n_bstate);
     RK_REQUIRE(n_traj >= 1 && n_obs >= 0 && n_block >= 1 && n_bstate >= 1 && n_steps >= 1, RK_ERR_INVALID,
@@ -342,8 +350,8 @@ int rk_gauss_obs_logpost(rk_handle h, int32_t n_traj, int32_t n_steps, int32_t n
     RK_HIP(hipSetDevice(h->device));
     LaunchTimer t(h, "gauss_logpost_kernel");
     hipLaunchKernelGGL(gauss_logpost_kernel, dim3(n_traj), dim3(64), 0, h->stream, n_traj, n_steps, n_block,
-                       n_bstate, layout == RK_LAYOUT_TILE3 ? 12 : (layout == RK_LAYOUT_BATCH_MINOR ? 0 : n_bstate * (n_bstate + 1)),
-                       layout == RK_LAYOUT_TILE3 ? 3 : n_bstate * n_bstate, x_state, obs, obs_ind, n_obs, noise_sd, upars, n_prior, prior_sd, logpost);
+                       n_bstate, tile3 ? 12 : (layout == RK_LAYOUT_BATCH_MINOR ? 0 : n_bstate * (n_bstate + 1)),
+                       tile3 ? 3 : n_bstate * n_bstate, layout == RK_LAYOUT_TILE3_PACKED, x_state, obs, obs_ind, n_obs, noise_sd, upars, n_prior, prior_sd, logpost);
     t.stop();
     RK_HIP(hipGetLastError());
     return RK_OK;

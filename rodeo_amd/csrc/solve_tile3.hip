@@ -237,11 +237,34 @@ __global__ void __launch_bounds__(256) bwd_mv_tile3_kernel(SolveArgs a, double* 
         // carry = filt[N] (solve.py:279-282); lanes without a slot hold row 3 = e_3 of the augmented tile (or zeros)
         double Ms = st ? base[(size_t)a.N * ostride] : ((r == 3 && c == 3) ? 1.0 : 0.0);
         // full chunks store with a scalar row pointer + this lane's byte offset in the tile-wave's 384 bytes
-        const char* const wave_rows = (const char*)(tiles + (size_t)tw * 4 * TILE_DOUBLES);
+        char* const wave_rows = (char*)(tiles + (size_t)tw * 4 * TILE_DOUBLES);
         const size_t row_bytes = tstride * sizeof(double);
         const unsigned bvoff = st ? (unsigned)((g * TILE_DOUBLES + idx) * sizeof(double)) : 0x80000000u;   // or: out of range
         const bool buffer_ok = (CHUNK - 1) * row_bytes + 384 < 0x7fffffffull;      // one chunk's rows within a 2 GiB buffer window
         const int chunk_span = (int)((CHUNK - 1) * row_bytes + 384);
+        // Packed smoothed rows (a.pack_out, tile3_pack.hpp; full tile-waves only, like the packed filtered rows): the smoothed
+        // state of step n leaves as a 72-byte record over the bytes of step n's FILTERED record -- group n >> 2 = the stripe
+        // rows 3 (n >> 2) + 1 .. + 3, byte (n & 3) 288 + 72 g + 8 slot of the group.  The store stays the one buffer store of
+        // the step: its scalar offset carries the group's first stripe row, its per-lane offset the byte inside the group's
+        // three rows.  n & 3 of step s of a chunk is ((N - 1) - s) & 3 in EVERY chunk (CHUNK = 16), so four per-lane offsets
+        // (s & 3) and sixteen scalar ones are fixed here, in front of the time loop; lanes of the lower triangle, of row 3 and
+        // of absent tiles are out of range.  The natural rows use the same store with voff = bvoff and one row per step.
+        const bool pack_out = a.pack_out && tile3_pack_full_wave(tw, n_tiles);
+        const int slot = st ? tile3_pack_slot(r, c) : -1;
+        const int ph0 = (a.N - 1) & 3;
+        unsigned pv[4];                                             // byte behind the group's first row, by n & 3
+#pragma unroll
+        for (int ph = 0; ph < 4; ++ph) {
+            const int gb = tile3_pack_group_byte(ph, g, slot < 0 ? 0 : slot);
+            pv[ph] = (unsigned)((gb / T3P_STRIPE) * row_bytes) + (unsigned)(gb % T3P_STRIPE);
+        }
+        int voff[4], soff[CHUNK];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) voff[j] = (int)(pack_out ? (slot < 0 ? 0x80000000u : pv[(ph0 - j) & 3]) : bvoff);
+#pragma unroll
+        for (int s = 0; s < CHUNK; ++s)                             // (>> of a negative int rounds down)
+            soff[s] = __builtin_amdgcn_readfirstlane(
+                (int)((pack_out ? 3 * (((ph0 - s) >> 2) - ((ph0 - (CHUNK - 1)) >> 2)) : CHUNK - 1 - s) * row_bytes));
         lds_barrier();                                               // tick -3
         lds_barrier();                                               // tick -2
         lds_barrier();                                               // tick -1: chunk 0 is in LDS
@@ -269,8 +292,10 @@ __global__ void __launch_bounds__(256) bwd_mv_tile3_kernel(SolveArgs a, double* 
                     };
 #pragma unroll
                     for (int s = 0; s < LOOKAHEAD; ++s) load(s);
+                    // the window starts at the chunk's lowest row: natural row n_hi - 15, or the first stripe row of its lowest group
+                    const int row_lo = pack_out ? tile3_pack_chunk_first_row(n_hi - (CHUNK - 1)) : n_hi - (CHUNK - 1);
                     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                        (void*)(wave_rows + (size_t)(n_hi - (CHUNK - 1)) * row_bytes), 0, chunk_span, 0x00020000);
+                        (void*)(wave_rows + (size_t)row_lo * row_bytes), 0, chunk_span, 0x00020000);
                     double Dm = Ms - Mp[0];
 #pragma unroll
                     for (int s = 0; s < CHUNK; ++s) {
@@ -281,27 +306,39 @@ __global__ void __launch_bounds__(256) bwd_mv_tile3_kernel(SolveArgs a, double* 
                         if (s + 1 < CHUNK) Dm = Ms - Mp[s + 1];
                         u32x2 bits;
                         __builtin_memcpy(&bits, &Ms, 8);
-                        __builtin_amdgcn_raw_buffer_store_b64(bits, rsrc, (int)bvoff, (int)((CHUNK - 1 - s) * row_bytes), 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(bits, rsrc, voff[s & 3], soff[s], 0);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 } else {
+                    // a partial last chunk, or rows too far apart for one window: the same records through pointers
                     for (int s = 0; s < cnt; ++s) {
                         const char* q = in + lds_byte(s, g, 0, idx);
                         const double Mp = *(const double*)(q), Gt = *(const double*)(q + 128), Mf = *(const double*)(q + 256);
                         const double V1 = MF(Ms - Mp, Gt, 0.0);
                         Ms = MF(V1, Gt, Mf);
-                        o[0] = Ms;
-                        o -= ostride;
+                        if (pack_out) {
+                            const int n = n_hi - s;
+                            double* const rec = (double*)(wave_rows + (size_t)(3 * (n >> 2) + 1) * row_bytes + pv[n & 3]);
+                            *(slot < 0 ? dump + lane : rec) = Ms;
+                        } else {
+                            o[0] = Ms;
+                            o -= ostride;
+                        }
                     }
                 }
             }
-            // Packed rows (a.pack, tile3_pack.hpp): the natural rows this tick wrote, n_hi .. n_hi - cnt + 1, lie over packed
-            // records of this workgroup's own stripe, and stripe row m holds records of steps >= m - 1 only (invariant 2):
-            // steps of this chunk and, in its lowest row, of the next one.  A producer has a chunk's records in its
-            // landing zone at lds_dma_wait_all() of stage 1, THREE barriers before the chunk is smoothed: the loads of
-            // chunk t + 1 were complete before the barrier that ended tick t - 2, the stores above were issued behind the
-            // one that ended tick t - 1.  No other workgroup reads or writes this stripe.  So only consumed records are
-            // overwritten, and this barrier need not wait for the stores (lds_barrier()).
+            // Stores over packed filtered rows (a.pack, tile3_pack.hpp); no other workgroup reads or writes this stripe.  A
+            // producer has a chunk's records in its landing zone at lds_dma_wait_all() of stage 1, THREE barriers before the
+            // chunk is smoothed: the loads of chunk t + 1 were complete before the barrier that ended tick t - 2, the stores
+            // above were issued behind the one that ended tick t - 1.
+            //   Packed output: the smoothed record of step n overwrites the filtered record of step n and nothing else (same
+            //   group, same bytes).  That record belongs to this chunk, so it reached its producer's zone at least two
+            //   barriers ago.  The fetches of later chunks that cover the same stripe row (a group shared by two chunks) were
+            //   complete by then as well, and those chunks never use the bytes of this chunk's steps.
+            //   Natural output (a.pack without a.pack_out): the rows n_hi .. n_hi - cnt + 1 lie over packed records, and stripe
+            //   row m holds records of steps >= m - 1 only (invariant 2): steps of this chunk and, in its lowest row, of the
+            //   next one, which is in its zone already.
+            // So only consumed records are overwritten, and this barrier need not wait for the stores (lds_barrier()).
             lds_barrier();
         }
     }
@@ -873,16 +910,18 @@ int tile3_solve_sim_logpost(rk_handle h, const rk_solve_cfg* c, const SolveArgs&
 }
 
 // solve_mv packs the filtered rows in place (tile3_pack.hpp) where the forward instance is the headline loop, the one
-// that honours SolveArgs::pack: a built-in right-hand side in tile form at n_block = 2, not chkrebtii; N >= 16; and the
-// whole tile array inside one store window of the forward kernel.  RK_TILE3_PACK = 0 (read per call) keeps the natural
-// rows: same bits, for parity tests and measurements.
-template <class RHS>
-static bool tile3_packs(const rk_solve_cfg* c, const SolveArgs& a, int mode) {
-    if (!(rhs_has_tile_form<RHS>::value && RHS::D == 2) || mode != RK_MODE_MV || c->interrogate == RK_INTERROGATE_CHKREBTII) return false;
+// that honours SolveArgs::pack: a built-in right-hand side in tile form at n_block = 2, not chkrebtii.  RK_TILE3_PACK = 0
+// (read per call) keeps the natural rows: same bits, for parity tests and measurements.  This is the route on which
+// RK_FLAG_TILE3_PACKED_MV makes rk_solve_layout report RK_LAYOUT_TILE3_PACKED; the sizes (tile3_pack_sizes) and the
+// tile-wave (tile3_pack_full_wave) then decide record by record, for the writer and for every reader.
+bool tile3_pack_route(const rk_solve_cfg* c, int mode) {
+    if (mode != RK_MODE_MV || c->interrogate == RK_INTERROGATE_CHKREBTII || is_user_rhs(c->rhs_id) || !tile3_supported(c, mode))
+        return false;
     const char* const force = getenv("RK_TILE3_PACK");
     if (force && force[0] == '0') return false;
-    const size_t array_bytes = (size_t)(a.N + 1) * a.B * RHS::D * TILE_DOUBLES * sizeof(double);
-    return a.N >= T3P_MIN_STEPS && array_bytes < 0x7fff0000ull;
+    bool headline = false;
+    with_builtin_rhs(c->rhs_id, [&](auto rhs) { headline = rhs_has_tile_form<decltype(rhs)>::value && decltype(rhs)::D == 2; });
+    return headline;
 }
 
 int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* tiles, int mode, const SimLogpost* lp) {
@@ -890,7 +929,8 @@ int tile3_solve(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double* 
     SolveArgs ap = a;
     if (is_user_rhs(c->rhs_id)) rc = user_forward_tile(h, c, a, tiles, JIT_TILE3);
     else with_builtin_rhs(c->rhs_id, [&](auto rhs) {                                                  // (tile3_supported: a built-in id)
-        ap.pack = tile3_packs<decltype(rhs)>(c, a, mode);
+        ap.pack = tile3_pack_route(c, mode) && tile3_pack_sizes(a.N, (long long)a.B * a.D);
+        ap.pack_out = ap.pack && (c->flags & RK_FLAG_TILE3_PACKED_MV) != 0;
         rc = launch_fwd_tile<decltype(rhs)>(h, c, ap, tiles);
     });
     if (rc || mode == RK_MODE_FILTER) return rc;

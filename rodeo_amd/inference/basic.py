@@ -12,8 +12,7 @@ log-likelihood -- a float, or an array of shape (B,) for batched inputs -- and t
 the device buffers are reused by the next call with the same configuration, after which an unread ``Xt`` is stale.
 """
 import numpy as np
-from .. import _lib
-from ..solve import TILE_LAYOUTS, cached_plan
+from ..solve import cached_plan
 from .logpost import gauss_obs_logpost, obs_index
 
 
@@ -67,15 +66,7 @@ def basic(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate
         ll = gauss_obs_logpost(plan, obs_data, ind, obs_loglik.noise_sd, reuse_out=True).to_host()
         return (ll if plan.batched else float(ll[0])), Xt
     # generic callable: fetch only the observed time slices
-    rows = []
-    for n in ind:
-        if plan.layout in TILE_LAYOUTS:
-            rows.append(plan.records_mean_var(plan.var_state.slice0_host(int(n)))[0])   # (B, d, p) means
-        elif plan.layout == _lib.LAYOUT_TRAJ_MAJOR:
-            rows.append(plan.mean_state.to_host()[:, int(n)])
-        else:
-            rows.append(np.moveaxis(plan.mean_state.slice0_host(int(n)), -1, 0))   # (d, p, B) -> (B, d, p)
-    ode_data = np.stack(rows, axis=1)                              # (B, n_obs, d, p)
+    ode_data = plan.mean_rows_host(ind)                            # (B, n_obs, d, p)
     out = np.array([obs_loglik(obs_data, ode_data[b], **{k: (np.asarray(v)[b] if np.ndim(v) >= 2 else v)
                                                           for k, v in params.items()}) for b in range(plan.B)])
     return (out if plan.batched else out[0]), Xt

@@ -62,10 +62,9 @@ def _plan(args, params, mode, n_bobs):
     p, d = int(np.shape(args[1])[-1]), int(np.shape(args[1])[-3])
     tiles = p == 3 and n_bobs == 1 and d <= 4 and os.environ.get("RK_DALTON_LANES", "0") in ("", "0")
     plan = cached_plan(*args, batch_minor=not tiles, **params)
-    want, lay = C.c_int32(0), C.c_int32(0)
+    want = C.c_int32(0)
     _lib.check(plan.dev.lib.rk_dalton_layout(C.byref(plan.cfg), mode, n_bobs, C.byref(want)))
-    _lib.check(plan.dev.lib.rk_solve_layout(C.byref(plan.cfg), mode, C.byref(lay)))
-    if lay.value != want.value:                                     # (e.g. a user right-hand side without a tile form)
+    if plan.solve_layout(mode) != want.value:                                     # (e.g. a user right-hand side without a tile form)
         plan = cached_plan(*args, batch_minor=True, **params)
     return plan
 

@@ -59,8 +59,8 @@ def gauss_obs_logpost(plan, obs_data, obs_ind, noise_sd, upars=None, prior_sd=10
         plan._require_path()
         state, layout = plan.x_state, _lib.LAYOUT_BATCH_MINOR
     else:
-        layout = plan.layout
-        state = plan.var_state if layout in TILE_LAYOUTS else plan.mean_state
+        layout = plan.records_layout                 # (RK_LAYOUT_TILE3_PACKED after a packing mv(): the kernel reads both forms)
+        state = plan.var_state if plan.layout in TILE_LAYOUTS else plan.mean_state
     # per call one upload (upars) and one kernel
     d_obs, d_ind, d_up, k = _staged(plan, obs, ind, upars, n_prior)
     # The result is a fresh device array unless the caller opts into `reuse_out`: then it comes from the plan's ring of four

@@ -148,7 +148,9 @@ class SolvePlan:
             prior_var=self._R.ptr, prior_var_batched=int(R.ndim == 4),
             theta=self._theta.ptr if self._theta is not None else None, theta_batched=int(Bt is not None))
         self._store_pred = store_pred
-        self.layout = None                 # layout of the last launch (RK_LAYOUT_*)
+        self.layout = None                 # layout of the last launch (RK_LAYOUT_*), RK_LAYOUT_TILE3 for its packed form too
+        self.records_layout = None         # ... as the library reported it: RK_LAYOUT_TILE3_PACKED after a packing mv()
+        self.smoothed_tile3 = False        # the records are mv()'s smoothed p = 3 tiles: Sigma is read from its upper triangle
         self.last_mode = None              # RK_MODE_* of the last launch
         self._bufs = {}                    # layout -> (mean_state, var_state)
         self._ws = None                    # device scratch for the dense path
@@ -179,12 +181,22 @@ class SolvePlan:
                 raise TypeError("this ODE has no parameters")
             self._theta.upload(_bm(theta, Bt is not None))
 
-    def _prepare_out(self, mode, path=True):
-        """Ask the library which layout this call uses and (once) allocate the outputs for it.  ``path=False``: a sampler launch
-        that stores no path -- x_state is neither allocated nor handed to the library, and the plan holds no path afterwards."""
+    def solve_layout(self, mode, packed_mv=False):
+        """rk_solve_layout of this plan for ``mode``.  ``packed_mv`` (mv() at n_bstate = 3) sets RK_FLAG_TILE3_PACKED_MV in the
+        plan's cfg, any other query clears it: the flag stands in ``cfg`` exactly while the plan's records may be packed."""
+        self.cfg.flags = (self.cfg.flags & ~_lib.FLAG_TILE3_PACKED_MV) | (_lib.FLAG_TILE3_PACKED_MV if packed_mv else 0)
         lay = C.c_int32(0)
         _lib.check(self.dev.lib.rk_solve_layout(C.byref(self.cfg), mode, C.byref(lay)))
-        lay = lay.value
+        return lay.value
+
+    def _prepare_out(self, mode, path=True, packed_mv=False):
+        """Ask the library which layout this call uses and (once) allocate the outputs for it.  ``path=False``: a sampler launch
+        that stores no path -- x_state is neither allocated nor handed to the library, and the plan holds no path afterwards.
+        RK_LAYOUT_TILE3_PACKED is RK_LAYOUT_TILE3 with records packed in place: ONE buffer serves both, so filter() and mv() on
+        one plan keep working in place."""
+        self.records_layout = lay = self.solve_layout(mode, packed_mv)
+        if lay == _lib.LAYOUT_TILE3_PACKED:
+            lay = _lib.LAYOUT_TILE3
         dev, N1, d, p, B = self.dev, self.N + 1, self.d, self.p, self.B
         if lay not in self._bufs:
             if lay == _lib.LAYOUT_TILE3:
@@ -235,11 +247,13 @@ class SolvePlan:
             x_state=self.x_state.ptr if path and self.x_state is not None else None)
 
     # ---- launches (asynchronous) ----
-    def launch(self, fn, key, mode, *extra, path=True):
+    def launch(self, fn, key, mode, *extra, path=True, packed_mv=False):
         """The one way a library entry writes this plan's outputs: ``fn(handle, cfg, in, out, *extra)`` after the bookkeeping
-        every such launch owes -- generation, outputs of ``mode``'s layout, last_mode, seed.  ``path=False``: see _prepare_out."""
+        every such launch owes -- generation, outputs of ``mode``'s layout, last_mode, seed.  ``path=False``: see _prepare_out;
+        ``packed_mv``: see solve_layout (mv() alone)."""
         self.generation += 1               # whatever is in the output buffers now belongs to an earlier call
-        self._prepare_out(mode, path)
+        self._prepare_out(mode, path, packed_mv)
+        self.smoothed_tile3 = packed_mv and self.layout == _lib.LAYOUT_TILE3
         self.last_mode = mode
         self.set_seed(key)
         _lib.check(fn(self.dev.h, C.byref(self.cfg), C.byref(self.inp), C.byref(self._out), *extra))
@@ -252,7 +266,7 @@ class SolvePlan:
         self.launch(self.dev.lib.rk_solve_filter, key, _lib.MODE_FILTER)
 
     def mv(self, key=None):
-        self.launch(self.dev.lib.rk_solve_mv, key, _lib.MODE_MV)
+        self.launch(self.dev.lib.rk_solve_mv, key, _lib.MODE_MV, packed_mv=self.p == 3)
 
     def sim(self, key=None):
         self.launch(self.dev.lib.rk_solve_sim, key, _lib.MODE_SIM)
@@ -300,10 +314,80 @@ class SolvePlan:
         p = self.p
         return t[..., p * p:], t[..., :p * p].reshape(t.shape[:-1] + (p, p))
 
+    # ---- smoothed p = 3 tiles on the host: packed records (RK_LAYOUT_TILE3_PACKED, include/rodeo_kalman.h) and the mirror rule ----
+    def packed_waves(self):
+        """Leading tile-waves (four tiles each, tile = b d + block) whose steps 1 .. N-1 are packed records in var_state; 0 when
+        nothing is packed.  The size rule is the library's (rk_tile3_packed_waves)."""
+        if self.records_layout != _lib.LAYOUT_TILE3_PACKED:
+            return 0
+        return int(self.dev.lib.rk_tile3_packed_waves(self.N, self.B * self.d))
+
+    @staticmethod
+    def _tile3_fill(t, rec):
+        """Natural tiles t (..., 3, 4) from packed records rec (..., 9) = [S00 S01 S02 S11 S12 S22 | mu]: the symmetric Sigma
+        (both triangles) and the mean."""
+        for slot, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2), (0, 3), (1, 3), (2, 3))):
+            t[..., i, j] = rec[..., slot]
+            if i < j < 3:
+                t[..., j, i] = rec[..., slot]
+
+    def _tile3_mirror(self, t):
+        """Sigma's lower triangle from the upper one, in place, for mv()'s smoothed tiles in BOTH layouts: a packed record holds
+        no lower triangle, and the natural one differs from the upper in the last bit."""
+        if self.smoothed_tile3:
+            for i, j in ((0, 1), (0, 2), (1, 2)):
+                t[..., j, i] = t[..., i, j]
+        return t
+
+    def tile3_unpack(self, raw, waves):
+        """``raw`` (N+1, B, d, 3, 4) as downloaded, with the steps 1 .. N-1 of the first ``waves`` tile-waves packed: the natural
+        tiles, in place.  The groups of four steps are three whole stripe rows each, so the gather is two reshapes."""
+        N, T = self.N, self.B * self.d
+        if waves:
+            K = ((N - 1) >> 2) + 1                                             # groups 0 .. K-1 hold the steps 1 .. N-1
+            grp = raw.reshape(N + 1, T * 12)[1:1 + 3 * K, :waves * 48].reshape(K, 3, waves, 48)
+            grp = grp.transpose(0, 2, 1, 3).reshape(K, waves, 4, 4, 9)          # (group, tile-wave, step, tile, slot)
+            rec = grp.transpose(0, 2, 1, 3, 4).reshape(4 * K, 4 * waves, 9)[1:N].copy()     # (a view of raw at one tile-wave)
+            self._tile3_fill(raw.reshape(N + 1, T, 3, 4)[1:N, :4 * waves], rec)
+        return raw
+
+    def tile3_row_host(self, n):
+        """The natural tiles (B, d, 3, 4) of time row ``n`` of a RK_LAYOUT_TILE3 plan, whatever the records' layout: a packed
+        step lies in one or two stripe rows, and only those are downloaded."""
+        N, T, waves = self.N, self.B * self.d, self.packed_waves()
+        n = int(n) % (N + 1)
+        if not (waves and 1 <= n < N):
+            return self._tile3_mirror(self.var_state.slice0_host(n))
+        t = self.var_state.slice0_host(n) if 4 * waves < T else np.empty((self.B, self.d, 3, 4))     # (a ragged last tile-wave)
+        k, lo = n >> 2, (n & 3) * 36                                            # the step's 4 x 9 doubles inside the group's 3 x 48
+        r0, r1 = lo // 48, (lo + 35) // 48
+        rows = [self.var_state.slice0_host(3 * k + 1 + r).reshape(-1)[:waves * 48].reshape(waves, 48) for r in range(r0, r1 + 1)]
+        rec = np.concatenate(rows, axis=1)[:, lo - 48 * r0:lo - 48 * r0 + 36].reshape(4 * waves, 9)
+        self._tile3_fill(t.reshape(T, 3, 4)[:4 * waves], rec)
+        return self._tile3_mirror(t)
+
+    def mean_rows_host(self, ind):
+        """The posterior means (B, len(ind), d, p) at the time indices ``ind``: only the rows needed are downloaded."""
+        rows = []
+        for n in ind:
+            if self.layout == _lib.LAYOUT_TILE3:
+                rows.append(self.tile3_row_host(n)[..., 3])
+            elif self.layout in TILE_LAYOUTS:
+                rows.append(self.records_mean_var(self.var_state.slice0_host(int(n)))[0])      # (B, d, p) means
+            elif self.layout == _lib.LAYOUT_TRAJ_MAJOR:
+                rows.append(self.mean_state.to_host()[:, int(n)])
+            else:
+                rows.append(np.moveaxis(self.mean_state.slice0_host(int(n)), -1, 0))           # (d, p, B) -> (B, d, p)
+        return np.stack(rows, axis=1)
+
     def state_host(self):
-        """(mean, var) of the last filter() / mv() in the reference layout (views of one download, no transposes)."""
+        """(mean, var) of the last filter() / mv() in the reference layout (views of one download, no transposes; packed p = 3
+        records are gathered into their natural tiles first)."""
         if self.layout in TILE_LAYOUTS:
-            mean, var = self.records_mean_var(np.moveaxis(self.var_state.to_host(), 1, 0))     # (B, N+1, d, ...)
+            raw = self.var_state.to_host()
+            if self.layout == _lib.LAYOUT_TILE3:
+                raw = self._tile3_mirror(self.tile3_unpack(raw, self.packed_waves()))
+            mean, var = self.records_mean_var(np.moveaxis(raw, 1, 0))                          # (B, N+1, d, ...)
             return (mean, var) if self.batched else (mean[0], var[0])
         if self.layout == _lib.LAYOUT_TRAJ_MAJOR:                    # already the reference layout
             mean, var = self.mean_state.to_host(), self.var_state.to_host()
@@ -600,7 +684,8 @@ def _eval_at_device(key, ode_fun, W, x0, t_min, t_max, n_steps, interrogate, pri
     mean, var = dev.empty((filt.B, T, filt.d, filt.p)), dev.empty((filt.B, T, filt.d, filt.p, filt.p))
     q = _lib.EvalAtIn(n_query=T, n_quad=int(trans[0].shape[0]), query=query.ptr, trans=trans_dev.ptr, trans_batched=trans[1],
                       noise=noise_dev.ptr, noise_batched=noise[1])
-    _lib.check(dev.lib.rk_eval_at(dev.h, C.byref(filt.cfg), filt.layout, C.byref(filt._out), C.byref(smooth._out), C.byref(q),
+    # (the smoother's records may be the packed form of the filter's layout: rk_eval_at takes that id and reads `filt` as natural)
+    _lib.check(dev.lib.rk_eval_at(dev.h, C.byref(filt.cfg), smooth.records_layout, C.byref(filt._out), C.byref(smooth._out), C.byref(q),
                                   mean.ptr, var.ptr))
     m, v = mean.to_host(), var.to_host()
     return (m, v) if filt.batched else (m[0], v[0])
