@@ -481,6 +481,33 @@ int rk_fenrir_grid_solve_mv(rk_handle h, const rk_solve_cfg* cfg, const rk_solve
                             const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
                             const rk_grid_in* g, void* workspace);
 
+/* fenrir_grid_jvp (an addition): rk_fenrir_grid_loglik's value and its directional derivatives, forward mode, with respect to the
+ * ODE parameters and the initial state.  The first eleven arguments are rk_fenrir_grid_loglik's (out->mean_state / var_state
+ * receive the batch-minor filtered moments), the directions rk_dalton_grid_jvp's: dtheta (n_dir, n_theta), or (n_dir, n_theta,
+ * n_traj) batch-minor with dtheta_batched; dinit (n_dir, n_block, n_bstate), or (n_dir, n_block, n_bstate, n_traj) with
+ * dinit_batched; a NULL array is a zero direction in that argument.  value (n_traj) = log p(Y | Z); dvalue (n_traj, n_dir),
+ * trajectory-major: dvalue[b n_dir + k] is the derivative of value[b] along direction k.  Both are overwritten, one writer per
+ * element, no atomics (with several blocks the block sums are added in block order): two calls give the same bits.  It is the
+ * exact derivative of the filters' formulas as computed; a y term the value drops (|w| <= 1e-8) contributes nothing.
+ * Two kernels: fenrir_grid_jvp_fwd_kernel (fenrir_grad_kernels.hpp), a (trajectory, direction) item per lane, writes every item's
+ * tangent records to `workspace` -- rk_fenrir_grid_jvp_workspace_bytes: (n_steps + 1) n_block (n_bstate + n_bstate^2) n_traj
+ * n_dir doubles, item-minor -- and fenrir_grid_jvp_bwd_kernel (fenrir_grad.hip), a lane per (block, item), reads them.  The
+ * directions are independent: a caller short of memory runs them in chunks.
+ * Served: kalman_type standard, n_bmeas = 1, n_bobs = 1, interrogate rodeo / schober / kramer, fitzhugh_nagumo and lorenz63 at
+ * n_bstate 2..3, and a user right-hand side of the gradient kind (hiprtc, JIT_FENRIR_GRAD) with n_block n_bstate^2 <= 27;
+ * cfg->flags must carry RK_FLAG_BATCH_MINOR.  What is not served is refused on cfg, n_bobs and n_dir alone -- RK_ERR_INVALID (a
+ * non-positive size, n_dir < 1, RK_FLAG_BATCH_MINOR missing) or RK_ERR_UNSUPPORTED ("not built") -- before the handle or any
+ * pointer is looked at.                                                                                                      */
+int rk_fenrir_grid_jvp_workspace_bytes(const rk_solve_cfg* cfg, int32_t n_dir, size_t* bytes);
+int rk_fenrir_grid_jvp(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
+                       const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
+                       const rk_grid_in* g, int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit,
+                       int32_t dinit_batched, void* workspace, double* value, double* dvalue);
+/* Build rk_fenrir_grid_jvp's forward kernel for a registered right-hand side of the gradient kind without a device, as
+ * rk_dalton_grad_compile_check does for rk_dalton_grid_jvp's, or around a built-in right-hand side (its id); RK_ERR_INVALID
+ * with the compiler's log otherwise.                                                                                        */
+int rk_fenrir_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate);
+
 /* solve_sim_draws (an addition): n_draws sample paths per trajectory from one forward filter.  Runs the forward pass of
  * rk_solve_filter (cfg must carry RK_FLAG_BATCH_MINOR; out->mean_state / var_state hold the filtered moments afterwards), then
  * one backward kernel, one lane per (chunk of draws, block, trajectory), which does the work that no draw changes -- the

@@ -1,0 +1,286 @@
+// fenrir_grid_jvp / fenrir_grid_grad / fenrir_grad (an addition): host side of rk_fenrir_grid_jvp,
+// directional derivatives of rk_fenrir_grid_loglik's value with respect to the ODE parameters and the initial state, and the
+// backward kernel.  Two launches: fenrir_grid_jvp_fwd_kernel (fenrir_grad_kernels.hpp), one (trajectory, direction) item per
+// lane, which stores the primal filtered records in the plan's batch-minor mean / var and every item's tangent records in the
+// caller's workspace; then fenrir_grid_jvp_bwd_kernel (below), one lane per (block, item), the derivative of fenrir_grid's
+// backward Markov chain; with more than one block, magi_sum_kernel twice (launch_block_sum).  Standard form, n_bmeas = 1,
+// n_bobs = 1, built-in FitzHugh-Nagumo and Lorenz63, or a user right-hand side of the gradient kind (hiprtc, rhs_jit.hip's
+// JIT_FENRIR_GRAD, the forward kernel only: the backward kernel has no right-hand side).  The sizes test, the grid's staging,
+// the test of the output pointers and the launch patterns are grid_entry.hpp's; the rest of the configuration check is worded
+// for this entry alone ("not built: ...").
+#include "common.hpp"
+#include "rhs.hpp"
+#include "kalman_small.hpp"
+#include "solve_args.hpp"
+#include "solve_paths.hpp"
+#include "grid_entry.hpp"
+#include "grid_kernels.hpp"
+#include "fenrir_kernels.hpp"
+#include "records.hpp"
+#include "fenrir_grad_kernels.hpp"
+
+namespace rk {
+
+// The tangent of fenrir_markov_step<P> along one direction: given filt[n] = (mf, Sf), pred[n + 1] = (mp, Sp) and their tangents,
+// the carry (bm, bS) BEFORE the primal step overwrites it and its tangent (dbm, dbS), which is stepped in place.
+//   T = Sigma_f Q^T, T. = Sigma._f Q^T ;  G = T (Sigma-)^-1, G. = (T. - G Sigma.-) (Sigma-)^-1  (a second LU solve on Sigma-, with
+//   the transposed right-hand side as smooth_gain does; smooth_gain itself gives T and G)
+//   b = mu_f - G mu-            b. = mu._f - G. mu- - G mu.-
+//   C = Sigma_f - G T^T         C. = Sigma._f - G. T^T - G T.^T
+//   m <- G m + b                m. <- G. m + G m. + b.
+//   S <- G S G^T + C            S. <- G. S G^T + G S. G^T + G S G.^T + C.
+template <int P>
+__device__ __forceinline__ void jvp_markov_step(const double (&Q)[P][P], const double (&Sf)[P][P], const double (&mp)[P],
+                                                const double (&Sp)[P][P], const double (&dmf)[P], const double (&dSf)[P][P],
+                                                const double (&dmp)[P], const double (&dSp)[P][P], const double (&bm)[P],
+                                                const double (&bS)[P][P], double (&dbm)[P], double (&dbS)[P][P]) {
+    double T[P][P], G[P][P], dT[P][P], dG[P][P];
+    smooth_gain<P>(Q, Sf, Sp, T, G);
+    mm_nt<P, P, P>(dSf, Q, dT);
+    {
+        double GdS[P][P], A[P][P], X[P][P];
+        mm<P, P, P>(G, dSp, GdS);
+#pragma unroll
+        for (int i = 0; i < P; ++i)
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                A[i][j] = Sp[i][j];
+                X[i][j] = dT[j][i] - GdS[j][i];
+            }
+        lu_solve<P, P>(A, X);
+#pragma unroll
+        for (int i = 0; i < P; ++i)
+#pragma unroll
+            for (int j = 0; j < P; ++j) dG[i][j] = X[j][i];
+    }
+    double dGT[P][P], GdT[P][P], GS[P][P], dGS[P][P], GdbS[P][P], t1[P][P], t2[P][P], t3[P][P];
+    mm_nt<P, P, P>(dG, T, dGT);                                         // G. T^T
+    mm_nt<P, P, P>(G, dT, GdT);                                         // G T.^T
+    mm<P, P, P>(G, bS, GS);
+    mm<P, P, P>(dG, bS, dGS);
+    mm<P, P, P>(G, dbS, GdbS);
+    mm_nt<P, P, P>(dGS, G, t1);                                         // G. S G^T
+    mm_nt<P, P, P>(GdbS, G, t2);                                        // G S. G^T
+    mm_nt<P, P, P>(GS, dG, t3);                                         // G S G.^T
+    double nm[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const double db = dmf[r] - dot<P>(dG[r], mp) - dot<P>(G[r], dmp);
+        nm[r] = dot<P>(dG[r], bm) + dot<P>(G[r], dbm) + db;
+#pragma unroll
+        for (int c = 0; c < P; ++c) dbS[r][c] = t1[r][c] + t2[r][c] + t3[r][c] + (dSf[r][c] - dGT[r][c] - GdT[r][c]);
+    }
+#pragma unroll
+    for (int r = 0; r < P; ++r) dbm[r] = nm[r];
+}
+
+// ---- backward filter and its tangent (n_bobs = 1) --------------------------------------------------------------------------------
+// fenrir_grid_bwd_kernel<P, false, 1>'s recursion (fenrir_grid.hip), a sibling of it, not an edit: one lane per (block, item) on
+// bwd_lane_geom(B K, D), item = b K + k.  The primal record is read at index b of the plan's batch-minor mean / var, the tangent
+// record at index `item` of dmean / dvar (B K items wide), the pair by grid_load_pair.  The prefetch discipline is that kernel's:
+// the records -- primal and tangent -- and the pair of step n - 1 are fetched before step n computes and rotated in behind it,
+// the slot one step further ahead, everything issued before the loop is complete before the loop is entered, and the node of
+// the next observation is held in a register.  Per step: predict_block / jvp_predict_block re-evaluate pred[n + 1] and its
+// tangent from filt[n], jvp_markov_step runs on the carry before fenrir_markov_step overwrites it, and where node n is observed
+// jvp_observe runs before fenrir_observe_scalar -- node 0 and node N like any other.  A y term the value drops (|w| <= 1e-8)
+// adds nothing to the derivative (jvp_update's rule).
+// No atomics: every lane writes its block's dacc to dpart[blk * B K + item], the k = 0 item writes acc to part[blk * B + b], and
+// magi_sum_kernel adds them in block order; with one block part / dpart are value / dvalue themselves.
+template <int P>
+__global__ void __launch_bounds__(64) fenrir_grid_jvp_bwd_kernel(SolveArgs a, DaltonObs o, GridArgs g, int K,
+                                                                 const double* __restrict__ dmean, const double* __restrict__ dvar,
+                                                                 double* __restrict__ part, double* __restrict__ dpart) {
+    const long long n_items = (long long)a.B * K;
+    const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_items * a.D) return;
+    const int blk = (int)(l / n_items), item = (int)(l - (long long)blk * n_items);
+    const int b = item / K, k = item - b * K;
+    const size_t B = (size_t)a.B, BK = (size_t)n_items;
+    double bm[P], bS[P][P], dbm[P], dbS[P][P];
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, bm, bS);       // terminal point (fenrir.py:186-188)
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(dmean, dvar, BK, a.D, a.N, blk, item, dbm, dbS);
+    double acc = 0.0, dacc = 0.0;
+    int i = o.n_obs - 1;
+    int obs_node = i >= 0 ? o.obs_ind[i] : -1;                              // node of observation i; -1: none left
+    auto observe = [&]() {
+        jvp_observe<P>(o, (size_t)i * a.D + blk, bm, bS, dbm, dbS, dacc);   // (before the primal update of the carry)
+        fenrir_observe_scalar<P>(o, (size_t)i * a.D + blk, bm, bS, acc);
+        --i;
+        obs_node = i >= 0 ? o.obs_ind[i] : -1;
+        asm volatile("" : "+v"(obs_node));                                  // waited for here, on the rare path, not behind a prefetch
+    };
+    if (obs_node >= a.N) observe();                                         // fenrir.py:189-209
+
+    double mf[P], Sf[P][P], dmf[P], dSf[P][P], Q[P][P], R[P][P];
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(dmean, dvar, BK, a.D, a.N - 1, blk, item, dmf, dSf);
+    grid_load_pair<P>(g, a.B, a.D, grid_slot(g, a.N - 1), blk, b, Q, R);
+    int s_next = a.N >= 2 ? g.slot[a.N - 2] : 0;              // slot of step n - 1 as the table has it: clamped where it is used
+    // every load so far is complete before the loop is entered, so that no step waits for its own prefetch (grid_fwd_kernel)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    for (int n = a.N - 1; n >= 0; --n) {
+        const bool more = n >= 1;
+        double mfn[P], Sfn[P][P], dmfn[P], dSfn[P][P], Qn[P][P], Rn[P][P];
+        int s_after = 0;
+        if (more) {
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(dmean, dvar, BK, a.D, n - 1, blk, item, dmfn, dSfn);
+            grid_load_pair<P>(g, a.B, a.D, grid_clamp(g, s_next), blk, b, Qn, Rn);
+            if (n >= 2) s_after = g.slot[n - 2];
+        }
+        double mp[P], Sp[P][P], dmp[P], dSp[P][P], G[P][P];
+        predict_block<P>(Q, R, mf, Sf, mp, Sp);                             // pred[n + 1] from filt[n] and the pair of step n
+        jvp_predict_block<P>(Q, dmf, dSf, dmp, dSp);
+        jvp_markov_step<P>(Q, Sf, mp, Sp, dmf, dSf, dmp, dSp, bm, bS, dbm, dbS);              // (the carry is still step n + 1's)
+        fenrir_markov_step<P>(Q, mf, Sf, mp, Sp, bm, bS, G);
+        if (obs_node == n) observe();                                       // fenrir.py:155-170 (the same in every lane of the wave)
+        if (more) {
+            asm volatile("" : "+v"(s_after));                 // the fetched slot stays in a vector register until here (grid_fwd_kernel)
+            s_next = s_after;
+#pragma unroll
+            for (int r = 0; r < P; ++r) {
+                mf[r] = mfn[r];
+                dmf[r] = dmfn[r];
+#pragma unroll
+                for (int c = 0; c < P; ++c) {
+                    Sf[r][c] = Sfn[r][c];
+                    dSf[r][c] = dSfn[r][c];
+                    Q[r][c] = Qn[r][c];
+                    R[r][c] = Rn[r][c];
+                }
+            }
+        }
+    }
+    dpart[(size_t)blk * BK + item] = dacc;
+    if (k == 0) part[(size_t)blk * B + b] = acc;
+}
+
+// ---- dispatch ---------------------------------------------------------------------------------------------------
+// The rule an instance ships by: the forward kernel uses no more scratch than grid_fwd_kernel<RHS, P,
+// ITG>, the backward kernel no more than fenrir_grid_bwd_kernel<P, false, 1>.  profiles/fenrir_grad_code_objects.txt has every
+// instance next to its yardstick (scripts/fenrir_grad_code_objects.py).  What is built is what jvp_interrogate's register set gave
+// DALTON: n_bstate 2 and 3 of FitzHugh-Nagumo and Lorenz63 (D P^2 <= 27).
+constexpr int FENRIR_GRAD_PMIN = 2, FENRIR_GRAD_PMAX = 3;
+template <class RHS>
+constexpr bool fenrir_grad_has_rhs() { return std::is_same<RHS, FitzHughNagumo>::value || std::is_same<RHS, Lorenz63>::value; }
+
+// Is this call served?  Decided on the configuration, n_bobs and n_dir alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
+static int fenrir_grad_check(const rk_solve_cfg* c, int n_bobs, int n_dir) {
+    const int rc = grid_sizes_check("fenrir_grid_jvp", c);               // (grid_entry.hpp; from here on the wording is this entry's own)
+    if (rc) return rc;
+    RK_REQUIRE(n_dir >= 1, RK_ERR_INVALID, "fenrir_grid_jvp: n_dir must be at least 1, got %d", n_dir);
+    RK_REQUIRE((long long)c->n_traj * n_dir * c->n_block <= 0x7fffffffLL, RK_ERR_INVALID,
+               "fenrir_grid_jvp: n_traj * n_dir * n_block = %lld exceeds 2^31 - 1", (long long)c->n_traj * n_dir * c->n_block);
+    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "fenrir_grid_jvp: cfg->flags must carry RK_FLAG_BATCH_MINOR");
+    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: RK_FLAG_STORE_PRED is not served");
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: kalman_type %d (standard only)",
+               c->kalman_type);
+    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_KRAMER, RK_ERR_UNSUPPORTED,
+               "fenrir_grid_jvp: not built: interrogate id %d (rodeo, schober, kramer)", c->interrogate);
+    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: n_bmeas = %d (1 only)", c->n_bmeas);
+    RK_REQUIRE(n_bobs == 1, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: n_bobs = %d (1 only: the derivative of the "
+               "eigendecomposition's cut-off density is out of scope)", n_bobs);
+    if (is_user_rhs(c->rhs_id)) return user_fenrir_grad_check(c);
+    bool known = false;
+    with_builtin_rhs(c->rhs_id, [&](auto rhs) { known = fenrir_grad_has_rhs<decltype(rhs)>(); });
+    RK_REQUIRE(known, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: rhs %d (fitzhugh_nagumo and lorenz63)", c->rhs_id);
+    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: rhs %d needs another n_block than %d",
+               c->rhs_id, c->n_block);
+    RK_REQUIRE(c->n_bstate >= FENRIR_GRAD_PMIN && c->n_bstate <= FENRIR_GRAD_PMAX, RK_ERR_UNSUPPORTED,
+               "fenrir_grid_jvp: not built: rhs %d at n_bstate %d (%d .. %d)", c->rhs_id, c->n_bstate, FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX);
+    return RK_OK;
+}
+
+// bytes of the tangent records of n_dir directions: dmean (N+1, D, P, B n_dir) then dvar (N+1, D, P, P, B n_dir)
+static size_t fenrir_grad_ws_bytes(const rk_solve_cfg* c, int n_dir) {
+    return sizeof(double) * (size_t)(c->n_steps + 1) * c->n_block * ((size_t)c->n_bstate + (size_t)c->n_bstate * c->n_bstate) *
+           (size_t)c->n_traj * (size_t)n_dir;
+}
+
+static int fenrir_grid_jvp_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga, const JvpDirs& dir,
+                                   double* dmean, double* dvar) {
+    return launch_by_rhs(c, a, [&] { return user_fenrir_grad(h, c, a, ga, dir, a.B * dir.K, dmean, dvar); }, [&](auto rhs) {
+        using RHS = decltype(rhs);
+        if constexpr (fenrir_grad_has_rhs<RHS>()) {
+            const LaunchGeom g = dalton_lane_geom(a.B * dir.K, false);      // 64 (trajectory, direction) items per wave
+            return launch_fwd_instance<FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX, RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
+                h, c, "fenrir_grid_jvp_fwd_kernel", "fenrir_grid_jvp", [&](auto P, auto I) {
+                    hipLaunchKernelGGL((fenrir_grid_jvp_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga, dir, dmean, dvar);
+                });
+        } else {
+            return (int)RK_ERR_UNSUPPORTED;                                 // (fenrir_grad_check has refused it)
+        }
+    });
+}
+
+static int fenrir_grid_jvp_backward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
+                                    int K, const double* dmean, const double* dvar, double* part, double* dpart) {
+    const LaunchGeom g = bwd_lane_geom(a.B * K, a.D);
+    LaunchTimer t(h, "fenrir_grid_jvp_bwd_kernel");
+    const bool ok = dispatch_int<FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX>(c->n_bstate, [&](auto P) {
+        hipLaunchKernelGGL((fenrir_grid_jvp_bwd_kernel<P>), g.grid, g.block, 0, h->stream, a, o, ga, K, dmean, dvar, part, dpart);
+    });
+    RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: no backward kernel for n_bstate %d", c->n_bstate);
+    t.stop();
+    RK_HIP(hipGetLastError());
+    return RK_OK;
+}
+
+}  // namespace rk
+
+using namespace rk;
+
+extern "C" {
+
+int rk_fenrir_grid_jvp_workspace_bytes(const rk_solve_cfg* c, int32_t n_dir, size_t* bytes) {
+    RK_REQUIRE(c && bytes, RK_ERR_INVALID, "rk_fenrir_grid_jvp_workspace_bytes: null argument");
+    const int rc = grid_sizes_check("fenrir_grid_jvp", c);
+    if (rc) return rc;
+    RK_REQUIRE(n_dir >= 1, RK_ERR_INVALID, "fenrir_grid_jvp: n_dir must be at least 1, got %d", n_dir);
+    *bytes = fenrir_grad_ws_bytes(c, n_dir);
+    return RK_OK;
+}
+
+int rk_fenrir_grid_jvp(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
+                       const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
+                       const rk_grid_in* g, int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit,
+                       int32_t dinit_batched, void* workspace, double* value, double* dvalue) {
+    const char* who = "rk_fenrir_grid_jvp (fenrir_grid_jvp)";
+    RK_REQUIRE(c, RK_ERR_INVALID, "%s: null cfg", who);
+    int rc = fenrir_grad_check(c, n_bobs, n_dir);                   // (the configuration alone, before anything else is looked at)
+    if (rc) return rc;
+    RK_REQUIRE(h && out && g && workspace && value && dvalue, RK_ERR_INVALID, "%s: null argument", who);
+    GridArgs ga;
+    rc = grid_args(who, g, ga);
+    if (rc) return rc;
+    rc = check_cfg(c, in);
+    if (rc) return rc;
+    RK_REQUIRE(n_obs >= 0 && (n_obs == 0 || (obs && obs_weight && obs_var && obs_node)), RK_ERR_INVALID,
+               "%s: null observation array or n_obs < 0", who);
+    rc = grid_out_check(who, out, RK_MODE_MV);
+    if (rc) return rc;
+    rc = begin_solve(h);
+    if (rc) return rc;
+    SolveArgs a;
+    make_args(c, in, out, a);
+    const DaltonObs o{obs, obs_weight, obs_var, obs_node, n_obs};
+    const JvpDirs dir{dtheta, dinit, dtheta_batched != 0, dinit_batched != 0, n_dir};
+    const size_t BK = (size_t)a.B * (size_t)n_dir;
+    double* dmean = (double*)workspace;
+    double* dvar = dmean + (size_t)(a.N + 1) * a.D * c->n_bstate * BK;
+    rc = fenrir_grid_jvp_forward(h, c, a, ga, dir, dmean, dvar);
+    if (rc) return rc;
+    double *part = value, *dpart = dvalue;                          // one block: the lanes write value / dvalue themselves
+    if (a.D > 1) {
+        rc = lane_scratch(h, sizeof(double) * (size_t)a.D * ((size_t)a.B + BK), &part);
+        if (rc) return rc;
+        dpart = part + (size_t)a.D * a.B;
+    }
+    rc = fenrir_grid_jvp_backward(h, c, a, o, ga, n_dir, dmean, dvar, part, dpart);
+    if (rc || a.D == 1) return rc;
+    rc = launch_block_sum(h, part, a.B, a.D, value);                // block order, B and then B K sums: two calls give the same bits
+    if (rc) return rc;
+    return launch_block_sum(h, dpart, (int)BK, a.D, dvalue);
+}
+
+}  // extern "C"

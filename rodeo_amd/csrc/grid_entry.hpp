@@ -1,7 +1,7 @@
 // What the host sides of the non-uniform-grid entries share (host code only, not part of the hiprtc set; DESIGN.md section 7
 // (22)): the configuration check in pieces, the staging of rk_grid_in and the test of the output pointers -- the longer bodies
 // are in grid.hip -- and the three launch patterns as templates.  Included by grid.hip, grid_calib.hip, grid_draws.hip,
-// dalton_grid.hip, daltonng_grid.hip, fenrir_grid.hip and dalton_grad.hip, and by dynamic.hip for the launch patterns.
+// dalton_grid.hip, daltonng_grid.hip, fenrir_grid.hip, dalton_grad.hip and fenrir_grad.hip, and by dynamic.hip for the launch patterns.
 #pragma once
 #include "common.hpp"
 #include "solve_paths.hpp"

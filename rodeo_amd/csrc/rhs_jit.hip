@@ -83,6 +83,7 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_DALTONNG_GRID      */ {"rk::daltonng_grid_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, false>", "daltonng_grid_kernels.hpp", "daltonng_grid_fwd_kernel<store>"},
     /* JIT_DALTONNG_GRID_BOTH */ {"rk::daltonng_grid_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, true>", "daltonng_grid_kernels.hpp", "daltonng_grid_fwd_kernel<both>"},
     /* JIT_DALTON_GRAD        */ {"rk::dalton_grid_jvp_kernel<rk::UserRhsT, {P}, {I}>", "dalton_grad_kernels.hpp", "dalton_grid_jvp_kernel<user>"},
+    /* JIT_FENRIR_GRAD        */ {"rk::fenrir_grid_jvp_fwd_kernel<rk::UserRhsT, {P}, {I}>", "fenrir_grad_kernels.hpp", "fenrir_grid_jvp_fwd_kernel<user>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -261,13 +262,16 @@ static int jit_program(const JitKey& key, JitProgram& p) {
     int rc = is_user_rhs(key.rhs) ? user_rhs(key.rhs, &u) : RK_OK;
     if (rc == RK_OK && key.obs >= 0) rc = user_obs(key.obs, &ob);
     if (rc) return rc;
-    RK_REQUIRE(u || ob, RK_ERR_INVALID, "unknown user rhs_id %d", key.rhs);
+    // (neither: a built-in right-hand side under a kind that names one -- rk_fenrir_grad_compile_check's check of the header)
+    const char* builtin = !u && !ob && strstr(row.expr, "UserRhsT") ? builtin_rhs_type(key.rhs) : nullptr;
+    RK_REQUIRE(u || ob || builtin, RK_ERR_INVALID, "unknown user rhs_id %d", key.rhs);
     if (ob) p.src = std::string("#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n") +
                     (u ? "" : "#include \"rhs.hpp\"\n");                // (a user's names stay free)
     else p.src = "#include \"solve_small_kernels.hpp\"\n#include \"dual.hpp\"\n"
                  "#include \"solve_tile3_kernels.hpp\"\n#include \"solve_tile4_kernels.hpp\"\n"
                  "#include \"solve_tilen_kernels.hpp\"\n#include \"solve_sqrt_kernels.hpp\"\n"
                  "#include \"solve_small_m_kernels.hpp\"\n#include \"solve_dense_itg_kernels.hpp\"\n";
+    if (builtin) p.src += "#include \"rhs.hpp\"\n";
     if (row.header) p.src += std::string("#include \"") + row.header + "\"\n";
     p.src += "namespace rk {\n";
     if (u) {
@@ -280,8 +284,8 @@ static int jit_program(const JitKey& key, JitProgram& p) {
     if (ob) p.src += ob->source + "\nusing UserObsT = " + ob->type_name + ";\n";
     p.src += "}  // namespace rk\n";
     p.expr = kernel_expr(key, ob ? ob->n_active : 0);
-    p.what = ob ? ob->type_name : u->type_name;
-    p.role = ob ? "observation log-likelihood" : "user right-hand side";
+    p.what = ob ? ob->type_name : u ? u->type_name : builtin;
+    p.role = ob ? "observation log-likelihood" : u ? "user right-hand side" : "built-in right-hand side";
     return RK_OK;
 }
 
@@ -564,6 +568,27 @@ int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, con
     return launch_jit(h, jit_key(JIT_DALTON_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, true), params);
 }
 
+// fenrir_grid_jvp's forward kernel around a user right-hand side of the gradient kind (fenrir_grad_kernels.hpp): dalton_grid_jvp's
+// rule under this entry's name (n_block, n_bmeas = 1, n_bstate 2 .. 3, n_block n_bstate^2 <= 27: DESIGN.md section 7 (23)), then
+// the launch, one (trajectory, direction) item per lane like fenrir_grad.hip's.
+int user_fenrir_grad_check(const rk_solve_cfg* c) {
+    const int rc = user_lane_check(c, "fenrir_grid_jvp");
+    if (rc) return rc;
+    RK_REQUIRE(c->n_bstate >= 2 && c->n_bstate <= 3 && c->n_block * c->n_bstate * c->n_bstate <= 27, RK_ERR_UNSUPPORTED,
+               "fenrir_grid_jvp: not built: a user right-hand side with %d blocks at n_bstate %d (n_bstate 2 .. 3 and n_block "
+               "n_bstate^2 <= 27)", c->n_block, c->n_bstate);
+    return RK_OK;
+}
+
+int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir, int n_items,
+                     double* dmean, double* dvar) {
+    const int rc = user_fenrir_grad_check(c);
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&g, (void*)&dir, &dmean, &dvar};
+    return launch_jit(h, jit_key(JIT_FENRIR_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, false), params);
+}
+
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm) {
     const int rc = user_rhs_check(c);
@@ -710,6 +735,20 @@ int rk_dalton_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t inter
     c.n_bstate = n_bstate;
     c.interrogate = interrogate;
     return jit_lookup(jit_key(JIT_DALTON_GRAD, rhs_id, &c), nullptr, nullptr);
+}
+
+// the same for fenrir_grid_jvp's forward kernel; a built-in id builds the kernel around that right-hand side, which shows without
+// a device that fenrir_grad_kernels.hpp is RTC-safe (a built-in one without rhs_generic fails like a source of the solver's kind)
+int rk_fenrir_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
+    if (!builtin_rhs_type(rhs_id)) {
+        const UserRhs* u;
+        const int rc = user_rhs(rhs_id, &u);
+        if (rc) return rc;
+    }
+    rk_solve_cfg c{};
+    c.n_bstate = n_bstate;
+    c.interrogate = interrogate;
+    return jit_lookup(jit_key(JIT_FENRIR_GRAD, rhs_id, &c), nullptr, nullptr);
 }
 
 }  // extern "C"

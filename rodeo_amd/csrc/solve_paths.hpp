@@ -68,6 +68,7 @@ enum JitKind : int {
     JIT_DALTONNG_GRID = 29,   // daltonng_grid_fwd_kernel<.., false> (solve_mv_nn_grid, the joint filter's moments)
     JIT_DALTONNG_GRID_BOTH = 30,  // daltonng_grid_fwd_kernel<.., true> (daltonng_grid, the joint filter and the filter on Z alone)
     JIT_DALTON_GRAD = 31,     // dalton_grid_jvp_kernel (dalton_grid_jvp: value and directional derivatives; a gradient-kind source)
+    JIT_FENRIR_GRAD = 32,     // fenrir_grid_jvp_fwd_kernel (fenrir_grid_jvp: the forward tangent filter; a gradient-kind source)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -117,6 +118,10 @@ struct JvpDirs;
 int user_dalton_grad_check(const rk_solve_cfg* c);
 int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, const JvpDirs& dir,
                      int n_items, double* value, double* dvalue);
+// fenrir_grid_jvp: the same for its forward kernel (fenrir_grad.hip); dmean / dvar are the tangent records of the n_items items
+int user_fenrir_grad_check(const rk_solve_cfg* c);
+int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir, int n_items,
+                     double* dmean, double* dvar);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them

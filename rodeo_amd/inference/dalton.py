@@ -248,9 +248,10 @@ def _grad_ode(who, ode_fun, W, params):
                               "lorenz63, or a traced Python function)")
 
 
-def _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight, names, params):
+def _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight, names, params, sibling="dalton_grid"):
     """What the gradient kernels do not serve (NotImplementedError, "not built") and the names a derivative is asked for
-    (ValueError for an unknown one), before any device work.  Returns the right-hand side to run (``_grad_ode``)."""
+    (ValueError for an unknown one), before any device work.  Returns the right-hand side to run (``_grad_ode``).  ``sibling``
+    names the value call whose kernel is the yardstick of the size limit (``fenrir.py`` passes its own)."""
     from ..solve import _interrogate_id
     if kalman_type != "standard":
         raise NotImplementedError(f"{who}: not built: kalman_type {kalman_type!r} (the standard form only)")
@@ -266,7 +267,7 @@ def _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight,
                                   "eigendecomposition's cut-off density is out of scope)")
     if not _GRAD_BSTATE[0] <= W[-1] <= _GRAD_BSTATE[1]:
         raise NotImplementedError(f"{who}: not built: n_bstate = {W[-1]} ({_GRAD_BSTATE[0]} .. {_GRAD_BSTATE[1]}: beyond, the kernel "
-                                  "needs more scratch than dalton_grid's)")
+                                  f"needs more scratch than {sibling}'s)")
     if W[-3] * W[-1] ** 2 > _GRAD_STATE_MAX:
         raise NotImplementedError(f"{who}: not built: {W[-3]} blocks at n_bstate = {W[-1]} (n_block n_bstate^2 <= {_GRAD_STATE_MAX})")
     ode = _grad_ode(who, ode_fun, W, params)

@@ -19,7 +19,11 @@ observations at their own times, between grid nodes where they fall there (``rk_
 ``fenrir_grid`` / ``solve_mv_grid`` (an addition, imported from this module like ``fenrir_at``): the likelihood and the
 data-adaptive solver on a non-uniform grid shared by the batch, every observation on a node (``rk_fenrir_grid_loglik`` /
 ``rk_fenrir_grid_solve_mv``).
+``fenrir_grid_jvp`` / ``fenrir_grid_grad`` / ``fenrir_grad`` (an addition, imported from this module likewise): ``fenrir_grid``'s
+value with its derivatives in the ODE parameters and the initial state, forward mode on the device (``rk_fenrir_grid_jvp``,
+DESIGN.md section 7 (23)).
 """
+import collections
 import ctypes as C
 import os
 import numpy as np
@@ -211,6 +215,149 @@ def _solve_grid(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_a
         raise RuntimeError(f"fenrir.solve_mv_grid: the plan reports layout {plan.layout}, not the batch-minor records")
     plan.sync()                                                     # (the sweep has read the workspace before it is released)
     return plan
+
+
+# --- Fenrir gradients on the device (an addition) --------------------------------------------------
+
+FenrirGrad = collections.namedtuple("FenrirGrad", ["value", "grad"])
+
+# The tangent records of one call grow with the direction count K ((N + 1) d (p + p^2) B K doubles).  The directions are
+# independent, so they run in chunks whose records fit this many bytes; a chunk is at least one direction.
+_GRAD_WORKSPACE_BYTES = 2 ** 32
+
+
+def _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var, tangents,
+         kalman_type, params):
+    """``fenrir_grid_jvp``'s body: the gradient refusals (``dalton.py``'s helpers under this call's name), then ``fenrir_grid``'s in
+    its order, the directions, and -- unless the observation set is empty -- the cached plan with the grid, the observations and
+    the directions staged on it and one rk_fenrir_grid_jvp per chunk of directions.  Returns (value (B,), dvalue (B, K), batched)."""
+    from .. import grid
+    from ..solve import _shape_rule
+    from .dalton import _grad_config, _obs_nodes, _stage_directions
+    if not isinstance(tangents, dict):
+        raise ValueError(f"{who}: tangents must be a dict name -> directions")
+    ode_fun = _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight, list(tangents), params, sibling="fenrir_grid")
+    obs, D, Om, n_bobs = _check_obs(obs_data, obs_weight, obs_var)
+    node = _obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
+    ode, t, slot, pairs = grid._refusals(who, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
+    d, p = int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1])
+    if D.shape[1:] != (d, n_bobs, p):
+        raise ValueError(f"obs_weight must have shape (n_obs, {d}, n_bobs, {p})")
+    sizes = _shape_rule(ode, ode_weight, ode_init, pairs[0], params)[-1]
+    B, batched = (sizes[0], True) if sizes else (1, False)
+    K, dtheta, dtheta_b, dinit, dinit_b = _stage_directions(who, ode, tangents, B, batched, d, p)
+    if len(node) == 0:                                              # nothing is conditioned on: no plan, no launch
+        return np.zeros(B), np.zeros((B, K)), batched
+    plan, g, (p_obs, p_w, p_v, p_node, n_obs, n_bobs) = _grid_plan("fenrir_grid", ode, ode_weight, ode_init, t, slot, pairs, interrogate,
+                                                                   kalman_type, params, obs, D, Om, node, n_bobs)
+    per_dir = C.c_size_t(0)
+    _lib.check(plan.dev.lib.rk_fenrir_grid_jvp_workspace_bytes(C.byref(plan.cfg), 1, C.byref(per_dir)))
+    K_c = min(K, max(1, _GRAD_WORKSPACE_BYTES // per_dir.value))
+    ws = plan.dev.empty((K_c * per_dir.value // 8,))                # the tangent records of one chunk: released on return
+    value, dvalue = None, np.zeros((plan.B, K))
+    for ci, k0 in enumerate(range(0, K, K_c)):
+        k1 = min(K, k0 + K_c)
+        d_th, d_x0 = plan.staged(("fenrir_grad", ci), np.zeros(1) if dtheta is None else dtheta[k0:k1],
+                                 np.zeros(1) if dinit is None else dinit[k0:k1])
+        val, dval = plan.dev.empty((plan.B,)), plan.dev.empty((plan.B, k1 - k0))
+        plan.launch(plan.dev.lib.rk_fenrir_grid_jvp, key, _lib.MODE_FILTER, p_obs, p_w, p_v, p_node, n_obs, n_bobs, C.byref(g), k1 - k0,
+                    None if dtheta is None else d_th.ptr, dtheta_b, None if dinit is None else d_x0.ptr, dinit_b, ws.ptr, val.ptr,
+                    dval.ptr)
+        dvalue[:, k0:k1] = dval.to_host()
+        if value is None:                                           # (every chunk recomputes the same primal filter)
+            value = val.to_host()
+    plan.sync()                                                     # (the backward kernel has read the workspace before it is released)
+    return value, dvalue, batched
+
+
+def fenrir_grid_jvp(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                    obs_data, obs_times, obs_weight, obs_var, tangents, kalman_type="standard", **params):
+    """
+    ``fenrir_grid`` and its directional derivatives (an addition; forward mode, on the device): ``(value, dvalue)``.  The first
+    eleven arguments, ``kalman_type`` and ``**params`` are ``fenrir_grid``'s.  ``tangents`` is ``dalton_grid_jvp``'s: a dict that holds
+    K directions, its keys names of ``params`` and / or ``"ode_init"``; a parameter direction has shape (K, size), or (B, K, size)
+    when it differs per trajectory, an ``"ode_init"`` direction (K, d, p) or (B, K, d, p); a missing key is a zero direction.
+    ``value`` is ``fenrir_grid``'s result, a float or (B,); ``dvalue`` is (K,) or (B, K): entry k is the derivative of ``value`` along
+    direction k of (params, ode_init).  Imported from this module, not re-exported by ``rodeo_amd.inference``.
+
+    It is the exact derivative of ``fenrir_grid``'s formulas as the kernels compute them.  Forward, a (trajectory, direction) pair
+    per lane runs the data-free filter with its tangent and stores the tangent of every node's filtered moments; backward, a lane
+    per (block, trajectory, direction) runs the derivative of the Markov chain -- of the smoothing gain, of the chain's offset and
+    noise, of the conditioning on y -- next to the chain itself.  No atomics, and the block sums are added in block order: two
+    calls give the same bits.  The tangent records take (N + 1) d (p + p^2) B K doubles; beyond ``_GRAD_WORKSPACE_BYTES`` (4 GiB)
+    the directions run in chunks, which changes no bit of the result.
+
+    THE 1e-8 RULE.  A y term that ``fenrir_grid`` drops (a forecast variance |w| <= 1e-8, utils.py:60-78) contributes nothing to
+    the derivative either: where the value jumps, the derivative is that of the side the parameters are on.
+
+    Served: kalman_type "standard", n_bmeas = 1, n_bobs = 1, rodeo / schober / kramer, n_bstate 2 and 3 with n_block n_bstate^2
+    <= 27; ``rodeo_amd.ode.fitzhugh_nagumo``, ``lorenz63`` and plain Python right-hand sides (a function, or ``ode.from_python``'s
+    result: traced once more with generic parameters, ``rodeo_amd.trace.grad_from_python``, and built with hiprtc).
+    NotImplementedError ("not built") before any device work: interrogate_chkrebtii, the square-root form, n_bobs > 1,
+    n_bmeas > 1, another size or right-hand side, and a direction in the prior ("sigma"), ``ode_weight``, the data or the grid.
+    ValueError before any device work: an unknown name in ``tangents``, a direction of the wrong shape or non-finite, K = 0, and
+    whatever ``fenrir_grid`` refuses.  An empty observation set returns (0.0, zeros) without a launch.
+    """
+    value, dvalue, batched = _jvp("fenrir_grid_jvp", key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data,
+                                  obs_times, obs_weight, obs_var, tangents, kalman_type, params)
+    return (value, dvalue) if batched else (float(value[0]), dvalue[0])
+
+
+def fenrir_grid_grad(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
+                     obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", wrt=("theta",), init_jac=None, **params):
+    """
+    ``fenrir_grid`` and its gradient (an addition): ``FenrirGrad(value, grad)`` with ``grad`` a dict name -> (size,), or (B, size)
+    for batched inputs, for every name in ``wrt`` -- names of ``params`` and / or ``"ode_init"``, whose gradient has shape (d, p) or
+    (B, d, p).  This is ``fenrir_grid_jvp`` with the unit directions; the direction count is the sum of the sizes.  ``wrt`` and
+    ``init_jac`` are ``dalton_grid_grad``'s: ``init_jac`` is a dict name -> d ode_init / d param, shape (d, p, size) or (B, d, p, size),
+    added into that parameter's ``ode_init`` direction, so that the returned gradient is the total derivative for an initial state
+    built from the parameters (the quick start's ``init(v0, t, theta)``).  Served, refused and the 1e-8 rule as ``fenrir_grid_jvp``;
+    ValueError as well for a name in ``init_jac`` that is no parameter in ``wrt`` and for a Jacobian of the wrong shape.
+    """
+    from .dalton import _grad_config, _unit_directions
+    who = "fenrir_grid_grad"
+    _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight, (wrt,) if isinstance(wrt, str) else tuple(wrt), params,
+                 sibling="fenrir_grid")
+    tangents, layout = _unit_directions(who, ode_fun, ode_weight, ode_init, wrt, init_jac, params)
+    if not tangents:
+        raise ValueError(f"{who}: wrt is empty (K = 0)")
+    value, dvalue, batched = _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times,
+                                  obs_weight, obs_var, tangents, kalman_type, params)
+    grad = {}
+    for name, k0, shape in layout:
+        gr = dvalue[:, k0:k0 + int(np.prod(shape))].reshape((-1,) + shape)
+        grad[name] = gr if batched else gr[0]
+    return FenrirGrad(value if batched else float(value[0]), grad)
+
+
+def fenrir_grad(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
+                obs_data, obs_times, obs_weight, obs_var, kalman_type="standard", wrt=("theta",), init_jac=None, **params):
+    """
+    ``fenrir`` and its gradient on the uniform grid (an addition): ``fenrir_grid_grad`` on ``np.linspace(t_min, t_max, n_steps + 1)``
+    with ``prior_at = lambda dt: prior_pars``; the observation times are mapped to nodes by ``fenrir``'s own rule (``obs_index``: the
+    next grid index, which must not decrease; a last time past t_max is conditioned on at node n_steps, as ``fenrir`` does).  Here
+    the nodes must not repeat (ValueError): ``fenrir_grid`` has one observation per node.  The first thirteen arguments are
+    ``fenrir``'s, ``wrt`` and ``init_jac`` ``fenrir_grid_grad``'s; returns ``FenrirGrad(value, grad)``.
+
+    The value agrees with ``fenrir``'s to the cross-route bar (1e-7 of max(1, |value|)), NOT bit for bit: the time of node n is
+    the table's ``linspace`` entry here and ``t_min + (t_max - t_min) (n + 1) / n_steps`` there, which may differ by an ulp, and
+    ``fenrir`` may run on the tiles or on stored predictions where this call re-evaluates them.  Served, refused and the 1e-8 rule
+    as ``fenrir_grid_jvp``.
+    """
+    from .dalton import _grad_config
+    _grad_config("fenrir_grad", ode_fun, ode_weight, interrogate, kalman_type, obs_weight, (wrt,) if isinstance(wrt, str) else tuple(wrt),
+                 params, sibling="fenrir_grid")
+    obs, D, Om, _ = _check_obs(obs_data, obs_weight, obs_var)
+    ind = obs_index(t_min, t_max, n_steps, obs_times)               # fenrir.py:118-120
+    if np.any(np.diff(ind) < 0):
+        raise ValueError("obs_times must be ascending")
+    ind = np.minimum(ind, int(n_steps))                             # fenrir_bwd_kernel: an index past n_steps is node n_steps
+    if np.any(np.diff(ind) == 0):
+        raise ValueError("fenrir_grad: the observations' grid indices must be strictly increasing (one observation per grid "
+                         "point)")
+    t = np.linspace(float(t_min), float(t_max), int(n_steps) + 1)
+    return fenrir_grid_grad(key, ode_fun, ode_weight, ode_init, t, interrogate, lambda dt: prior_pars, obs, t[ind], D, Om,
+                            kalman_type=kalman_type, wrt=wrt, init_jac=init_jac, **params)
 
 
 def solve_mv(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,

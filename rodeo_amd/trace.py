@@ -209,7 +209,8 @@ _grad_cache = {}
 
 def grad_from_python(fun, n_vars, n_deriv_used=2, name=None, **param_sizes):
     """``DeviceODE`` of the gradient kind from an ordinary Python right-hand side (``from_python``'s arguments): registered as
-    ``AutoJacG<struct>``, it serves ``dalton_grid_jvp`` / ``dalton_grid_grad`` / ``dalton_grad`` and nothing else."""
+    ``AutoJacG<struct>``, it serves the gradient calls -- ``dalton_grid_jvp`` / ``dalton_grid_grad`` / ``dalton_grad`` and
+    ``fenrir_grid_jvp`` / ``fenrir_grid_grad`` / ``fenrir_grad`` -- and nothing else."""
     from . import ode
     spec = tuple((k, int(v)) for k, v in param_sizes.items())
     key = (fun, int(n_vars), int(n_deriv_used), spec)
