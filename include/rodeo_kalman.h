@@ -701,6 +701,24 @@ int rk_fd_grad_hess(rk_handle h, int32_t n_centre, int32_t k, const double* vals
 int rk_newton_step(rk_handle h, int32_t n_centre, int32_t k, const double* grad, const double* hess, const double* damping,
                    double* delta, double* logdet, int32_t* ok);
 
+/* The gradient mode of the same driver (laplace_grad): the caller supplies value AND exact gradient of the log-posterior,
+ * the Hessian is a first central difference of gradients.  S' = 2 k + 1 points per centre: the leading S' points of
+ * rk_fd_stencil (u, then u + h_i e_i, u - h_i e_i), in its order and with its arithmetic, so the rows are its rows bit for
+ * bit.  Refusals as above (n_centre < 1 or k < 1: RK_ERR_INVALID; k > 12: RK_ERR_UNSUPPORTED).
+ * rk_fd_grad_stencil writes the points: u (C, k), step (k) -> out (C, S', k).
+ * rk_fd_hess_from_grad: vals (C, S'), grads (C, S', k) with G[s] the gradient at point s ->
+ *     grad (C, k)     = G[0]
+ *     hess (C, k, k):   diagonal (G[1+2i][i] - G[2+2i][i]) / (2 h_i); off the diagonal, a = min(i, j), b = max(i, j),
+ *                       0.5 ((G[1+2a][b] - G[2+2a][b]) / (2 h_a) + (G[1+2b][a] - G[2+2b][a]) / (2 h_b)),
+ *                       both triangles from the same expression
+ *     grad_fd (C, k)  = (vals[1+2i] - vals[2+2i]) / (2 h_i), the difference quotient the driver checks G[0] against
+ *     n_bad (C)       the count of non-finite entries of vals and grads of the centre; where it is not 0 the centre's
+ *                     grad, hess and grad_fd are NaN.
+ * One fixed expression per entry (no atomics): identical bits from call to call.  Latency-bound, not tuned.          */
+int rk_fd_grad_stencil(rk_handle h, int32_t n_centre, int32_t k, const double* u, const double* step, double* out);
+int rk_fd_hess_from_grad(rk_handle h, int32_t n_centre, int32_t k, const double* vals, const double* grads,
+                         const double* step, double* grad, double* hess, double* grad_fd, int32_t* n_bad);
+
 /* ---- per-step operator boundary -------------------------------------------------------------------------
  * Batched versions of the nine functions of src/rodeo/kalmantv/standard.py (kalman_type = RK_KALMAN_STANDARD)
  * and src/rodeo/kalmantv/square_root.py (RK_KALMAN_SQRT).  n = batch size (the reference's vmap axis);

@@ -165,6 +165,8 @@ SIGNATURES = {
     "rk_fd_stencil": (C.c_int, [_H, _I, _I, _P, _P, _P]),
     "rk_fd_grad_hess": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P]),
     "rk_newton_step": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "rk_fd_grad_stencil": (C.c_int, [_H, _I, _I, _P, _P, _P]),
+    "rk_fd_hess_from_grad": (C.c_int, [_H, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "rk_kalman_predict_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 7),
     "rk_kalman_update_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 8),
     "rk_kalman_filter_batched": (C.c_int, [_H, C.POINTER(OpCfg)] + [_P] * 13),

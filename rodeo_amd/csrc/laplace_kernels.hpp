@@ -137,4 +137,71 @@ __global__ void __launch_bounds__(64) newton_step_kernel(const double* __restric
     ok_out[c] = ok ? 1 : 0;
 }
 
+// ---- gradient mode (laplace_grad): the user supplies the exact gradient, the Hessian is a first difference of gradients ----
+//
+// The stencil is the leading 2 k + 1 points of the one above -- s = 0: u;  s = 1 + 2 i, 2 + 2 i: u + h_i e_i, u - h_i e_i --
+// in fd_stencil_kernel's order and with its arithmetic (v = u_d, then v += (+-1.0) * h_d where d == i), so the rows equal the
+// first 2 k + 1 rows of fd_stencil_kernel's output bit for bit (tests/laplace_grad_oracle.py restates both kernels).
+// One lane per element of out (C, 2 k + 1, k).
+__global__ void __launch_bounds__(256) fd_grad_stencil_kernel(const double* __restrict__ u, const double* __restrict__ step,
+                                                              int C, int k, double* __restrict__ out) {
+    const int S = 2 * k + 1;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)C * S * k) return;
+    const int d = (int)(e % k);
+    const int s = (int)((e / k) % S);
+    const int c = (int)(e / ((long long)k * S));
+    int i = -1;
+    double si = 0.0;
+    if (s >= 1) {
+        i = (s - 1) >> 1;
+        si = ((s - 1) & 1) ? -1.0 : 1.0;
+    }
+    double v = u[(size_t)c * k + d];
+    if (d == i) v += si * step[d];
+    out[e] = v;
+}
+
+// vals (C, 2 k + 1), grads (C, 2 k + 1, k): value and gradient of the log-posterior at the points above.  One workgroup per
+// centre, one lane per Hessian entry (i, j); the lanes of the diagonal also write grad (the user's gradient at the centre)
+// and grad_fd (the central difference quotient of the values, what the driver checks the user's gradient against).  With
+// G[s][.] the gradient at point s and a = min(i, j), b = max(i, j):
+//     hess[i][i] = (G[1+2i][i] - G[2+2i][i]) / (2.0 h_i)
+//     hess[i][j] = 0.5 ((G[1+2a][b] - G[2+2a][b]) / (2.0 h_a) + (G[1+2b][a] - G[2+2b][a]) / (2.0 h_b))
+// the mean of the two one-sided estimates of d^2 f / du_a du_b.  Every entry is one fixed expression that the lanes (i, j) and
+// (j, i) evaluate alike (no sums across lanes, no atomics): symmetric, and the same bits from call to call.  The count of
+// non-finite entries of vals and grads is an integer reduction over the workgroup; where it is not 0 the centre's outputs
+// are NaN.
+__global__ void __launch_bounds__(256) fd_hess_from_grad_kernel(const double* __restrict__ vals, const double* __restrict__ grads,
+                                                                const double* __restrict__ step, int k,
+                                                                double* __restrict__ grad, double* __restrict__ hess,
+                                                                double* __restrict__ grad_fd, int* __restrict__ n_bad) {
+    const int S = 2 * k + 1;
+    const int n = S * (k + 1);                      // S values, then S k gradient entries
+    const int c = blockIdx.x, t = threadIdx.x;
+    const double* f = vals + (size_t)c * S;
+    const double* G = grads + (size_t)c * S * k;
+    int bad = 0;
+    for (int e0 = 0; e0 < n; e0 += 256) {           // the trip count is the same in every lane
+        const int e = e0 + t;
+        const double v = e < S ? f[e] : G[e < n ? e - S : 0];
+        bad += __syncthreads_count(e < n && !isfinite(v));
+    }
+    if (t == 0) n_bad[c] = bad;
+    if (t >= k * k) return;
+    const int i = t / k, j = t % k;
+    const double nan = __builtin_nan("");
+    if (i == j) {
+        const double h = step[i];
+        hess[((size_t)c * k + i) * k + i] = bad ? nan : (G[(1 + 2 * i) * k + i] - G[(2 + 2 * i) * k + i]) / (2.0 * h);
+        grad[(size_t)c * k + i] = bad ? nan : G[i];
+        grad_fd[(size_t)c * k + i] = bad ? nan : (f[1 + 2 * i] - f[2 + 2 * i]) / (2.0 * h);
+    } else {
+        const int a = i < j ? i : j, b = i < j ? j : i;
+        const double da = (G[(1 + 2 * a) * k + b] - G[(2 + 2 * a) * k + b]) / (2.0 * step[a]);
+        const double db = (G[(1 + 2 * b) * k + a] - G[(2 + 2 * b) * k + a]) / (2.0 * step[b]);
+        hess[((size_t)c * k + i) * k + j] = bad ? nan : 0.5 * (da + db);
+    }
+}
+
 }  // namespace rk

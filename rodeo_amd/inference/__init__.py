@@ -10,7 +10,7 @@ holds ``solve_mv`` / ``solve_sim``).  ``magi_logdens``: the MAGI log-density (sr
 ``rodeo_amd.inference.dalton`` and are imported from there (``from rodeo_amd.inference.dalton import daltonng``); they are not
 re-exported here.  ``laplace``: mode, Hessian and normal approximation of a batched log-posterior by central
 differences on the device (docs/examples/parameter.md:239-275; ``rodeo_amd.inference.laplace`` is the module, its function
-is ``laplace.laplace``).
+is ``laplace.laplace``; ``laplace.laplace_grad`` is the same fit on the exact gradients of ``fenrir_grad`` / ``dalton_grad``).
 """
 from .basic import basic
 from .logpost import gauss_obs_logpost, obs_index, sim_logpost, stage_upars
