@@ -508,6 +508,31 @@ int rk_fenrir_grid_jvp(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* 
  * with the compiler's log otherwise.                                                                                        */
 int rk_fenrir_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate);
 
+/* The hyper forms of the two (an addition): rk_dalton_grid_jvp / rk_fenrir_grid_jvp with two more directions per block, the argument
+ * lists of those entries followed by dlog_sigma, dlog_sigma_batched, dlog_obs_var, dlog_obs_var_batched (rk_fenrir_grid_jvp_hyper:
+ * in front of workspace).  dlog_sigma (n_dir, n_block), or (n_dir, n_block, n_traj) batch-minor with its flag: entry b is the rate
+ * of log sigma_b, the prior scale of block b, under the scale law r_b ~ sigma_b^2 with q free of sigma -- every step's own r as
+ * loaded gets the tangent 2 rate r, q none, and the initial variance is not scaled.  dlog_obs_var likewise: entry b is the rate of
+ * a common log-scale of block b's observation variances, obs_var. = rate obs_var at every observation, node 0 and node n_steps
+ * included.  A NULL array is a zero direction; with both NULL the result has rk_dalton_grid_jvp's / rk_fenrir_grid_jvp's bits.
+ * Kernels of their own (dalton_grid_jvp_hyper_kernel; fenrir_grid_jvp_fwd_hyper_kernel, fenrir_grid_jvp_bwd_hyper_kernel), the
+ * plain entries launch what they launched; the workspace is rk_fenrir_grid_jvp_workspace_bytes'.  Served and refused as the plain
+ * entries, on cfg, n_bobs and n_dir alone; an instance whose hyper kernel would need more scratch than its yardstick is
+ * RK_ERR_UNSUPPORTED ("not built").  The two compile checks build the hiprtc kinds (JIT_DALTON_GRAD_HYPER, JIT_FENRIR_GRAD_HYPER)
+ * without a device, as the plain ones do.                                                                                    */
+int rk_dalton_grid_jvp_hyper(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const double* obs, const double* obs_weight,
+                             const double* obs_var, const int32_t* obs_ind, int32_t n_obs, int32_t n_bobs, const rk_grid_in* g,
+                             int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit, int32_t dinit_batched,
+                             const double* dlog_sigma, int32_t dlog_sigma_batched, const double* dlog_obs_var,
+                             int32_t dlog_obs_var_batched, double* value, double* dvalue);
+int rk_fenrir_grid_jvp_hyper(rk_handle h, const rk_solve_cfg* cfg, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
+                             const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
+                             const rk_grid_in* g, int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit,
+                             int32_t dinit_batched, const double* dlog_sigma, int32_t dlog_sigma_batched, const double* dlog_obs_var,
+                             int32_t dlog_obs_var_batched, void* workspace, double* value, double* dvalue);
+int rk_dalton_grad_hyper_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate);
+int rk_fenrir_grad_hyper_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate);
+
 /* solve_sim_draws (an addition): n_draws sample paths per trajectory from one forward filter.  Runs the forward pass of
  * rk_solve_filter (cfg must carry RK_FLAG_BATCH_MINOR; out->mean_state / var_state hold the filtered moments afterwards), then
  * one backward kernel, one lane per (chunk of draws, block, trajectory), which does the work that no draw changes -- the

@@ -157,6 +157,12 @@ SIGNATURES = {
     "rk_fenrir_grid_jvp_workspace_bytes": (C.c_int, [_P, _I, C.POINTER(C.c_size_t)]),
     "rk_fenrir_grid_jvp": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _I, _P, _I, _P, _I, _P, _P, _P]),
     "rk_fenrir_grad_compile_check": (C.c_int, [_I, _I, _I]),
+    "rk_dalton_grid_jvp_hyper": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _I, _P, _I, _P, _I, _P, _I, _P, _I,
+                                           _P, _P]),
+    "rk_fenrir_grid_jvp_hyper": (C.c_int, [_H, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(GridIn), _I, _P, _I, _P, _I, _P, _I, _P,
+                                           _I, _P, _P, _P]),
+    "rk_dalton_grad_hyper_compile_check": (C.c_int, [_I, _I, _I]),
+    "rk_fenrir_grad_hyper_compile_check": (C.c_int, [_I, _I, _I]),
     "rk_solve_sim_draws":(C.c_int, [_H, _P, _P, _P, _I, _P, _I, _P]),
     "rk_sim_draws_chunk": (C.c_int, []),
     "rk_solve_sim_draws_grid": (C.c_int, [_H, _P, _P, _P, C.POINTER(GridIn), _I, _P, _I, _P]),

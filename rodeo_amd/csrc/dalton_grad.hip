@@ -2,7 +2,8 @@
 // directional derivatives of rk_dalton_grid_loglik's value with respect to the ODE parameters and the initial state.  One
 // route: dalton_grid_jvp_kernel (dalton_grad_kernels.hpp), one (trajectory, direction) item per lane pair, 32 items per wave.
 // Standard form, n_bmeas = 1, n_bobs = 1, built-in FitzHugh-Nagumo and Lorenz63, or a user right-hand side of the gradient kind
-// (hiprtc, rhs_jit.hip's JIT_DALTON_GRAD).  No workspace.  The sizes test, the grid's staging (through dalton_grid_inputs) and
+// (hiprtc, rhs_jit.hip's JIT_DALTON_GRAD).  rk_dalton_grid_jvp_hyper (section 7 (25)) is the same entry with the log sigma / log
+// observation variance directions, on dalton_grid_jvp_hyper_kernel (JIT_DALTON_GRAD_HYPER).  No workspace.  The sizes test, the grid's staging (through dalton_grid_inputs) and
 // the launch patterns are grid_entry.hpp's; the rest of the configuration check is worded for this entry alone ("not built: ...").
 #include "common.hpp"
 #include "rhs.hpp"
@@ -62,13 +63,27 @@ static int dalton_grad_check(const rk_solve_cfg* c, int n_bobs, int n_dir) {
     return RK_OK;
 }
 
+// `hy`: null for rk_dalton_grid_jvp, the hyper directions for rk_dalton_grid_jvp_hyper (dalton_grid_jvp_hyper_kernel)
+// The hyper form's instances (dalton_grid_jvp_hyper_kernel) ship by the rule above with dalton_grid_jvp_kernel
+// <RHS, P, ITG> as the yardstick.  All twelve pass without scratch (profiles/hyper_grad_code_objects.txt; Lorenz63 at 3 with rodeo
+// takes the last of the 512 registers), so rk_dalton_grid_jvp_hyper serves what rk_dalton_grid_jvp serves.
 static int dalton_grid_jvp_launch(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
-                                  const JvpDirs& dir, double* value, double* dvalue) {
-    return launch_by_rhs(c, a, [&] { return user_dalton_grad(h, c, a, o, ga, dir, a.B * dir.K, value, dvalue); }, [&](auto rhs) {
+                                  const JvpDirs& dir, const JvpHyper* hy, double* value, double* dvalue) {
+    const auto user = [&] {
+        return hy ? user_dalton_grad_hyper(h, c, a, o, ga, dir, *hy, a.B * dir.K, value, dvalue)
+                  : user_dalton_grad(h, c, a, o, ga, dir, a.B * dir.K, value, dvalue);
+    };
+    return launch_by_rhs(c, a, user, [&](auto rhs) {
         using RHS = decltype(rhs);
         if constexpr (dalton_grad_has_rhs<RHS>()) {
             const LaunchGeom g = dalton_lane_geom(a.B * dir.K, true);       // 32 (trajectory, direction) items per wave
             // (one writer per element: nothing to clear)
+            if (hy)
+                return launch_fwd_instance<2, 3, RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
+                    h, c, "dalton_grid_jvp_hyper_kernel", "dalton_grid_jvp_hyper", [&](auto P, auto I) {
+                        hipLaunchKernelGGL((dalton_grid_jvp_hyper_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, o, ga, dir, *hy,
+                                           value, dvalue);
+                    });
             return launch_fwd_instance<2, dalton_grad_pmax<RHS>(), RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
                 h, c, "dalton_grid_jvp_kernel", "dalton_grid_jvp", [&](auto P, auto I) {
                     hipLaunchKernelGGL((dalton_grid_jvp_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, o, ga, dir, value, dvalue);
@@ -102,7 +117,29 @@ int rk_dalton_grid_jvp(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
     SolveArgs a;
     make_args(c, in, nullptr, a);
     const JvpDirs dir{dtheta, dinit, dtheta_batched != 0, dinit_batched != 0, n_dir};
-    return dalton_grid_jvp_launch(h, c, a, o, ga, dir, value, dvalue);
+    return dalton_grid_jvp_launch(h, c, a, o, ga, dir, nullptr, value, dvalue);
+}
+
+int rk_dalton_grid_jvp_hyper(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const double* obs, const double* obs_weight,
+                             const double* obs_var, const int32_t* obs_ind, int32_t n_obs, int32_t n_bobs, const rk_grid_in* g,
+                             int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit, int32_t dinit_batched,
+                             const double* dlog_sigma, int32_t dlog_sigma_batched, const double* dlog_obs_var,
+                             int32_t dlog_obs_var_batched, double* value, double* dvalue) {
+    RK_REQUIRE(c, RK_ERR_INVALID, "rk_dalton_grid_jvp_hyper: null cfg");
+    int rc = dalton_grad_check(c, n_bobs, n_dir);                   // (the configuration alone, before anything else is looked at)
+    if (rc) return rc;
+    RK_REQUIRE(h && g && value && dvalue, RK_ERR_INVALID, "rk_dalton_grid_jvp_hyper: null argument");
+    DaltonObs o;
+    GridArgs ga;
+    rc = dalton_grid_inputs("rk_dalton_grid_jvp_hyper", c, in, obs, obs_weight, obs_var, obs_ind, n_obs, g, o, ga);
+    if (rc) return rc;
+    rc = begin_solve(h);
+    if (rc) return rc;
+    SolveArgs a;
+    make_args(c, in, nullptr, a);
+    const JvpDirs dir{dtheta, dinit, dtheta_batched != 0, dinit_batched != 0, n_dir};
+    const JvpHyper hy{dlog_sigma, dlog_obs_var, dlog_sigma_batched != 0, dlog_obs_var_batched != 0};
+    return dalton_grid_jvp_launch(h, c, a, o, ga, dir, &hy, value, dvalue);
 }
 
 }  // extern "C"

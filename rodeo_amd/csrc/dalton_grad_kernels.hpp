@@ -16,6 +16,13 @@
 //   y update       the same with the constant row D and the variance Omega (n_bobs = 1)
 //   node 0         log N(y_0; D_0 x_0, Omega_0) differentiated in x_0; nothing is updated
 // The marginal filter is the same recursion without y; dvalue = d(joint) - d(marginal).
+//
+// The hyper form (dalton_grid_jvp_hyper_kernel) adds two directions per block: l. = the rate of
+// log sigma_b, under the scale law R_b ~ sigma_b^2 with Q free of it, and w. = the rate of a common log-scale of block b's
+// observation variances:
+//   predict        Sigma.- = Q Sigma. Q^T + 2 l. R     (the step's own R as it is loaded; the initial variance is not scaled)
+//   y update       Omega. = w. Omega                    (node 0 included: -1/2 w. + 1/2 innov^2 w. / Omega)
+// It is a sibling kernel on the same device functions, not a flag of dalton_grid_jvp_kernel, whose code stays what it was.
 #pragma once
 #include "rk_enums.hpp"
 #include "kalman_small.hpp"
@@ -54,6 +61,28 @@ struct JvpDirs {
     int dtheta_b, dinit_b;
     int K;
 };
+
+// the hyper directions of rk_dalton_grid_jvp_hyper / rk_fenrir_grid_jvp_hyper, batch-minor like dtheta: dlog_sigma and dlog_obs_var
+// (K, D[, B]); null: zero directions.  A struct of its own, for the hyper kernels only: JvpDirs travels by value into the others.
+struct JvpHyper {
+    const double *dlsig, *dlobs;
+    int dlsig_b, dlobs_b;
+};
+
+// one rate of direction k, block blk, trajectory b, from dlsig or dlobs
+__device__ __forceinline__ double hyper_rate(const double* v, int batched, int D, int k, int blk, int B, int b) {
+    return v ? ld(v, (size_t)k * D + blk, batched, B, b) : 0.0;
+}
+
+// Sigma.- += 2 l. R: the prior scale's share of the predicted variance's tangent
+template <int P>
+__device__ __forceinline__ void jvp_predict_scale(const double (&R)[P][P], double dlsig, double (&dSp)[P][P]) {
+    const double r2 = 2.0 * dlsig;
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+#pragma unroll
+        for (int j = 0; j < P; ++j) dSp[i][j] = fma(r2, R[i][j], dSp[i][j]);
+}
 
 // mu.- = Q mu. ;  Sigma.- = (Q Sigma.) Q^T
 template <int P>
@@ -186,6 +215,24 @@ __device__ __forceinline__ void jvp_observe(const DaltonObs& o, size_t ib, const
     }
 }
 
+// The same where the variance has the tangent Omega. = rate Omega (the hyper kernels).  Its own few lines: with jvp_observe written
+// as the rate-0 case of this one, the compiler orders that function's loads differently, and dalton_grid_jvp_kernel's code with them.
+template <int P>
+__device__ __forceinline__ void jvp_observe_rate(const DaltonObs& o, size_t ib, double rate, const double (&m)[P],
+                                                 const double (&S)[P][P], double (&dm)[P], double (&dS)[P][P], double& dacc) {
+    double Drow[P], dm2[P], dS2[P][P];
+#pragma unroll
+    for (int k = 0; k < P; ++k) Drow[k] = o.obs_w[ib * P + k];
+    const double V = o.obs_v[ib];
+    jvp_update<P, false>(Drow, Drow, -o.obs[ib], 0.0, V, rate * V, m, S, dm, dS, dm2, dS2, dacc);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        dm[i] = dm2[i];
+#pragma unroll
+        for (int j = 0; j < P; ++j) dS[i][j] = dS2[i][j];
+    }
+}
+
 // Work item = (trajectory b, direction k), B K items; a wave holds 32: lanes 0..31 run the items' joint filters, lanes 32..63
 // their marginal filters (dalton_grid_fwd_kernel's halves).  A lane recomputes its trajectory's primal filter and carries one
 // tangent.  dvalue[b K + k] = d(joint) - d(marginal) and, from the k = 0 item, value[b] = joint - marginal leave through one
@@ -273,6 +320,105 @@ __global__ void __launch_bounds__(64) dalton_grid_jvp_kernel(SolveArgs a, Dalton
                 ++i;
                 obs_node = i < o.n_obs ? o.obs_ind[i] : -1;
                 asm volatile("" : "+v"(obs_node));                          // (dalton_grid_fwd_kernel: waited for on the rare path)
+            }
+        });
+    }
+    const double marg = __shfl_down(acc, 32, 64), dmarg = __shfl_down(dacc, 32, 64);     // lane l < 32 reads lane l + 32
+    if (joint && live) {
+        dvalue[lane_item] = dacc - dmarg;
+        if (k == 0) value[b] = acc - marg;
+    }
+}
+
+// The hyper form: dalton_grid_jvp_kernel's items, lanes, walk and exits, with the rates l.[D] of log sigma and w.[D] of the
+// observation variances' log-scale of the item's direction in registers (2 D doubles): jvp_predict_scale after every
+// jvp_predict_block, in both filters, and jvp_observe_rate where that kernel has jvp_observe.
+template <class RHS, int P, int ITG>
+__global__ void __launch_bounds__(64) dalton_grid_jvp_hyper_kernel(SolveArgs a, DaltonObs o, GridArgs g, JvpDirs dir, JvpHyper hy,
+                                                                   double* __restrict__ value, double* __restrict__ dvalue) {
+    constexpr int D = RHS::D, NT = RHS::NTHETA;
+    const int lane = threadIdx.x;
+    const bool joint = lane < 32;
+    const long long n_items = (long long)a.B * dir.K;
+    const long long lane_item = (long long)blockIdx.x * 32 + (lane & 31);
+    const bool live = lane_item < n_items;
+    const long long item = live ? lane_item : n_items - 1;                  // (a lane past B K reads an item that exists)
+    const int b = (int)(item / dir.K), k = (int)(item % dir.K);
+    double acc = 0.0, dacc = 0.0;
+    if (live || grid_walk_needs_helpers<RHS, P>(g)) {
+        double W[D][P], th[NT], dth[NT], mu[D][P], S[D][P][P], dmu[D][P], dS[D][P][P], dls[D], dlo[D];
+        {
+            double Q0[D][P][P], R0[D][P][P];
+            lane_load_model<RHS, P>(a, b, Q0, R0, W, th);                   // W and theta: the plan's own pair is not read
+        }
+        lane_load_init<D, P>(a, b, mu, S);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) dth[j] = dir.dtheta ? ld(dir.dtheta, (size_t)k * NT + j, dir.dtheta_b, a.B, b) : 0.0;
+#pragma unroll
+        for (int blk = 0; blk < D; ++blk) {
+            dls[blk] = hyper_rate(hy.dlsig, hy.dlsig_b, D, k, blk, a.B, b);
+            dlo[blk] = hyper_rate(hy.dlobs, hy.dlobs_b, D, k, blk, a.B, b);
+#pragma unroll
+            for (int r = 0; r < P; ++r) {
+                dmu[blk][r] = dir.dinit ? ld(dir.dinit, ((size_t)k * D + blk) * P + r, dir.dinit_b, a.B, b) : 0.0;
+#pragma unroll
+                for (int c = 0; c < P; ++c) dS[blk][r][c] = 0.0;
+            }
+        }
+        // node 0: log p(y_0 | x_0) with Omega. = w. Omega; nothing is updated
+        int i = 0;
+        if (o.n_obs > 0 && o.obs_ind[0] == 0) {
+            if (joint) {
+#pragma unroll
+                for (int blk = 0; blk < D; ++blk) {
+                    double m0[P], S0[P][P], dm0[P], dS0[P][P];
+#pragma unroll
+                    for (int r = 0; r < P; ++r) {
+                        m0[r] = mu[blk][r];
+                        dm0[r] = dmu[blk][r];
+#pragma unroll
+                        for (int c = 0; c < P; ++c) S0[r][c] = dS0[r][c] = 0.0;
+                    }
+                    jvp_observe_rate<P>(o, (size_t)blk, dlo[blk], m0, S0, dm0, dS0, dacc);
+                    dalton_observe<P, 1>(o, (size_t)blk, m0, S0, acc);
+                }
+            }
+            i = 1;
+        }
+        int obs_node = i < o.n_obs ? o.obs_ind[i] : -1;                     // node of observation i; -1: none left
+
+        const uint32_t traj = (uint32_t)(a.traj_offset + (uint64_t)b);
+        // (always_inline: the walk calls the step from more than one loop, and an outlined step would keep the state in scratch)
+        grid_walk<RHS, P>(a, g, b, live, [&](const double (&Q)[D][P][P], const double (&R)[D][P][P], double t, int n)
+                                             __attribute__((always_inline)) {
+            double mup[D][P], Sp[D][P][P], dmup[D][P], dSp[D][P][P];
+#pragma unroll
+            for (int blk = 0; blk < D; ++blk) {
+                predict_block<P>(Q[blk], R[blk], mu[blk], S[blk], mup[blk], Sp[blk]);
+                jvp_predict_block<P>(Q[blk], dmu[blk], dS[blk], dmup[blk], dSp[blk]);
+                jvp_predict_scale<P>(R[blk], dls[blk], dSp[blk]);
+            }
+            double wgt[D][P], am[D], V[D], dwgt[D][P], dam[D], dV[D];
+            interrogate_traj<RHS, P, ITG>(W, th, t, mup, Sp, a.seed, traj, (uint32_t)n, wgt, am, V);
+            jvp_interrogate<RHS, P, ITG>(W, th, dth, t, mup, dmup, dSp, wgt, dwgt, dam, dV);
+            const bool obs_here = obs_node == n + 1;                        // (the same in every lane of the wave)
+#pragma unroll
+            for (int blk = 0; blk < D; ++blk) {
+                double Wm[P];
+#pragma unroll
+                for (int j = 0; j < P; ++j) Wm[j] = W[blk][j] + wgt[blk][j];
+                jvp_update<P, ITG == RK_INTERROGATE_KRAMER>(Wm, dwgt[blk], am[blk], dam[blk], V[blk], dV[blk], mup[blk], Sp[blk],
+                                                            dmup[blk], dSp[blk], dmu[blk], dS[blk], dacc);
+                dalton_update_z<P>(Wm, am[blk], V[blk], mup[blk], Sp[blk], mu[blk], S[blk], acc);
+                if (obs_here && joint) {
+                    jvp_observe_rate<P>(o, (size_t)i * D + blk, dlo[blk], mu[blk], S[blk], dmu[blk], dS[blk], dacc);
+                    dalton_observe<P, 1>(o, (size_t)i * D + blk, mu[blk], S[blk], acc);
+                }
+            }
+            if (obs_here) {
+                ++i;
+                obs_node = i < o.n_obs ? o.obs_ind[i] : -1;
+                asm volatile("" : "+v"(obs_node));                          // (dalton_grid_jvp_kernel: waited for on the rare path)
             }
         });
     }

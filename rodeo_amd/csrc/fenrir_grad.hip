@@ -5,7 +5,8 @@
 // caller's workspace; then fenrir_grid_jvp_bwd_kernel (below), one lane per (block, item), the derivative of fenrir_grid's
 // backward Markov chain; with more than one block, magi_sum_kernel twice (launch_block_sum).  Standard form, n_bmeas = 1,
 // n_bobs = 1, built-in FitzHugh-Nagumo and Lorenz63, or a user right-hand side of the gradient kind (hiprtc, rhs_jit.hip's
-// JIT_FENRIR_GRAD, the forward kernel only: the backward kernel has no right-hand side).  The sizes test, the grid's staging,
+// JIT_FENRIR_GRAD, the forward kernel only: the backward kernel has no right-hand side).  rk_fenrir_grid_jvp_hyper (section 7 (25))
+// is the same entry with the log sigma / log observation variance directions, on the two hyper kernels.  The sizes test, the grid's staging,
 // the test of the output pointers and the launch patterns are grid_entry.hpp's; the rest of the configuration check is worded
 // for this entry alone ("not built: ...").
 #include "common.hpp"
@@ -155,6 +156,82 @@ __global__ void __launch_bounds__(64) fenrir_grid_jvp_bwd_kernel(SolveArgs a, Da
     if (k == 0) part[(size_t)blk * B + b] = acc;
 }
 
+// The hyper form, a sibling of the kernel above with its lanes, prefetch discipline and exits: the
+// lane keeps its block's two rates, l. of log sigma and w. of the observation variances' log-scale; the re-evaluated pred[n + 1]
+// has Sigma.- = Q Sigma._f Q^T + 2 l. R (jvp_predict_scale), and an observation has Omega. = w. Omega (jvp_observe_rate).
+template <int P>
+__global__ void __launch_bounds__(64) fenrir_grid_jvp_bwd_hyper_kernel(SolveArgs a, DaltonObs o, GridArgs g, int K, JvpHyper hy,
+                                                                       const double* __restrict__ dmean,
+                                                                       const double* __restrict__ dvar, double* __restrict__ part,
+                                                                       double* __restrict__ dpart) {
+    const long long n_items = (long long)a.B * K;
+    const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_items * a.D) return;
+    const int blk = (int)(l / n_items), item = (int)(l - (long long)blk * n_items);
+    const int b = item / K, k = item - b * K;
+    const size_t B = (size_t)a.B, BK = (size_t)n_items;
+    const double dls = hyper_rate(hy.dlsig, hy.dlsig_b, a.D, k, blk, a.B, b);
+    const double dlo = hyper_rate(hy.dlobs, hy.dlobs_b, a.D, k, blk, a.B, b);
+    double bm[P], bS[P][P], dbm[P], dbS[P][P];
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N, blk, b, bm, bS);       // terminal point (fenrir.py:186-188)
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(dmean, dvar, BK, a.D, a.N, blk, item, dbm, dbS);
+    double acc = 0.0, dacc = 0.0;
+    int i = o.n_obs - 1;
+    int obs_node = i >= 0 ? o.obs_ind[i] : -1;                              // node of observation i; -1: none left
+    auto observe = [&]() {
+        jvp_observe_rate<P>(o, (size_t)i * a.D + blk, dlo, bm, bS, dbm, dbS, dacc);           // (before the primal update of the carry)
+        fenrir_observe_scalar<P>(o, (size_t)i * a.D + blk, bm, bS, acc);
+        --i;
+        obs_node = i >= 0 ? o.obs_ind[i] : -1;
+        asm volatile("" : "+v"(obs_node));                                  // waited for here, on the rare path, not behind a prefetch
+    };
+    if (obs_node >= a.N) observe();                                         // fenrir.py:189-209
+
+    double mf[P], Sf[P][P], dmf[P], dSf[P][P], Q[P][P], R[P][P];
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, a.N - 1, blk, b, mf, Sf);
+    load_moments<P, RK_LAYOUT_BATCH_MINOR>(dmean, dvar, BK, a.D, a.N - 1, blk, item, dmf, dSf);
+    grid_load_pair<P>(g, a.B, a.D, grid_slot(g, a.N - 1), blk, b, Q, R);
+    int s_next = a.N >= 2 ? g.slot[a.N - 2] : 0;              // slot of step n - 1 as the table has it: clamped where it is used
+    // every load so far is complete before the loop is entered, so that no step waits for its own prefetch (grid_fwd_kernel)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    for (int n = a.N - 1; n >= 0; --n) {
+        const bool more = n >= 1;
+        double mfn[P], Sfn[P][P], dmfn[P], dSfn[P][P], Qn[P][P], Rn[P][P];
+        int s_after = 0;
+        if (more) {
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(a.mean, a.var, B, a.D, n - 1, blk, b, mfn, Sfn);
+            load_moments<P, RK_LAYOUT_BATCH_MINOR>(dmean, dvar, BK, a.D, n - 1, blk, item, dmfn, dSfn);
+            grid_load_pair<P>(g, a.B, a.D, grid_clamp(g, s_next), blk, b, Qn, Rn);
+            if (n >= 2) s_after = g.slot[n - 2];
+        }
+        double mp[P], Sp[P][P], dmp[P], dSp[P][P], G[P][P];
+        predict_block<P>(Q, R, mf, Sf, mp, Sp);                             // pred[n + 1] from filt[n] and the pair of step n
+        jvp_predict_block<P>(Q, dmf, dSf, dmp, dSp);
+        jvp_predict_scale<P>(R, dls, dSp);
+        jvp_markov_step<P>(Q, Sf, mp, Sp, dmf, dSf, dmp, dSp, bm, bS, dbm, dbS);              // (the carry is still step n + 1's)
+        fenrir_markov_step<P>(Q, mf, Sf, mp, Sp, bm, bS, G);
+        if (obs_node == n) observe();                                       // fenrir.py:155-170 (the same in every lane of the wave)
+        if (more) {
+            asm volatile("" : "+v"(s_after));                 // the fetched slot stays in a vector register until here (grid_fwd_kernel)
+            s_next = s_after;
+#pragma unroll
+            for (int r = 0; r < P; ++r) {
+                mf[r] = mfn[r];
+                dmf[r] = dmfn[r];
+#pragma unroll
+                for (int c = 0; c < P; ++c) {
+                    Sf[r][c] = Sfn[r][c];
+                    dSf[r][c] = dSfn[r][c];
+                    Q[r][c] = Qn[r][c];
+                    R[r][c] = Rn[r][c];
+                }
+            }
+        }
+    }
+    dpart[(size_t)blk * BK + item] = dacc;
+    if (k == 0) part[(size_t)blk * B + b] = acc;
+}
+
 // ---- dispatch ---------------------------------------------------------------------------------------------------
 // The rule an instance ships by: the forward kernel uses no more scratch than grid_fwd_kernel<RHS, P,
 // ITG>, the backward kernel no more than fenrir_grid_bwd_kernel<P, false, 1>.  profiles/fenrir_grad_code_objects.txt has every
@@ -191,18 +268,32 @@ static int fenrir_grad_check(const rk_solve_cfg* c, int n_bobs, int n_dir) {
     return RK_OK;
 }
 
+// The hyper kernels ship by the same rule with their non-hyper siblings as yardsticks.  All fourteen
+// pass without scratch (profiles/hyper_grad_code_objects.txt), so rk_fenrir_grid_jvp_hyper serves what rk_fenrir_grid_jvp serves.
+
 // bytes of the tangent records of n_dir directions: dmean (N+1, D, P, B n_dir) then dvar (N+1, D, P, P, B n_dir)
 static size_t fenrir_grad_ws_bytes(const rk_solve_cfg* c, int n_dir) {
     return sizeof(double) * (size_t)(c->n_steps + 1) * c->n_block * ((size_t)c->n_bstate + (size_t)c->n_bstate * c->n_bstate) *
            (size_t)c->n_traj * (size_t)n_dir;
 }
 
+// `hy`: null for rk_fenrir_grid_jvp, the hyper directions for rk_fenrir_grid_jvp_hyper (the hyper kernels)
 static int fenrir_grid_jvp_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga, const JvpDirs& dir,
-                                   double* dmean, double* dvar) {
-    return launch_by_rhs(c, a, [&] { return user_fenrir_grad(h, c, a, ga, dir, a.B * dir.K, dmean, dvar); }, [&](auto rhs) {
+                                   const JvpHyper* hy, double* dmean, double* dvar) {
+    const auto user = [&] {
+        return hy ? user_fenrir_grad_hyper(h, c, a, ga, dir, *hy, a.B * dir.K, dmean, dvar)
+                  : user_fenrir_grad(h, c, a, ga, dir, a.B * dir.K, dmean, dvar);
+    };
+    return launch_by_rhs(c, a, user, [&](auto rhs) {
         using RHS = decltype(rhs);
         if constexpr (fenrir_grad_has_rhs<RHS>()) {
             const LaunchGeom g = dalton_lane_geom(a.B * dir.K, false);      // 64 (trajectory, direction) items per wave
+            if (hy)
+                return launch_fwd_instance<FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX, RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
+                    h, c, "fenrir_grid_jvp_fwd_hyper_kernel", "fenrir_grid_jvp_hyper", [&](auto P, auto I) {
+                        hipLaunchKernelGGL((fenrir_grid_jvp_fwd_hyper_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga, dir, *hy,
+                                           dmean, dvar);
+                    });
             return launch_fwd_instance<FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX, RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(
                 h, c, "fenrir_grid_jvp_fwd_kernel", "fenrir_grid_jvp", [&](auto P, auto I) {
                     hipLaunchKernelGGL((fenrir_grid_jvp_fwd_kernel<RHS, P, I>), g.grid, g.block, 0, h->stream, a, ga, dir, dmean, dvar);
@@ -214,11 +305,15 @@ static int fenrir_grid_jvp_forward(rk_handle h, const rk_solve_cfg* c, const Sol
 }
 
 static int fenrir_grid_jvp_backward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& ga,
-                                    int K, const double* dmean, const double* dvar, double* part, double* dpart) {
+                                    int K, const JvpHyper* hy, const double* dmean, const double* dvar, double* part, double* dpart) {
     const LaunchGeom g = bwd_lane_geom(a.B * K, a.D);
-    LaunchTimer t(h, "fenrir_grid_jvp_bwd_kernel");
+    LaunchTimer t(h, hy ? "fenrir_grid_jvp_bwd_hyper_kernel" : "fenrir_grid_jvp_bwd_kernel");
     const bool ok = dispatch_int<FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX>(c->n_bstate, [&](auto P) {
-        hipLaunchKernelGGL((fenrir_grid_jvp_bwd_kernel<P>), g.grid, g.block, 0, h->stream, a, o, ga, K, dmean, dvar, part, dpart);
+        if (hy)
+            hipLaunchKernelGGL((fenrir_grid_jvp_bwd_hyper_kernel<P>), g.grid, g.block, 0, h->stream, a, o, ga, K, *hy, dmean, dvar, part,
+                               dpart);
+        else
+            hipLaunchKernelGGL((fenrir_grid_jvp_bwd_kernel<P>), g.grid, g.block, 0, h->stream, a, o, ga, K, dmean, dvar, part, dpart);
     });
     RK_REQUIRE(ok, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: no backward kernel for n_bstate %d", c->n_bstate);
     t.stop();
@@ -241,11 +336,12 @@ int rk_fenrir_grid_jvp_workspace_bytes(const rk_solve_cfg* c, int32_t n_dir, siz
     return RK_OK;
 }
 
-int rk_fenrir_grid_jvp(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
-                       const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
-                       const rk_grid_in* g, int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit,
-                       int32_t dinit_batched, void* workspace, double* value, double* dvalue) {
-    const char* who = "rk_fenrir_grid_jvp (fenrir_grid_jvp)";
+// the body of rk_fenrir_grid_jvp (hy null) and rk_fenrir_grid_jvp_hyper
+static int fenrir_grid_jvp_run(const char* who, rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out,
+                               const double* obs, const double* obs_weight, const double* obs_var, const int32_t* obs_node,
+                               int32_t n_obs, int32_t n_bobs, const rk_grid_in* g, const JvpDirs& dir, const JvpHyper* hy,
+                               void* workspace, double* value, double* dvalue) {
+    const int n_dir = dir.K;
     RK_REQUIRE(c, RK_ERR_INVALID, "%s: null cfg", who);
     int rc = fenrir_grad_check(c, n_bobs, n_dir);                   // (the configuration alone, before anything else is looked at)
     if (rc) return rc;
@@ -264,11 +360,10 @@ int rk_fenrir_grid_jvp(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
     SolveArgs a;
     make_args(c, in, out, a);
     const DaltonObs o{obs, obs_weight, obs_var, obs_node, n_obs};
-    const JvpDirs dir{dtheta, dinit, dtheta_batched != 0, dinit_batched != 0, n_dir};
     const size_t BK = (size_t)a.B * (size_t)n_dir;
     double* dmean = (double*)workspace;
     double* dvar = dmean + (size_t)(a.N + 1) * a.D * c->n_bstate * BK;
-    rc = fenrir_grid_jvp_forward(h, c, a, ga, dir, dmean, dvar);
+    rc = fenrir_grid_jvp_forward(h, c, a, ga, dir, hy, dmean, dvar);
     if (rc) return rc;
     double *part = value, *dpart = dvalue;                          // one block: the lanes write value / dvalue themselves
     if (a.D > 1) {
@@ -276,11 +371,31 @@ int rk_fenrir_grid_jvp(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in
         if (rc) return rc;
         dpart = part + (size_t)a.D * a.B;
     }
-    rc = fenrir_grid_jvp_backward(h, c, a, o, ga, n_dir, dmean, dvar, part, dpart);
+    rc = fenrir_grid_jvp_backward(h, c, a, o, ga, n_dir, hy, dmean, dvar, part, dpart);
     if (rc || a.D == 1) return rc;
     rc = launch_block_sum(h, part, a.B, a.D, value);                // block order, B and then B K sums: two calls give the same bits
     if (rc) return rc;
     return launch_block_sum(h, dpart, (int)BK, a.D, dvalue);
+}
+
+int rk_fenrir_grid_jvp(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
+                       const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
+                       const rk_grid_in* g, int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit,
+                       int32_t dinit_batched, void* workspace, double* value, double* dvalue) {
+    const JvpDirs dir{dtheta, dinit, dtheta_batched != 0, dinit_batched != 0, n_dir};
+    return fenrir_grid_jvp_run("rk_fenrir_grid_jvp (fenrir_grid_jvp)", h, c, in, out, obs, obs_weight, obs_var, obs_node, n_obs, n_bobs,
+                               g, dir, nullptr, workspace, value, dvalue);
+}
+
+int rk_fenrir_grid_jvp_hyper(rk_handle h, const rk_solve_cfg* c, const rk_solve_in* in, const rk_solve_out* out, const double* obs,
+                             const double* obs_weight, const double* obs_var, const int32_t* obs_node, int32_t n_obs, int32_t n_bobs,
+                             const rk_grid_in* g, int32_t n_dir, const double* dtheta, int32_t dtheta_batched, const double* dinit,
+                             int32_t dinit_batched, const double* dlog_sigma, int32_t dlog_sigma_batched, const double* dlog_obs_var,
+                             int32_t dlog_obs_var_batched, void* workspace, double* value, double* dvalue) {
+    const JvpDirs dir{dtheta, dinit, dtheta_batched != 0, dinit_batched != 0, n_dir};
+    const JvpHyper hy{dlog_sigma, dlog_obs_var, dlog_sigma_batched != 0, dlog_obs_var_batched != 0};
+    return fenrir_grid_jvp_run("rk_fenrir_grid_jvp_hyper (fenrir_grid_jvp)", h, c, in, out, obs, obs_weight, obs_var, obs_node, n_obs,
+                               n_bobs, g, dir, &hy, workspace, value, dvalue);
 }
 
 }  // extern "C"

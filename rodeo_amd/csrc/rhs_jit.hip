@@ -84,6 +84,8 @@ static const JitKindRow kJitKinds[JIT_N_KINDS] = {
     /* JIT_DALTONNG_GRID_BOTH */ {"rk::daltonng_grid_fwd_kernel<rk::UserRhsT, rk::UserObsT, {P}, {I}, {A}, true>", "daltonng_grid_kernels.hpp", "daltonng_grid_fwd_kernel<both>"},
     /* JIT_DALTON_GRAD        */ {"rk::dalton_grid_jvp_kernel<rk::UserRhsT, {P}, {I}>", "dalton_grad_kernels.hpp", "dalton_grid_jvp_kernel<user>"},
     /* JIT_FENRIR_GRAD        */ {"rk::fenrir_grid_jvp_fwd_kernel<rk::UserRhsT, {P}, {I}>", "fenrir_grad_kernels.hpp", "fenrir_grid_jvp_fwd_kernel<user>"},
+    /* JIT_DALTON_GRAD_HYPER  */ {"rk::dalton_grid_jvp_hyper_kernel<rk::UserRhsT, {P}, {I}>", "dalton_grad_kernels.hpp", "dalton_grid_jvp_hyper_kernel<user>"},
+    /* JIT_FENRIR_GRAD_HYPER  */ {"rk::fenrir_grid_jvp_fwd_hyper_kernel<rk::UserRhsT, {P}, {I}>", "fenrir_grad_kernels.hpp", "fenrir_grid_jvp_fwd_hyper_kernel<user>"},
 };
 
 // What one build depends on.  A field that the kind's name expression does not read stays 0 (obs: -1, no observation
@@ -589,6 +591,25 @@ int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, con
     return launch_jit(h, jit_key(JIT_FENRIR_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, false), params);
 }
 
+// the hyper forms: the same checks, the hyper kernels with their second struct of directions
+int user_dalton_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g,
+                           const JvpDirs& dir, const JvpHyper& hy, int n_items, double* value, double* dvalue) {
+    const int rc = user_dalton_grad_check(c);
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&o, (void*)&g, (void*)&dir, (void*)&hy, &value, &dvalue};
+    return launch_jit(h, jit_key(JIT_DALTON_GRAD_HYPER, c->rhs_id, c), dalton_lane_geom(n_items, true), params);
+}
+
+int user_fenrir_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir,
+                           const JvpHyper& hy, int n_items, double* dmean, double* dvar) {
+    const int rc = user_fenrir_grad_check(c);
+    if (rc) return rc;
+    SolveArgs args = a;
+    void* params[] = {&args, (void*)&g, (void*)&dir, (void*)&hy, &dmean, &dvar};
+    return launch_jit(h, jit_key(JIT_FENRIR_GRAD_HYPER, c->rhs_id, c), dalton_lane_geom(n_items, false), params);
+}
+
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm) {
     const int rc = user_rhs_check(c);
@@ -735,6 +756,29 @@ int rk_dalton_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t inter
     c.n_bstate = n_bstate;
     c.interrogate = interrogate;
     return jit_lookup(jit_key(JIT_DALTON_GRAD, rhs_id, &c), nullptr, nullptr);
+}
+
+// the same for the hyper forms (rk_dalton_grid_jvp_hyper / rk_fenrir_grid_jvp_hyper's forward kernel)
+int rk_dalton_grad_hyper_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
+    const UserRhs* u;
+    const int rc = user_rhs(rhs_id, &u);
+    if (rc) return rc;
+    rk_solve_cfg c{};
+    c.n_bstate = n_bstate;
+    c.interrogate = interrogate;
+    return jit_lookup(jit_key(JIT_DALTON_GRAD_HYPER, rhs_id, &c), nullptr, nullptr);
+}
+
+int rk_fenrir_grad_hyper_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
+    if (!builtin_rhs_type(rhs_id)) {
+        const UserRhs* u;
+        const int rc = user_rhs(rhs_id, &u);
+        if (rc) return rc;
+    }
+    rk_solve_cfg c{};
+    c.n_bstate = n_bstate;
+    c.interrogate = interrogate;
+    return jit_lookup(jit_key(JIT_FENRIR_GRAD_HYPER, rhs_id, &c), nullptr, nullptr);
 }
 
 // the same for fenrir_grid_jvp's forward kernel; a built-in id builds the kernel around that right-hand side, which shows without

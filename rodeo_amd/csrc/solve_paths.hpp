@@ -69,6 +69,8 @@ enum JitKind : int {
     JIT_DALTONNG_GRID_BOTH = 30,  // daltonng_grid_fwd_kernel<.., true> (daltonng_grid, the joint filter and the filter on Z alone)
     JIT_DALTON_GRAD = 31,     // dalton_grid_jvp_kernel (dalton_grid_jvp: value and directional derivatives; a gradient-kind source)
     JIT_FENRIR_GRAD = 32,     // fenrir_grid_jvp_fwd_kernel (fenrir_grid_jvp: the forward tangent filter; a gradient-kind source)
+    JIT_DALTON_GRAD_HYPER = 33,  // dalton_grid_jvp_hyper_kernel (the same with log sigma / log observation variance directions)
+    JIT_FENRIR_GRAD_HYPER = 34,  // fenrir_grid_jvp_fwd_hyper_kernel (the same with log sigma directions)
     JIT_N_KINDS
 };
 bool is_user_rhs(int rhs_id);
@@ -115,6 +117,7 @@ int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, con
 // dalton_grid_jvp: the configuration against the registration and the launch (dalton_grad.hip); the right-hand side must be of
 // the gradient kind (AutoJacG around a struct with rhs_generic: rodeo_amd.trace.trace_grad_source), else the build fails
 struct JvpDirs;
+struct JvpHyper;
 int user_dalton_grad_check(const rk_solve_cfg* c);
 int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, const JvpDirs& dir,
                      int n_items, double* value, double* dvalue);
@@ -122,6 +125,11 @@ int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, con
 int user_fenrir_grad_check(const rk_solve_cfg* c);
 int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir, int n_items,
                      double* dmean, double* dvar);
+// the hyper forms of the two (rk_dalton_grid_jvp_hyper / rk_fenrir_grid_jvp_hyper): the same checks, the hyper kernels
+int user_dalton_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g,
+                           const JvpDirs& dir, const JvpHyper& hy, int n_items, double* value, double* dvalue);
+int user_fenrir_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir,
+                           const JvpHyper& hy, int n_items, double* dmean, double* dvar);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them

@@ -10,7 +10,8 @@
   * ``dalton_grid`` / ``solve_mv_grid`` / ``solve_sim_grid``: the three on a non-uniform grid shared by the batch, every observation
     on a node (an addition, imported from this module like ``dalton_at``; ``rk_dalton_grid_loglik`` / ``rk_dalton_grid_solve``).
   * ``dalton_grid_jvp`` / ``dalton_grid_grad`` / ``dalton_grad``: ``dalton_grid``'s value with its derivatives in the ODE parameters
-    and the initial state, forward mode, on the device (an addition, imported from this module; ``rk_dalton_grid_jvp``).
+    and the initial state, forward mode, on the device (an addition, imported from this module; ``rk_dalton_grid_jvp``), and in
+    the two log-scales ``"log_sigma"`` / ``"log_obs_var"`` (``rk_dalton_grid_jvp_hyper``).
   * ``daltonng`` / ``solve_mv_nn`` for non-Gaussian observations (:547-1039) and ``daltonng_grid`` / ``solve_mv_nn_grid``, the two
     on that non-uniform grid (an addition; ``rk_daltonng_grid_loglik`` / ``rk_daltonng_grid_solve``); imported from this module.
 All of it runs on the device (``rk_dalton_loglik`` / ``rk_dalton_loglik_at`` / ``rk_dalton_solve``): both filters of every parameter set in one
@@ -229,6 +230,10 @@ _GRAD_STATE_MAX = 27                                                # n_block n_
 # arguments of the call that are no parameter of the ODE: a derivative with respect to one of them is not built
 _GRAD_NOT_WRT = ("sigma", "prior", "prior_pars", "prior_at", "ode_weight", "obs_data", "obs_weight", "obs_var", "obs_times",
                  "t_grid")
+# The two reserved direction names, shape (K, d) / (B, K, d): the rate of log sigma_b, the prior scale
+# of block b (every step's R_b gets 2 rate R_b, Q nothing, the initial variance nothing), and the rate of a common log-scale of
+# block b's observation variances.  A name in ``params`` wins over the reserved meaning.
+_GRAD_HYPER = ("log_sigma", "log_obs_var")
 
 
 def _grad_ode(who, ode_fun, W, params):
@@ -275,9 +280,45 @@ def _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight,
         if name in _GRAD_NOT_WRT and name not in params:
             raise NotImplementedError(f"{who}: not built: a derivative with respect to {name!r} (the ODE parameters and "
                                       "'ode_init' only)")
-        if name != "ode_init" and name not in params:
-            raise ValueError(f"{who}: {name!r} is no parameter of this call (known: {sorted(params) + ['ode_init']})")
+        if name != "ode_init" and name not in params and name not in _GRAD_HYPER:
+            raise ValueError(f"{who}: {name!r} is no parameter of this call (known: {sorted(params) + ['ode_init'] + list(_GRAD_HYPER)})")
     return ode
+
+
+def _split_hyper(tangents, params):
+    """``tangents`` as (the ODE parameters' and ode_init's, the reserved hyper names'): a name in ``params`` is a parameter."""
+    hyper = {name: v for name, v in tangents.items() if name in _GRAD_HYPER and name not in params}
+    return {name: v for name, v in tangents.items() if name not in hyper}, hyper
+
+
+def _stage_hyper(who, hyper, B, batched, d, K):
+    """The hyper directions checked and batch-minor: ``(K, dlog_sigma, its batched flag, dlog_obs_var, its batched flag)`` with an
+    array (K, d) or (K, d, B), None for a missing name.  ``K``: the count of the other directions, None when there is none."""
+    out = []
+    for name in _GRAD_HYPER:
+        if name not in hyper:
+            out += [None, 0]
+            continue
+        a = _direction(who, name, hyper[name], B, batched, (d,))
+        k = a.shape[a.ndim - 2]
+        if K is not None and k != K:
+            raise ValueError(f"{who}: the directions must agree in their count K, got {sorted({K, k})}")
+        K = k
+        if K == 0:
+            raise ValueError(f"{who}: no direction given (K = 0)")
+        out += [np.ascontiguousarray(a), 0] if a.ndim == 2 else [np.ascontiguousarray(np.moveaxis(a, 0, -1)), 1]
+    return (K,) + tuple(out)
+
+
+def _stage_all(who, ode, tangents, params, B, batched, d, p):
+    """``_stage_directions`` on the parameters' and ode_init's directions and ``_stage_hyper`` on the reserved names': ``(K, dtheta,
+    dtheta_batched, dinit, dinit_batched, hyper)`` with hyper None without a reserved name, else ``_stage_hyper``'s four."""
+    plain, hyper = _split_hyper(tangents, params)
+    if not hyper:
+        return _stage_directions(who, ode, plain, B, batched, d, p) + (None,)
+    staged = _stage_directions(who, ode, plain, B, batched, d, p) if plain else (None, None, 0, None, 0)
+    hy = _stage_hyper(who, hyper, B, batched, d, staged[0])
+    return (hy[0],) + staged[1:] + (hy[1:],)
 
 
 def _direction(who, name, v, B, batched, tail):
@@ -341,7 +382,7 @@ def _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
     sizes = _shape_rule(ode, ode_weight, ode_init, pairs[0], params)[-1]
     B, batched = (sizes[0], True) if sizes else (1, False)
     d, p = int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1])
-    K, dtheta, dtheta_b, dinit, dinit_b = _stage_directions(who, ode, tangents, B, batched, d, p)
+    K, dtheta, dtheta_b, dinit, dinit_b, hyper = _stage_all(who, ode, tangents, params, B, batched, d, p)
     if len(node) == 0:                                              # joint = marginal: nothing to launch
         return np.zeros(B), np.zeros((B, K)), batched
     plan, g, (p_obs, p_w, p_v, p_ind, n_obs, n_bobs) = _grid_plan("dalton_grid", ode, ode_weight, ode_init, t, slot, pairs, interrogate,
@@ -349,9 +390,15 @@ def _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
     d_th, d_x0 = plan.staged("dalton_grad", np.zeros(1) if dtheta is None else dtheta, np.zeros(1) if dinit is None else dinit)
     plan.set_seed(key)
     value, dvalue = plan.dev.empty((plan.B,)), plan.dev.empty((plan.B, K))
-    _lib.check(plan.dev.lib.rk_dalton_grid_jvp(plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), p_obs, p_w, p_v, p_ind, n_obs, n_bobs,
-                                               C.byref(g), K, None if dtheta is None else d_th.ptr, dtheta_b,
-                                               None if dinit is None else d_x0.ptr, dinit_b, value.ptr, dvalue.ptr))
+    head = (plan.dev.h, C.byref(plan.cfg), C.byref(plan.inp), p_obs, p_w, p_v, p_ind, n_obs, n_bobs, C.byref(g), K,
+            None if dtheta is None else d_th.ptr, dtheta_b, None if dinit is None else d_x0.ptr, dinit_b)
+    if hyper is None:                                               # (the kernel of every call without a reserved name)
+        _lib.check(plan.dev.lib.rk_dalton_grid_jvp(*head, value.ptr, dvalue.ptr))
+    else:
+        dls, dls_b, dlo, dlo_b = hyper
+        d_ls, d_lo = plan.staged("dalton_grad_hyper", np.zeros(1) if dls is None else dls, np.zeros(1) if dlo is None else dlo)
+        _lib.check(plan.dev.lib.rk_dalton_grid_jvp_hyper(*head, None if dls is None else d_ls.ptr, dls_b,
+                                                         None if dlo is None else d_lo.ptr, dlo_b, value.ptr, dvalue.ptr))
     return value.to_host(), dvalue.to_host(), batched
 
 
@@ -372,11 +419,21 @@ def dalton_grid_jvp(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, pri
     THE 1e-8 RULE (see ``dalton_grid``'s warning).  A forecast term that ``dalton_grid`` drops (|s| <= 1e-8) contributes nothing
     to the derivative either: where the value jumps, the derivative is that of the side the parameters are on.
 
+    THE TWO LOG-SCALES.  Two reserved names are directions too, unless ``params`` has a parameter of
+    that name (which then wins).  ``"log_sigma"``, shape (K, d) or (B, K, d): entry b is the rate of log sigma_b, the prior scale
+    of block b, under the scale law ``evidence_scale`` relies on -- every step's prior variance R_b is proportional to sigma_b^2
+    and Q does not depend on it, which is what ``prior_at = lambda h: ibm_init(h, p, sigma)`` satisfies; the initial variance is
+    not scaled.  A ``prior_at`` that is no such scale family gets the derivative of (Q, e^{2c} R) in c, and nothing else.
+    ``"log_obs_var"``, shape (K, d) or (B, K, d): entry b is the rate of a common log-scale of block b's observation variances,
+    at every observation, node 0 and node N included.  They mix with the other names in one call, with one K; a call that holds
+    one of them runs kernels of its own (``rk_dalton_grid_jvp_hyper``), every other call the kernels it ran before.
+
     Served: kalman_type "standard", n_bmeas = 1, n_bobs = 1, rodeo / schober / kramer, n_bstate 2 and 3 with n_block n_bstate^2
     <= 27; ``rodeo_amd.ode.fitzhugh_nagumo``, ``lorenz63`` and plain Python right-hand sides (a function, or ``ode.from_python``'s
     result: traced once more with generic parameters, ``rodeo_amd.trace.grad_from_python``, and built with hiprtc).
     NotImplementedError ("not built") before any device work: interrogate_chkrebtii, the square-root form, n_bobs > 1,
-    n_bmeas > 1, another size or right-hand side, and a direction in the prior ("sigma"), ``ode_weight`` or the data.  ValueError before any device work: an unknown name in ``tangents``, a direction of the wrong
+    n_bmeas > 1, another size or right-hand side, and a direction in the prior ("sigma", "prior_pars": use "log_sigma"),
+    ``ode_weight`` or the data ("obs_var": use "log_obs_var").  ValueError before any device work: an unknown name in ``tangents``, a direction of the wrong
     shape or non-finite, K = 0, and whatever ``dalton_grid`` refuses.  An empty observation set returns (0.0, zeros) without a
     launch.
     """
@@ -399,6 +456,8 @@ def _unit_directions(who, ode_fun, ode_weight, ode_init, wrt, init_jac, params):
             shapes.append((name, (d, p)))
         elif name in params:
             shapes.append((name, (int(np.shape(params[name])[-1]) if np.ndim(params[name]) else 1,)))
+        elif name in _GRAD_HYPER:
+            shapes.append((name, (d,)))
         else:
             shapes.append((name, (0,)))                             # (_grad_config raises for it)
     for name in init_jac:
@@ -448,7 +507,9 @@ def dalton_grid_grad(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, pr
     (B, d, p).  This is ``dalton_grid_jvp`` with the unit directions, in ONE launch; the direction count is the sum of the sizes.
     ``init_jac`` (optional): a dict name -> d ode_init / d param, shape (d, p, size) or (B, d, p, size); it is added into that
     parameter's ``ode_init`` direction, and the returned gradient is then the total derivative for an initial state that depends
-    on the parameters (the quick start's ``init(v0, t, theta)``).  Served, refused and the 1e-8 rule as ``dalton_grid_jvp``;
+    on the parameters (the quick start's ``init(v0, t, theta)``).  ``wrt`` may hold ``"log_sigma"`` and ``"log_obs_var"``
+    (``dalton_grid_jvp``'s two log-scales, d unit directions each): ``grad["log_sigma"]`` and ``grad["log_obs_var"]`` are (d,) or
+    (B, d); ``init_jac`` for either is a ValueError.  Served, refused and the 1e-8 rule as ``dalton_grid_jvp``;
     ValueError as well for a name in ``init_jac`` that is no parameter in ``wrt`` and for a Jacobian of the wrong shape.
     """
     who = "dalton_grid_grad"
@@ -475,7 +536,8 @@ def dalton_grad(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, inter
 
     The value agrees with ``dalton``'s to 1e-9 relative, NOT bit for bit: the time of node n is the table's ``linspace`` entry
     here and ``t_min + (t_max - t_min) (n + 1) / n_steps`` there, which may differ by an ulp (and ``dalton`` may run on the tiles).
-    Served, refused and the 1e-8 rule as ``dalton_grid_jvp``.
+    Served, refused and the 1e-8 rule as ``dalton_grid_jvp``; ``wrt`` may hold ``"log_sigma"`` (with ``prior_pars =
+    ibm_init(dt, p, sigma)``: the derivative in log sigma) and ``"log_obs_var"`` as in ``dalton_grid_grad``.
     """
     _grad_config("dalton_grad", ode_fun, ode_weight, interrogate, kalman_type, obs_weight, (wrt,) if isinstance(wrt, str) else tuple(wrt),
                  params)

@@ -21,7 +21,7 @@ data-adaptive solver on a non-uniform grid shared by the batch, every observatio
 ``rk_fenrir_grid_solve_mv``).
 ``fenrir_grid_jvp`` / ``fenrir_grid_grad`` / ``fenrir_grad`` (an addition, imported from this module likewise): ``fenrir_grid``'s
 value with its derivatives in the ODE parameters and the initial state, forward mode on the device (``rk_fenrir_grid_jvp``,
-DESIGN.md section 7 (23)).
+DESIGN.md section 7 (23)), and in the two log-scales ``"log_sigma"`` / ``"log_obs_var"`` (``rk_fenrir_grid_jvp_hyper``, section 7 (25)).
 """
 import collections
 import ctypes as C
@@ -233,7 +233,7 @@ def _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
     the directions staged on it and one rk_fenrir_grid_jvp per chunk of directions.  Returns (value (B,), dvalue (B, K), batched)."""
     from .. import grid
     from ..solve import _shape_rule
-    from .dalton import _grad_config, _obs_nodes, _stage_directions
+    from .dalton import _grad_config, _obs_nodes, _stage_all
     if not isinstance(tangents, dict):
         raise ValueError(f"{who}: tangents must be a dict name -> directions")
     ode_fun = _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight, list(tangents), params, sibling="fenrir_grid")
@@ -245,7 +245,8 @@ def _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
         raise ValueError(f"obs_weight must have shape (n_obs, {d}, n_bobs, {p})")
     sizes = _shape_rule(ode, ode_weight, ode_init, pairs[0], params)[-1]
     B, batched = (sizes[0], True) if sizes else (1, False)
-    K, dtheta, dtheta_b, dinit, dinit_b = _stage_directions(who, ode, tangents, B, batched, d, p)
+    K, dtheta, dtheta_b, dinit, dinit_b, hyper = _stage_all(who, ode, tangents, params, B, batched, d, p)
+    dls, dls_b, dlo, dlo_b = hyper if hyper is not None else (None, 0, None, 0)
     if len(node) == 0:                                              # nothing is conditioned on: no plan, no launch
         return np.zeros(B), np.zeros((B, K)), batched
     plan, g, (p_obs, p_w, p_v, p_node, n_obs, n_bobs) = _grid_plan("fenrir_grid", ode, ode_weight, ode_init, t, slot, pairs, interrogate,
@@ -260,9 +261,15 @@ def _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at,
         d_th, d_x0 = plan.staged(("fenrir_grad", ci), np.zeros(1) if dtheta is None else dtheta[k0:k1],
                                  np.zeros(1) if dinit is None else dinit[k0:k1])
         val, dval = plan.dev.empty((plan.B,)), plan.dev.empty((plan.B, k1 - k0))
-        plan.launch(plan.dev.lib.rk_fenrir_grid_jvp, key, _lib.MODE_FILTER, p_obs, p_w, p_v, p_node, n_obs, n_bobs, C.byref(g), k1 - k0,
-                    None if dtheta is None else d_th.ptr, dtheta_b, None if dinit is None else d_x0.ptr, dinit_b, ws.ptr, val.ptr,
-                    dval.ptr)
+        head = (key, _lib.MODE_FILTER, p_obs, p_w, p_v, p_node, n_obs, n_bobs, C.byref(g), k1 - k0,
+                None if dtheta is None else d_th.ptr, dtheta_b, None if dinit is None else d_x0.ptr, dinit_b)
+        if hyper is None:                                           # (the kernels of every call without a reserved name)
+            plan.launch(plan.dev.lib.rk_fenrir_grid_jvp, *head, ws.ptr, val.ptr, dval.ptr)
+        else:                                                       # (the hyper directions are sliced with the others)
+            d_ls, d_lo = plan.staged(("fenrir_grad_hyper", ci), np.zeros(1) if dls is None else dls[k0:k1],
+                                     np.zeros(1) if dlo is None else dlo[k0:k1])
+            plan.launch(plan.dev.lib.rk_fenrir_grid_jvp_hyper, *head, None if dls is None else d_ls.ptr, dls_b,
+                        None if dlo is None else d_lo.ptr, dlo_b, ws.ptr, val.ptr, dval.ptr)
         dvalue[:, k0:k1] = dval.to_host()
         if value is None:                                           # (every chunk recomputes the same primal filter)
             value = val.to_host()
@@ -290,6 +297,16 @@ def fenrir_grid_jvp(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, pri
     THE 1e-8 RULE.  A y term that ``fenrir_grid`` drops (a forecast variance |w| <= 1e-8, utils.py:60-78) contributes nothing to
     the derivative either: where the value jumps, the derivative is that of the side the parameters are on.
 
+    THE TWO LOG-SCALES.  Two reserved names are directions too, unless ``params`` has a parameter of
+    that name (which then wins).  ``"log_sigma"``, shape (K, d) or (B, K, d): entry b is the rate of log sigma_b, the prior scale
+    of block b, under the scale law ``evidence_scale`` relies on -- every step's prior variance R_b is proportional to sigma_b^2
+    and Q does not depend on it, which is what ``prior_at = lambda h: ibm_init(h, p, sigma)`` satisfies; the initial variance is
+    not scaled.  A ``prior_at`` that is no such scale family gets the derivative of (Q, e^{2c} R) in c, and nothing else.
+    ``"log_obs_var"``, shape (K, d) or (B, K, d): entry b is the rate of a common log-scale of block b's observation variances,
+    at every observation, node 0 and node N included.  They mix with the other names in one call, with one K; a call that holds
+    one of them runs kernels of its own (``rk_fenrir_grid_jvp_hyper``), every other call the kernels it ran before.
+    In chunked runs the two arrays are sliced with the others.
+
     Served: kalman_type "standard", n_bmeas = 1, n_bobs = 1, rodeo / schober / kramer, n_bstate 2 and 3 with n_block n_bstate^2
     <= 27; ``rodeo_amd.ode.fitzhugh_nagumo``, ``lorenz63`` and plain Python right-hand sides (a function, or ``ode.from_python``'s
     result: traced once more with generic parameters, ``rodeo_amd.trace.grad_from_python``, and built with hiprtc).
@@ -311,7 +328,9 @@ def fenrir_grid_grad(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, pr
     (B, d, p).  This is ``fenrir_grid_jvp`` with the unit directions; the direction count is the sum of the sizes.  ``wrt`` and
     ``init_jac`` are ``dalton_grid_grad``'s: ``init_jac`` is a dict name -> d ode_init / d param, shape (d, p, size) or (B, d, p, size),
     added into that parameter's ``ode_init`` direction, so that the returned gradient is the total derivative for an initial state
-    built from the parameters (the quick start's ``init(v0, t, theta)``).  Served, refused and the 1e-8 rule as ``fenrir_grid_jvp``;
+    built from the parameters (the quick start's ``init(v0, t, theta)``).  ``wrt`` may hold ``"log_sigma"`` and ``"log_obs_var"``
+    (``fenrir_grid_jvp``'s two log-scales, d unit directions each): ``grad["log_sigma"]`` and ``grad["log_obs_var"]`` are (d,) or
+    (B, d); ``init_jac`` for either is a ValueError.  Served, refused and the 1e-8 rule as ``fenrir_grid_jvp``;
     ValueError as well for a name in ``init_jac`` that is no parameter in ``wrt`` and for a Jacobian of the wrong shape.
     """
     from .dalton import _grad_config, _unit_directions
@@ -342,7 +361,8 @@ def fenrir_grad(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, inter
     The value agrees with ``fenrir``'s to the cross-route bar (1e-7 of max(1, |value|)), NOT bit for bit: the time of node n is
     the table's ``linspace`` entry here and ``t_min + (t_max - t_min) (n + 1) / n_steps`` there, which may differ by an ulp, and
     ``fenrir`` may run on the tiles or on stored predictions where this call re-evaluates them.  Served, refused and the 1e-8 rule
-    as ``fenrir_grid_jvp``.
+    as ``fenrir_grid_jvp``; ``wrt`` may hold ``"log_sigma"`` (with ``prior_pars = ibm_init(dt, p, sigma)``: the derivative in
+    log sigma) and ``"log_obs_var"`` as in ``fenrir_grid_grad``.
     """
     from .dalton import _grad_config
     _grad_config("fenrir_grad", ode_fun, ode_weight, interrogate, kalman_type, obs_weight, (wrt,) if isinstance(wrt, str) else tuple(wrt),
