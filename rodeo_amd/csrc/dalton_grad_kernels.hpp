@@ -22,7 +22,13 @@
 // observation variances:
 //   predict        Sigma.- = Q Sigma. Q^T + 2 l. R     (the step's own R as it is loaded; the initial variance is not scaled)
 //   y update       Omega. = w. Omega                    (node 0 included: -1/2 w. + 1/2 innov^2 w. / Omega)
-// It is a sibling kernel on the same device functions, not a flag of dalton_grid_jvp_kernel, whose code stays what it was.
+// All three kernel pairs of the gradient family (this one, fenrir_grad_kernels.hpp's and fenrir_grad.hip's) stay written out, two
+// kernels each on the same device functions.  As one `__device__
+// __forceinline__` body under `if constexpr (HYPER)` behind two one-line kernels, 23 of this pair's 24 instances keep their
+// registers, scratch 0 and fp64 instruction counts, and dalton_grid_jvp_hyper_kernel<Lorenz63, 3, rodeo>, which uses all 512
+// registers, spills 12 B per lane: with by-value and with by-reference parameters, with and without __restrict__ on the body, and
+// with the rates loaded in a loop of their own.  The Fenrir pairs kept their resources as one body and ran slower (DESIGN.md
+// section 7 (26)).
 #pragma once
 #include "rk_enums.hpp"
 #include "kalman_small.hpp"

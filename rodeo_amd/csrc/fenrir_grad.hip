@@ -6,9 +6,9 @@
 // backward Markov chain; with more than one block, magi_sum_kernel twice (launch_block_sum).  Standard form, n_bmeas = 1,
 // n_bobs = 1, built-in FitzHugh-Nagumo and Lorenz63, or a user right-hand side of the gradient kind (hiprtc, rhs_jit.hip's
 // JIT_FENRIR_GRAD, the forward kernel only: the backward kernel has no right-hand side).  rk_fenrir_grid_jvp_hyper (section 7 (25))
-// is the same entry with the log sigma / log observation variance directions, on the two hyper kernels.  The sizes test, the grid's staging,
-// the test of the output pointers and the launch patterns are grid_entry.hpp's; the rest of the configuration check is worded
-// for this entry alone ("not built: ...").
+// is the same entry with the log sigma / log observation variance directions, on the two hyper kernels (written out next to the
+// plain ones: section 7 (26)).  The configuration check (grad_check, shared with dalton_grad.hip and worded "not
+// built: ..."), the grid's staging, the test of the output pointers and the launch patterns are grid_entry.hpp's.
 #include "common.hpp"
 #include "rhs.hpp"
 #include "kalman_small.hpp"
@@ -156,7 +156,10 @@ __global__ void __launch_bounds__(64) fenrir_grid_jvp_bwd_kernel(SolveArgs a, Da
     if (k == 0) part[(size_t)blk * B + b] = acc;
 }
 
-// The hyper form, a sibling of the kernel above with its lanes, prefetch discipline and exits: the
+// The hyper form, a sibling of the kernel above with its lanes, prefetch discipline and exits,
+// written out: as one `__device__ __forceinline__` body under `if constexpr (HYPER)` behind two one-line kernels the pair kept its
+// registers (212 / 428 and 218 / 436), scratch 0 and fp64 instruction counts and ran 2.0 % (the kernel above) and 0.3 % (this one)
+// slower than the parent's, whose three block medians lie within 0.2 % (profiles/grad_shared_times.txt, section 7 (26)).  The
 // lane keeps its block's two rates, l. of log sigma and w. of the observation variances' log-scale; the re-evaluated pred[n + 1]
 // has Sigma.- = Q Sigma._f Q^T + 2 l. R (jvp_predict_scale), and an observation has Omega. = w. Omega (jvp_observe_rate).
 template <int P>
@@ -237,35 +240,12 @@ __global__ void __launch_bounds__(64) fenrir_grid_jvp_bwd_hyper_kernel(SolveArgs
 // ITG>, the backward kernel no more than fenrir_grid_bwd_kernel<P, false, 1>.  profiles/fenrir_grad_code_objects.txt has every
 // instance next to its yardstick (scripts/fenrir_grad_code_objects.py).  What is built is what jvp_interrogate's register set gave
 // DALTON: n_bstate 2 and 3 of FitzHugh-Nagumo and Lorenz63 (D P^2 <= 27).
-constexpr int FENRIR_GRAD_PMIN = 2, FENRIR_GRAD_PMAX = 3;
-template <class RHS>
-constexpr bool fenrir_grad_has_rhs() { return std::is_same<RHS, FitzHughNagumo>::value || std::is_same<RHS, Lorenz63>::value; }
+constexpr int FENRIR_GRAD_PMIN = GRAD_PMIN, FENRIR_GRAD_PMAX = 3;
 
-// Is this call served?  Decided on the configuration, n_bobs and n_dir alone: RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED.
+// Is this call served?  grid_entry.hpp's grad_check with this entry's item count (the backward kernel has one lane per block and
+// item), rule for a user right-hand side and range.
 static int fenrir_grad_check(const rk_solve_cfg* c, int n_bobs, int n_dir) {
-    const int rc = grid_sizes_check("fenrir_grid_jvp", c);               // (grid_entry.hpp; from here on the wording is this entry's own)
-    if (rc) return rc;
-    RK_REQUIRE(n_dir >= 1, RK_ERR_INVALID, "fenrir_grid_jvp: n_dir must be at least 1, got %d", n_dir);
-    RK_REQUIRE((long long)c->n_traj * n_dir * c->n_block <= 0x7fffffffLL, RK_ERR_INVALID,
-               "fenrir_grid_jvp: n_traj * n_dir * n_block = %lld exceeds 2^31 - 1", (long long)c->n_traj * n_dir * c->n_block);
-    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "fenrir_grid_jvp: cfg->flags must carry RK_FLAG_BATCH_MINOR");
-    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: RK_FLAG_STORE_PRED is not served");
-    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: kalman_type %d (standard only)",
-               c->kalman_type);
-    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_KRAMER, RK_ERR_UNSUPPORTED,
-               "fenrir_grid_jvp: not built: interrogate id %d (rodeo, schober, kramer)", c->interrogate);
-    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: n_bmeas = %d (1 only)", c->n_bmeas);
-    RK_REQUIRE(n_bobs == 1, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: n_bobs = %d (1 only: the derivative of the "
-               "eigendecomposition's cut-off density is out of scope)", n_bobs);
-    if (is_user_rhs(c->rhs_id)) return user_fenrir_grad_check(c);
-    bool known = false;
-    with_builtin_rhs(c->rhs_id, [&](auto rhs) { known = fenrir_grad_has_rhs<decltype(rhs)>(); });
-    RK_REQUIRE(known, RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: not built: rhs %d (fitzhugh_nagumo and lorenz63)", c->rhs_id);
-    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "fenrir_grid_jvp: rhs %d needs another n_block than %d",
-               c->rhs_id, c->n_block);
-    RK_REQUIRE(c->n_bstate >= FENRIR_GRAD_PMIN && c->n_bstate <= FENRIR_GRAD_PMAX, RK_ERR_UNSUPPORTED,
-               "fenrir_grid_jvp: not built: rhs %d at n_bstate %d (%d .. %d)", c->rhs_id, c->n_bstate, FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX);
-    return RK_OK;
+    return grad_check("fenrir_grid_jvp", c, n_bobs, n_dir, true, user_fenrir_grad_check, FENRIR_GRAD_PMAX);
 }
 
 // The hyper kernels ship by the same rule with their non-hyper siblings as yardsticks.  All fourteen
@@ -280,13 +260,10 @@ static size_t fenrir_grad_ws_bytes(const rk_solve_cfg* c, int n_dir) {
 // `hy`: null for rk_fenrir_grid_jvp, the hyper directions for rk_fenrir_grid_jvp_hyper (the hyper kernels)
 static int fenrir_grid_jvp_forward(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& ga, const JvpDirs& dir,
                                    const JvpHyper* hy, double* dmean, double* dvar) {
-    const auto user = [&] {
-        return hy ? user_fenrir_grad_hyper(h, c, a, ga, dir, *hy, a.B * dir.K, dmean, dvar)
-                  : user_fenrir_grad(h, c, a, ga, dir, a.B * dir.K, dmean, dvar);
-    };
+    const auto user = [&] { return user_fenrir_grad(h, c, a, ga, dir, hy, a.B * dir.K, dmean, dvar); };
     return launch_by_rhs(c, a, user, [&](auto rhs) {
         using RHS = decltype(rhs);
-        if constexpr (fenrir_grad_has_rhs<RHS>()) {
+        if constexpr (grad_has_rhs<RHS>()) {
             const LaunchGeom g = dalton_lane_geom(a.B * dir.K, false);      // 64 (trajectory, direction) items per wave
             if (hy)
                 return launch_fwd_instance<FENRIR_GRAD_PMIN, FENRIR_GRAD_PMAX, RK_INTERROGATE_RODEO, RK_INTERROGATE_KRAMER>(

@@ -91,7 +91,10 @@ __global__ void __launch_bounds__(64) fenrir_grid_jvp_fwd_kernel(SolveArgs a, Gr
     });
 }
 
-// The hyper form, a sibling of the kernel above on the same device functions: the item's rates l.[D]
+// The hyper form, a sibling of the kernel above on the same device functions, written out: as one
+// `__device__ __forceinline__` body under `if constexpr (HYPER)` behind two one-line kernels the pair kept its registers and fp64
+// instruction counts and ran 1.1 % (this kernel) and 2.3 % (the hyper one) slower than the parent's, whose three block medians
+// lie within 0.05 % (profiles/grad_shared_times.txt).  The item's rates l.[D]
 // of log sigma stay in registers, and Sigma.- = Q Sigma. Q^T + 2 l. R (jvp_predict_scale).  The forward pass has no observation:
 // the rates of the observation variances are the backward kernel's alone, and hy.dlobs is not read here.
 template <class RHS, int P, int ITG>

@@ -7,6 +7,7 @@
 // Also here: the bodies of what every entry on the grid shares (grid_entry.hpp) -- the pieces of the configuration check, the
 // staging of rk_grid_in and the test of the output pointers.
 #include <cmath>
+#include <cstdio>
 #include "common.hpp"
 #include "rhs.hpp"
 #include "solve_args.hpp"
@@ -96,6 +97,36 @@ int grid_rhs_check(const char* who, const rk_solve_cfg* c, const char* rule) {
     RK_REQUIRE(with_builtin_rhs(c->rhs_id, [](auto) {}), RK_ERR_UNSUPPORTED, "%s: unknown rhs_id %d", who, c->rhs_id);
     RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "%s: rhs %d needs another n_block than %d", who,
                c->rhs_id, c->n_block);
+    return RK_OK;
+}
+
+int grad_check(const char* who, const rk_solve_cfg* c, int n_bobs, int n_dir, bool per_block, int (*user_check)(const rk_solve_cfg*),
+               int pmax, const char* why_not) {
+    const int rc = grid_sizes_check(who, c);                             // (from here on the wording is the gradient entries' own)
+    if (rc) return rc;
+    RK_REQUIRE(n_dir >= 1, RK_ERR_INVALID, "%s: n_dir must be at least 1, got %d", who, n_dir);
+    const long long items = (long long)c->n_traj * n_dir * (per_block ? c->n_block : 1);
+    RK_REQUIRE(items <= 0x7fffffffLL, RK_ERR_INVALID, "%s: n_traj * n_dir%s = %lld exceeds 2^31 - 1", who, per_block ? " * n_block" : "",
+               items);
+    RK_REQUIRE((c->flags & RK_FLAG_BATCH_MINOR) != 0, RK_ERR_INVALID, "%s: cfg->flags must carry RK_FLAG_BATCH_MINOR", who);
+    RK_REQUIRE((c->flags & RK_FLAG_STORE_PRED) == 0, RK_ERR_UNSUPPORTED, "%s: RK_FLAG_STORE_PRED is not served", who);
+    RK_REQUIRE(c->kalman_type == RK_KALMAN_STANDARD, RK_ERR_UNSUPPORTED, "%s: not built: kalman_type %d (standard only)", who,
+               c->kalman_type);
+    RK_REQUIRE(c->interrogate >= RK_INTERROGATE_RODEO && c->interrogate <= RK_INTERROGATE_KRAMER, RK_ERR_UNSUPPORTED,
+               "%s: not built: interrogate id %d (rodeo, schober, kramer)", who, c->interrogate);
+    RK_REQUIRE(c->n_bmeas == 1, RK_ERR_UNSUPPORTED, "%s: not built: n_bmeas = %d (1 only)", who, c->n_bmeas);
+    RK_REQUIRE(n_bobs == 1, RK_ERR_UNSUPPORTED, "%s: not built: n_bobs = %d (1 only: the derivative of the "
+               "eigendecomposition's cut-off density is out of scope)", who, n_bobs);
+    if (is_user_rhs(c->rhs_id)) return user_check(c);
+    bool known = false;
+    with_builtin_rhs(c->rhs_id, [&](auto rhs) { known = grad_has_rhs<decltype(rhs)>(); });
+    RK_REQUIRE(known, RK_ERR_UNSUPPORTED, "%s: not built: rhs %d (fitzhugh_nagumo and lorenz63)", who, c->rhs_id);
+    RK_REQUIRE(builtin_has_n_block(c->rhs_id, c->n_block), RK_ERR_UNSUPPORTED, "%s: rhs %d needs another n_block than %d", who,
+               c->rhs_id, c->n_block);
+    char range[32];
+    snprintf(range, sizeof range, "%d .. %d", GRAD_PMIN, pmax);
+    RK_REQUIRE(c->n_bstate >= GRAD_PMIN && c->n_bstate <= pmax, RK_ERR_UNSUPPORTED, "%s: not built: rhs %d at n_bstate %d (%s)", who,
+               c->rhs_id, c->n_bstate, why_not ? why_not : range);
     return RK_OK;
 }
 

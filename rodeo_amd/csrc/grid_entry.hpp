@@ -38,6 +38,16 @@ int grid_served_check(const GridServed& s, const rk_solve_cfg* c);
 // `rule` the user check is another entry's (the forward pass is that entry's): its message under its name, prefixed with ours.
 int grid_rhs_check(const char* who, const rk_solve_cfg* c, const char* rule = nullptr);
 
+// The whole check of a gradient entry (dalton_grad.hip, fenrir_grad.hip), decided on the configuration, n_bobs and n_dir alone:
+// RK_OK, RK_ERR_INVALID or RK_ERR_UNSUPPORTED, worded "not built: ..." (tests/golden/grad_entry_refusals.npz).  What differs
+// between the two: the item limit -- n_traj * n_dir lanes, or with `per_block` that times n_block --, the check of a user
+// right-hand side, the last n_bstate served (from GRAD_PMIN on) and the parenthesis of the last refusal (null: the range).
+constexpr int GRAD_PMIN = 2;
+template <class RHS>
+constexpr bool grad_has_rhs() { return std::is_same<RHS, FitzHughNagumo>::value || std::is_same<RHS, Lorenz63>::value; }
+int grad_check(const char* who, const rk_solve_cfg* c, int n_bobs, int n_dir, bool per_block, int (*user_check)(const rk_solve_cfg*),
+               int pmax, const char* why_not = nullptr);
+
 // ---- the pointers of a served call -----------------------------------------------------------------------------------------
 // rk_grid_in's arrays and n_slots >= 1, and the kernels' view of it
 int grid_args(const char* who, const rk_grid_in* g, GridArgs& ga);

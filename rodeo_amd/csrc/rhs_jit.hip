@@ -561,13 +561,16 @@ int user_dalton_grad_check(const rk_solve_cfg* c) {
     return RK_OK;
 }
 
+// (`hy`: null for the plain kernel, else the hyper kernel with its second struct of directions)
 int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, const JvpDirs& dir,
-                     int n_items, double* value, double* dvalue) {
+                     const JvpHyper* hy, int n_items, double* value, double* dvalue) {
     const int rc = user_dalton_grad_check(c);
     if (rc) return rc;
     SolveArgs args = a;
-    void* params[] = {&args, (void*)&o, (void*)&g, (void*)&dir, &value, &dvalue};
-    return launch_jit(h, jit_key(JIT_DALTON_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, true), params);
+    void* plain[] = {&args, (void*)&o, (void*)&g, (void*)&dir, &value, &dvalue};
+    void* hyper[] = {&args, (void*)&o, (void*)&g, (void*)&dir, (void*)hy, &value, &dvalue};
+    return launch_jit(h, jit_key(hy ? JIT_DALTON_GRAD_HYPER : JIT_DALTON_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, true),
+                      hy ? hyper : plain);
 }
 
 // fenrir_grid_jvp's forward kernel around a user right-hand side of the gradient kind (fenrir_grad_kernels.hpp): dalton_grid_jvp's
@@ -582,32 +585,15 @@ int user_fenrir_grad_check(const rk_solve_cfg* c) {
     return RK_OK;
 }
 
-int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir, int n_items,
-                     double* dmean, double* dvar) {
+int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir, const JvpHyper* hy,
+                     int n_items, double* dmean, double* dvar) {
     const int rc = user_fenrir_grad_check(c);
     if (rc) return rc;
     SolveArgs args = a;
-    void* params[] = {&args, (void*)&g, (void*)&dir, &dmean, &dvar};
-    return launch_jit(h, jit_key(JIT_FENRIR_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, false), params);
-}
-
-// the hyper forms: the same checks, the hyper kernels with their second struct of directions
-int user_dalton_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g,
-                           const JvpDirs& dir, const JvpHyper& hy, int n_items, double* value, double* dvalue) {
-    const int rc = user_dalton_grad_check(c);
-    if (rc) return rc;
-    SolveArgs args = a;
-    void* params[] = {&args, (void*)&o, (void*)&g, (void*)&dir, (void*)&hy, &value, &dvalue};
-    return launch_jit(h, jit_key(JIT_DALTON_GRAD_HYPER, c->rhs_id, c), dalton_lane_geom(n_items, true), params);
-}
-
-int user_fenrir_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir,
-                           const JvpHyper& hy, int n_items, double* dmean, double* dvar) {
-    const int rc = user_fenrir_grad_check(c);
-    if (rc) return rc;
-    SolveArgs args = a;
-    void* params[] = {&args, (void*)&g, (void*)&dir, (void*)&hy, &dmean, &dvar};
-    return launch_jit(h, jit_key(JIT_FENRIR_GRAD_HYPER, c->rhs_id, c), dalton_lane_geom(n_items, false), params);
+    void* plain[] = {&args, (void*)&g, (void*)&dir, &dmean, &dvar};
+    void* hyper[] = {&args, (void*)&g, (void*)&dir, (void*)hy, &dmean, &dvar};
+    return launch_jit(h, jit_key(hy ? JIT_FENRIR_GRAD_HYPER : JIT_FENRIR_GRAD, c->rhs_id, c), dalton_lane_geom(n_items, false),
+                      hy ? hyper : plain);
 }
 
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
@@ -747,52 +733,32 @@ int rk_rhs_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) 
     return rc;
 }
 
-// the gradient kind's build for a registered right-hand side, without a device (what rk_rhs_compile_check is for the solver)
+// The gradient kinds' build for a registered right-hand side, without a device (what rk_rhs_compile_check is for the solver).
+// `builtin_too` (Fenrir's two): a built-in id builds the kernel around that right-hand side, which shows without a device that
+// fenrir_grad_kernels.hpp is RTC-safe (a built-in one without rhs_generic fails like a source of the solver's kind).
+static int grad_compile_check(JitKind kind, bool builtin_too, int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
+    if (!(builtin_too && builtin_rhs_type(rhs_id))) {
+        const UserRhs* u;
+        const int rc = user_rhs(rhs_id, &u);
+        if (rc) return rc;
+    }
+    rk_solve_cfg c{};
+    c.n_bstate = n_bstate;
+    c.interrogate = interrogate;
+    return jit_lookup(jit_key(kind, rhs_id, &c), nullptr, nullptr);
+}
+
 int rk_dalton_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
-    const UserRhs* u;
-    const int rc = user_rhs(rhs_id, &u);
-    if (rc) return rc;
-    rk_solve_cfg c{};
-    c.n_bstate = n_bstate;
-    c.interrogate = interrogate;
-    return jit_lookup(jit_key(JIT_DALTON_GRAD, rhs_id, &c), nullptr, nullptr);
+    return grad_compile_check(JIT_DALTON_GRAD, false, rhs_id, n_bstate, interrogate);
 }
-
-// the same for the hyper forms (rk_dalton_grid_jvp_hyper / rk_fenrir_grid_jvp_hyper's forward kernel)
 int rk_dalton_grad_hyper_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
-    const UserRhs* u;
-    const int rc = user_rhs(rhs_id, &u);
-    if (rc) return rc;
-    rk_solve_cfg c{};
-    c.n_bstate = n_bstate;
-    c.interrogate = interrogate;
-    return jit_lookup(jit_key(JIT_DALTON_GRAD_HYPER, rhs_id, &c), nullptr, nullptr);
+    return grad_compile_check(JIT_DALTON_GRAD_HYPER, false, rhs_id, n_bstate, interrogate);
 }
-
-int rk_fenrir_grad_hyper_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
-    if (!builtin_rhs_type(rhs_id)) {
-        const UserRhs* u;
-        const int rc = user_rhs(rhs_id, &u);
-        if (rc) return rc;
-    }
-    rk_solve_cfg c{};
-    c.n_bstate = n_bstate;
-    c.interrogate = interrogate;
-    return jit_lookup(jit_key(JIT_FENRIR_GRAD_HYPER, rhs_id, &c), nullptr, nullptr);
-}
-
-// the same for fenrir_grid_jvp's forward kernel; a built-in id builds the kernel around that right-hand side, which shows without
-// a device that fenrir_grad_kernels.hpp is RTC-safe (a built-in one without rhs_generic fails like a source of the solver's kind)
 int rk_fenrir_grad_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
-    if (!builtin_rhs_type(rhs_id)) {
-        const UserRhs* u;
-        const int rc = user_rhs(rhs_id, &u);
-        if (rc) return rc;
-    }
-    rk_solve_cfg c{};
-    c.n_bstate = n_bstate;
-    c.interrogate = interrogate;
-    return jit_lookup(jit_key(JIT_FENRIR_GRAD, rhs_id, &c), nullptr, nullptr);
+    return grad_compile_check(JIT_FENRIR_GRAD, true, rhs_id, n_bstate, interrogate);
+}
+int rk_fenrir_grad_hyper_compile_check(int32_t rhs_id, int32_t n_bstate, int32_t interrogate) {
+    return grad_compile_check(JIT_FENRIR_GRAD_HYPER, true, rhs_id, n_bstate, interrogate);
 }
 
 }  // extern "C"

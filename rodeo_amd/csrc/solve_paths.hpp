@@ -118,18 +118,14 @@ int user_dalton_grid(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, con
 // the gradient kind (AutoJacG around a struct with rhs_generic: rodeo_amd.trace.trace_grad_source), else the build fails
 struct JvpDirs;
 struct JvpHyper;
+// `hy`: null for rk_dalton_grid_jvp, the hyper directions of rk_dalton_grid_jvp_hyper (the same check, the hyper kernel)
 int user_dalton_grad_check(const rk_solve_cfg* c);
 int user_dalton_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g, const JvpDirs& dir,
-                     int n_items, double* value, double* dvalue);
+                     const JvpHyper* hy, int n_items, double* value, double* dvalue);
 // fenrir_grid_jvp: the same for its forward kernel (fenrir_grad.hip); dmean / dvar are the tangent records of the n_items items
 int user_fenrir_grad_check(const rk_solve_cfg* c);
-int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir, int n_items,
-                     double* dmean, double* dvar);
-// the hyper forms of the two (rk_dalton_grid_jvp_hyper / rk_fenrir_grid_jvp_hyper): the same checks, the hyper kernels
-int user_dalton_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const DaltonObs& o, const GridArgs& g,
-                           const JvpDirs& dir, const JvpHyper& hy, int n_items, double* value, double* dvalue);
-int user_fenrir_grad_hyper(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir,
-                           const JvpHyper& hy, int n_items, double* dmean, double* dvar);
+int user_fenrir_grad(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, const GridArgs& g, const JvpDirs& dir, const JvpHyper* hy,
+                     int n_items, double* dmean, double* dvar);
 int user_interrogate(rk_handle h, const rk_solve_cfg* c, const SolveArgs& a, double t, int step, const double* mp,
                      const double* vp, double* wm, double* mm_, double* vm);
 // observation models of DALTON's non-Gaussian form (rk_register_obs_source) and the hiprtc kernels built around them

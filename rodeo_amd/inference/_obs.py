@@ -119,6 +119,23 @@ def _stack_pairs(pairs, B, force=0):
     return tuple(out), batched
 
 
+def _obs_nodes(who, t, obs_times, n_obs):
+    """The node of every observation time on the checked grid ``t`` (int32, strictly increasing), or the ValueError."""
+    from ..grid import _times, nodes_of_times
+    if np.shape(obs_times) != (n_obs,):
+        raise ValueError(f"{who}: obs_times must have shape ({n_obs},), got {np.shape(obs_times)}")
+    x = _times(obs_times, t, who)
+    if np.any(np.diff(x) <= 0):
+        raise ValueError(f"{who}: obs_times must be strictly increasing")
+    node, on = nodes_of_times(t, x)
+    if not np.all(on):
+        raise ValueError(f"{who}: the observation time {float(x[~on][0])!r} is no node of t_grid (within EVAL_AT_NODE_TOL of the shorter "
+                         "adjacent step); rodeo_amd.grid_with_times(t_grid, obs_times) returns a grid that has every time as a node")
+    if np.any(np.diff(node) == 0):
+        raise ValueError(f"{who}: two observation times are the same node of t_grid (within EVAL_AT_NODE_TOL of a step)")
+    return node.astype(np.int32)
+
+
 def _grid_plan(obs_slot, ode, ode_weight, ode_init, t, slot, pairs, interrogate, kalman_type, params, obs, D, Om, node, n_bobs):
     """
     What the likelihoods on a non-uniform grid (``dalton_grid``, ``fenrir_grid`` and their solvers) do once nothing is left to

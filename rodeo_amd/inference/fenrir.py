@@ -28,7 +28,10 @@ import ctypes as C
 import os
 import numpy as np
 from .. import _lib
-from ..solve import SolvePlan, cached_plan
+from ..solve import SolvePlan, cached_plan, _shape_rule
+from . import _obs
+from ._grad import _grad_config, _grad_of, _wrt_directions
+from .dalton import _stage_all                                      # (lives there: see its comment)
 from ._obs import _at_inputs, _check_obs, _grid_plan, _served, _stage_at
 from .logpost import obs_index
 
@@ -142,9 +145,8 @@ def _on_grid(who, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, 
     empty observation set.
     """
     from .. import grid
-    from .dalton import _obs_nodes
     obs, D, Om, n_bobs = _check_obs(obs_data, obs_weight, obs_var)
-    node = _obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
+    node = _obs._obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])        # (by attribute: tests/test_fenrir_grid_host.py wants no _obs_nodes of this module's own)
     ode, t, slot, pairs = grid._refusals(who, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
     d, p = (int(n) for n in (np.shape(ode_weight)[-3], np.shape(ode_weight)[-1]))
     if D.shape[1:] != (d, n_bobs, p):
@@ -228,17 +230,15 @@ _GRAD_WORKSPACE_BYTES = 2 ** 32
 
 def _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times, obs_weight, obs_var, tangents,
          kalman_type, params):
-    """``fenrir_grid_jvp``'s body: the gradient refusals (``dalton.py``'s helpers under this call's name), then ``fenrir_grid``'s in
+    """``fenrir_grid_jvp``'s body: the gradient refusals (``_grad.py``'s helpers under this call's name), then ``fenrir_grid``'s in
     its order, the directions, and -- unless the observation set is empty -- the cached plan with the grid, the observations and
     the directions staged on it and one rk_fenrir_grid_jvp per chunk of directions.  Returns (value (B,), dvalue (B, K), batched)."""
     from .. import grid
-    from ..solve import _shape_rule
-    from .dalton import _grad_config, _obs_nodes, _stage_all
     if not isinstance(tangents, dict):
         raise ValueError(f"{who}: tangents must be a dict name -> directions")
     ode_fun = _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight, list(tangents), params, sibling="fenrir_grid")
     obs, D, Om, n_bobs = _check_obs(obs_data, obs_weight, obs_var)
-    node = _obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
+    node = _obs._obs_nodes(who, grid._grid(t_grid), obs_times, obs.shape[0])
     ode, t, slot, pairs = grid._refusals(who, ode_fun, ode_weight, ode_init, t_grid, prior_at, kalman_type, params)
     d, p = int(np.shape(ode_weight)[-3]), int(np.shape(ode_weight)[-1])
     if D.shape[1:] != (d, n_bobs, p):
@@ -333,20 +333,12 @@ def fenrir_grid_grad(key, ode_fun, ode_weight, ode_init, t_grid, interrogate, pr
     (B, d); ``init_jac`` for either is a ValueError.  Served, refused and the 1e-8 rule as ``fenrir_grid_jvp``;
     ValueError as well for a name in ``init_jac`` that is no parameter in ``wrt`` and for a Jacobian of the wrong shape.
     """
-    from .dalton import _grad_config, _unit_directions
     who = "fenrir_grid_grad"
-    _grad_config(who, ode_fun, ode_weight, interrogate, kalman_type, obs_weight, (wrt,) if isinstance(wrt, str) else tuple(wrt), params,
-                 sibling="fenrir_grid")
-    tangents, layout = _unit_directions(who, ode_fun, ode_weight, ode_init, wrt, init_jac, params)
-    if not tangents:
-        raise ValueError(f"{who}: wrt is empty (K = 0)")
+    tangents, layout = _wrt_directions(who, "fenrir_grid", ode_fun, ode_weight, ode_init, interrogate, kalman_type, obs_weight, wrt,
+                                       init_jac, params)
     value, dvalue, batched = _jvp(who, key, ode_fun, ode_weight, ode_init, t_grid, interrogate, prior_at, obs_data, obs_times,
                                   obs_weight, obs_var, tangents, kalman_type, params)
-    grad = {}
-    for name, k0, shape in layout:
-        gr = dvalue[:, k0:k0 + int(np.prod(shape))].reshape((-1,) + shape)
-        grad[name] = gr if batched else gr[0]
-    return FenrirGrad(value if batched else float(value[0]), grad)
+    return FenrirGrad(value if batched else float(value[0]), _grad_of(dvalue, layout, batched))
 
 
 def fenrir_grad(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, interrogate, prior_pars,
@@ -364,7 +356,6 @@ def fenrir_grad(key, ode_fun, ode_weight, ode_init, t_min, t_max, n_steps, inter
     as ``fenrir_grid_jvp``; ``wrt`` may hold ``"log_sigma"`` (with ``prior_pars = ibm_init(dt, p, sigma)``: the derivative in
     log sigma) and ``"log_obs_var"`` as in ``fenrir_grid_grad``.
     """
-    from .dalton import _grad_config
     _grad_config("fenrir_grad", ode_fun, ode_weight, interrogate, kalman_type, obs_weight, (wrt,) if isinstance(wrt, str) else tuple(wrt),
                  params, sibling="fenrir_grid")
     obs, D, Om, _ = _check_obs(obs_data, obs_weight, obs_var)
